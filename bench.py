@@ -11,10 +11,13 @@ Inputs are resident in HBM before the timed region.
 What is timed, however the script is invoked:
   1. state preparation (untimed, mandatory): every env is stepped to its steady-state occupancy — max(1500, 5 x load)
      steps, plus --warmup more; the mean number of active services is then checked (cfg2: 288 +- 5 %) and reported as
-     `state_before`.  --warmup adds to this preparation, it never replaces it.
-  2. the timed block: EXACTLY --steps steps, bracketed by a barrier + device synchronisation on both sides, max over ranks.
-     The block is repeated until >= 5 s have been timed (--min-timed-s; at least 3 blocks); `value` is the median block, `timed_region_s` the
-     sum.  `roofline.achieved` comes from the HIP-event duration of the same launches.
+     `state_before`; then max(1, min(50, 1000 // K)) runs of K = --steps steps (the timed run's own launch shape) lead up to
+     the timed run.  --warmup adds to this preparation, it never replaces it.
+  2. the timed region: EXACTLY --steps steps, one block bracketed by a barrier + device synchronisation on both sides, max
+     over ranks.  `roofline.achieved` comes from the HIP-event duration of the same launches.
+--dump-outputs DIR then writes what the timed run() left for its caller to read back (the batch state after its last step)
+as DIR/<name>.npy, float64 / float32, <= 64 MB in all: see dump_outputs().  The inputs (seeds, preparation steps) depend on
+the arguments only, so two builds run with the same arguments can be compared array for array.
 N > 1: one process per GPU, every rank owns its own 65 536 envs (weak scaling, no collective on the data path; the barrier
 and the max-over-ranks time go through a gloo group — the data path needs no RCCL).  Started under torchrun the script is one
 rank; started by hand with --gpus N > 1 it launches the N ranks itself (fresh child processes, before any GPU call) and
@@ -30,7 +33,6 @@ import argparse
 import json
 import math
 import os
-import statistics
 import sys
 import time
 
@@ -82,6 +84,38 @@ def algorithmic_bytes(env, mean_hops, active):
     lg = 64 * math.ceil(math.log2(max(active, 2)))
     fixed = 116 + 128 + 81 + (8 * env.obs_dim if env.obs_dim else 0)
     return dict(scan=scan, step=scan + 32 * mean_hops + 128 * mean_hops + lg + fixed)
+
+
+DUMP_BUDGET = 60 << 20  # bytes of array data --dump-outputs may write over all ranks (<= 64 MB with the .npy headers)
+
+
+def dump_outputs(env, out_dir, env_base, prefix="", budget=DUMP_BUDGET):
+    """What a caller of run() reads back after its last step, written as out_dir/<prefix><name>.npy:
+      counters [n, 8], services [n, 6], net_stats [n, 4], active [n] (+ observation [n, obs_dim] where the family has one),
+        rows env_index [n];
+      link_stats [m, 4, links] and slots [m, cores, links, slots] (0/1), rows sample_env_index [m].
+    Every array is float64 (integers are exact there) except the slot maps (float32).  Each of the two groups gets half the
+    budget: n is every env of the batch when it fits, else a fixed seeded sample; m a smaller one of the same draw.  The
+    env indices are global (env_base + the batch's own index)."""
+    os.makedirs(out_dir, exist_ok=True)
+    B = env.num_envs
+    small = dict(counters=env.counters(), services=env.services(), net_stats=env.net_stats_all(), active=env.active())
+    if env.obs_dim:
+        small["observation"] = env.observation()
+    small = {k: np.asarray(v, np.float64) for k, v in small.items()}
+    C, E, S = env.num_spatial_resources, env.topology.n_links, env.num_spectrum_resources
+    order = np.random.RandomState(0).permutation(B)
+    n = min(B, (budget // 2) // (8 * sum(a[0].size for a in small.values()) + 8))
+    m = min(n, (budget // 2) // (8 * 4 * E + 4 * C * E * S + 8))
+    rows = np.arange(B) if n == B else np.sort(order[:n])
+    sample = np.sort(order[:m])
+    out = {k: v[rows] for k, v in small.items()}
+    out["env_index"] = (env_base + rows).astype(np.float64)
+    out["link_stats"] = env.link_stats_all()[sample]
+    out["slots"] = np.stack([env.slots(int(e)) for e in sample]).astype(np.float32)
+    out["sample_env_index"] = (env_base + sample).astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, prefix + k + ".npy"), np.ascontiguousarray(v))
 
 
 def free_port():
@@ -176,8 +210,9 @@ def main():
                          "strong: --batch envs in total, cut into contiguous blocks of env indices over the ranks "
                          "(optical_rl_gym_amd.sharding.shard_range) — the headline batch of 65 536 at 1/2/4/8 GPUs")
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
-    ap.add_argument("--min-timed-s", type=float, default=5.0, help="repeat the timed block until this much has been timed")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the batch state they computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--device", type=int, default=None,
                     help="put EVERY rank on this GPU index (default: rank r on GPU LOCAL_RANK); with --gpus N > 1 this is a "
                          "functional check of the N-rank path on one device, not a scaling measurement")
@@ -259,41 +294,38 @@ def main():
     if expected is not None and abs(active_before - expected) > 0.05 * expected:
         raise SystemExit("bench: state preparation did not reach the steady state (mean active services %.1f, expected %.1f)"
                          % (active_before, expected))
+    # ... ending with runs of the timed length, ~1 000 steps of them, right up to the timed run: a 20-step cfg2 run measured 5-9 %
+    # slower after the 128-step launches, a pause or a read-back like the one above than within an unbroken series of them
+    for _ in range(max(1, min(50, 1000 // args.steps))):
+        env.run(policy, args.steps)
+        prep_steps += args.steps
 
-    # ---- 2. timed blocks of EXACTLY --steps steps ----------------------------------------------------------------
-    blocks = []  # (wall seconds max over ranks, RunStats)
-    own = []     # this rank's own block times (reported per rank; `value` uses the max over ranks of every block)
-    timed = 0.0
-    while len(blocks) < 3 or timed < args.min_timed_s:
-        barrier()
-        t0 = time.perf_counter()
-        st_run = env.run(policy, args.steps)   # policy + step, entirely on the device
-        device_sync()
-        elapsed = time.perf_counter() - t0     # this rank's K steps, device idle again
-        own.append(elapsed)
-        if dist is not None:
-            # the closing barrier, then the MAX over ranks of the per-rank times: the slowest rank's K steps.  (The clock is
-            # read before the gloo barrier — a TCP round trip among N processes takes as long as several of the 20-step
-            # blocks' steps and is not part of any rank's work; all ranks left the opening barrier together.)
-            dist.barrier()
-            t = torch.tensor([elapsed], dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            elapsed = float(t.item())
-        blocks.append((elapsed, st_run.ms_total, int(st_run.launches), st_run.n_kernels == 1 and st_run.kernels()[0][0] == "k_persist"))
-        timed += elapsed
-        if len(blocks) >= 20000:
-            break
-    per_rank = [dict(rank=rank, device=dev_index, envs=B, env_steps_per_s=round(B * args.steps / statistics.median(own), 1))]
+    # ---- 2. the timed region: EXACTLY --steps steps -----------------------------------------------------------------
+    barrier()
+    t0 = time.perf_counter()
+    st_run = env.run(policy, args.steps)   # policy + step, entirely on the device
+    device_sync()
+    own = elapsed = time.perf_counter() - t0  # this rank's K steps, device idle again
+    if dist is not None:
+        # the closing barrier, then the MAX over ranks of the per-rank times: the slowest rank's K steps.  (The clock is
+        # read before the gloo barrier — a TCP round trip among N processes takes as long as several of the 20-step
+        # blocks' steps and is not part of any rank's work; all ranks left the opening barrier together.)
+        dist.barrier()
+        t = torch.tensor([elapsed], dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    blk = (elapsed, st_run.ms_total, int(st_run.launches), st_run.n_kernels == 1 and st_run.kernels()[0][0] == "k_persist")
+    timed = elapsed
+    if args.dump_outputs:  # before anything below steps the batch again
+        dump_outputs(env, args.dump_outputs, lo, prefix="rank%d_" % rank if world > 1 else "", budget=DUMP_BUDGET // world)
+    per_rank = [dict(rank=rank, device=dev_index, envs=B, env_steps_per_s=round(B * args.steps / own, 1))]
     if dist is not None:
         gathered = [None] * world
         dist.all_gather_object(gathered, per_rank[0])
         per_rank = gathered
-    walls = sorted(b[0] for b in blocks)
-    elapsed = statistics.median(walls)
-    med = min(blocks, key=lambda b: abs(b[0] - elapsed))
     active_after = float(env.active().mean())
     if abs(active_after - active_before) > 0.05 * max(active_before, 1.0):
-        raise SystemExit("bench: the state drifted during the timed blocks (%.1f -> %.1f active services)" % (active_before, active_after))
+        raise SystemExit("bench: the state drifted during the timed steps (%.1f -> %.1f active services)" % (active_before, active_after))
 
     # ---- roofline of the dominant kernel, live: algorithmic bytes of the steps a launch covers / HIP-event duration ---
     processed, accepted = env.totals()
@@ -301,9 +333,9 @@ def main():
     h0 = t.path_hops[:, :, 0]
     mean_hops = float(h0[h0 > 0].mean())
     alg = algorithmic_bytes(env, mean_hops, active_after)
-    persistent = med[3]
-    launches = max(med[2], 1) if persistent else args.steps
-    ms_launch = med[1] / launches                      # HIP events on the batch's stream around the timed block
+    persistent = blk[3]
+    launches = max(blk[2], 1) if persistent else args.steps
+    ms_launch = blk[1] / launches                      # HIP events on the batch's stream around the timed block
     steps_per_launch = args.steps / launches
     bytes_per_launch = alg["step"] * B * steps_per_launch
     ach = bytes_per_launch / (ms_launch * 1e-3) / 1e9
@@ -327,7 +359,7 @@ def main():
         # counters taken over launches of the SAME length as the timed ones where there are such (cfg2: ten 20-step launches for
         # the driver's invocation), else over 128-step launches, scaled per step (then `traffic_scaled_from_steps` says so: the
         # window fill / write-back of a launch is amortised over 128 steps there)
-        k = tj.get("kernels", {}).get("%s_steps%d" % (kernel, int(round(args.steps / max(med[2], 1)))) if med[3] else kernel) \
+        k = tj.get("kernels", {}).get("%s_steps%d" % (kernel, int(round(args.steps / max(blk[2], 1)))) if blk[3] else kernel) \
             or tj.get("kernels", {}).get(kernel)
         same_state = abs(tj.get("mean_active_services", -1e9) - active_after) <= 0.05 * active_after
         if k and tj.get("workload") == args.workload and tj.get("batch") == B and same_state and \
@@ -511,8 +543,8 @@ def main():
                                        (["k_stats (the launch's deferred bookkeeping, one lane per env, behind every k_persist launch)"]
                                         if persistent else []),
                        "kernel_form": kernel_form},
-            "timing": {"blocks": len(blocks), "timed_region_s": round(timed, 4), "block_s_median": round(elapsed, 6),
-                       "block_s_min": round(walls[0], 6), "block_s_max": round(walls[-1], 6),
+            "timing": {"blocks": 1, "timed_region_s": round(timed, 4), "block_s_median": round(elapsed, 6),
+                       "block_s_min": round(elapsed, 6), "block_s_max": round(elapsed, 6),
                        "state_preparation_steps": prep_steps},
             "state_before": {"mean_active_services": round(active_before, 1)},
             "state": {"mean_active_services": round(active_after, 1),

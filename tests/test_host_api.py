@@ -1,12 +1,14 @@
 """Host-side mirrors of the reference interface (gym-shaped envs, heuristics, evaluate_heuristic, VecEnv glue),
 driven through the CPU oracle so they run without a GPU.  Expected numbers are the reference's own outputs for its
 tests/ scripts (reproduced in tests/golden by oracle/gen_golden.py)."""
+import os
+
 import numpy as np
 import pytest
 
 import optical_rl_gym_amd as orl
 from optical_rl_gym_amd.vec_env import OpticalVecEnv
-from tests.helpers import load_golden
+from tests.helpers import GOLDEN, load_golden
 from tests.oracle_backend import OracleBackend
 
 RMSA_KW = dict(allow_rejection=True, load=50, mean_service_holding_time=25, episode_length=100,
@@ -289,11 +291,9 @@ def test_reference_pickle_loader(tmp_path):
     for name in ("n_paths", "path_hops", "path_links", "path_length", "path_best_mod", "edge_iter_order", "link_length", "link_nodes"):
         assert np.array_equal(getattr(got, name), getattr(t, name)), name
     assert got.node_names == t.node_names and [m.name for m in got.modulations] == [m.name for m in t.modulations]
-    ref = "/root/reference/examples/topologies/nsfnet_chen_5-paths_6-modulations.h5"
-    import os
-    if os.path.exists(ref):  # build container only: the reference's own file
-        real = topology_io.load_reference_pickle(ref)
-        assert np.array_equal(real.path_links, t.path_links) and np.array_equal(real.path_length, t.path_length)
+    # the reference's own file (examples/topologies/nsfnet_chen_5-paths_6-modulations.h5), stored as a fixture
+    real = topology_io.load_reference_pickle(os.path.join(GOLDEN, "nsfnet_chen_5-paths_6-modulations.h5"))
+    assert np.array_equal(real.path_links, t.path_links) and np.array_equal(real.path_length, t.path_length)
 
 
 def test_action_spaces_of_every_family_and_start_environment():

@@ -5,7 +5,7 @@ O=$R/gpurun_out/${1:-ab_forms}
 mkdir -p $O
 run() {  # label, workload, batch, steps, env...
   l=$1; w=$2; b=$3; s=$4; shift 4
-  env "$@" python3 $R/bench.py --gpus 1 --workload $w --batch $b --steps $s --no-cpu-baseline --min-timed-s 0.7 > $O/$l.json 2> $O/$l.err
+  env "$@" python3 $R/bench.py --gpus 1 --workload $w --batch $b --steps $s --no-cpu-baseline > $O/$l.json 2> $O/$l.err
   python3 -c "import json; d=json.load(open('$O/$l.json')); print('$l', d['value'], d['ms_per_step'])" || tail -3 $O/$l.err
 }
 for w in cfg1 cfg3; do for s in 20 300; do for v in 4 5; do

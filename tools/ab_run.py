@@ -18,7 +18,7 @@ for spec in sys.argv[2:]:
         if kv.strip():
             k, v = kv.split("=", 1)
             env[k.strip()] = v
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--no-cpu-baseline", "--min-timed-s", "1.5"] + args.split()
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--no-cpu-baseline"] + args.split()
     p = subprocess.run(cmd, env=env, capture_output=True, text=True)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     if p.returncode != 0 or not lines:

@@ -4,7 +4,7 @@ one built for the configuration), and — RMSA / DeepRMSA — a loop of agent-dr
 run.  usage: fuzz_cross.py [seed] [cases]"""
 import os, sys
 os.environ.setdefault("ORL_JIT_SPEC", "0")
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import optical_rl_gym_amd as orl
 

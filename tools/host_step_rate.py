@@ -1,6 +1,6 @@
 """Host-driven policy()+step() rate for small batches under each step implementation (usage: host_step_rate.py)."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import optical_rl_gym_amd as orl
 kw = dict(load=300, mean_service_holding_time=25, episode_length=1000, num_spectrum_resources=320)
 for B in (1, 64, 1024, 4096):

@@ -17,7 +17,11 @@ example is the data path, not the learning algorithm — the SAP-FF heuristic's 
 `--halves`: the envs as TWO batches of num_envs / 2, each with its own stream and its own captured rollout, replayed side by side:
 the step kernel of one half (bound by memory latency, half of the vector ALU idle) overlaps the network's GEMMs of the other.
 
-    python examples/deeprmsa_agent_on_gpu.py [num_envs] [updates] [--eager] [--halves]
+`--mask`: action masking — after every step the batch's action-mask kernel is queued on the same stream (inside the captured
+rollout), and the logits of actions that cannot provision the pending service are set to -inf before sampling (and in the
+update, from the stored masks).  Without it the loop is unchanged.
+
+    python examples/deeprmsa_agent_on_gpu.py [num_envs] [updates] [--eager] [--halves] [--mask]
 """
 import os
 import sys
@@ -32,6 +36,7 @@ import optical_rl_gym_amd as orl  # noqa: E402
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 EAGER = "--eager" in sys.argv
 HALVES = "--halves" in sys.argv and not EAGER
+MASK = "--mask" in sys.argv
 B = int(args[0]) if len(args) > 0 else 4096
 UPDATES = int(args[1]) if len(args) > 1 else 60
 T = 32  # steps per rollout
@@ -57,6 +62,7 @@ opt = torch.optim.Adam(net.parameters(), lr=3e-4)
 obs_buf = torch.zeros((T, B, env.obs_dim), device=dev)  # the rollout of all envs; each part writes its columns
 act_buf = torch.zeros((T, B), dtype=torch.long, device=dev)
 rew_buf = torch.zeros((T, B), device=dev)
+mask_buf = torch.ones((T, B, n_actions), dtype=torch.bool, device=dev) if MASK else None  # the mask each action was sampled under
 
 
 class Part:
@@ -67,6 +73,9 @@ class Part:
         self.obs, self.rew, self.done, self.act = (e.device_tensor(k) for k in ("obs", "reward", "done", "actions"))
         e.reset()
         e.observation()  # the kernels keep `obs` current from here on
+        if MASK:
+            e.action_mask(fetch=False)  # (allocates the mask buffer: outside the capture)
+            self.mask = e.device_tensor("action_mask")[:, :n_actions]  # bool view at the device pitch, no copy
         self.stream = e.torch_stream()
         self.graph = None
 
@@ -76,6 +85,9 @@ class Part:
             x = self.obs.float()
             obs_buf[t, self.lo:self.hi].copy_(x)
             logits = net(x)
+            if MASK:
+                mask_buf[t, self.lo:self.hi].copy_(self.mask)
+                logits = logits.masked_fill(~self.mask, float("-inf"))
             u = torch.rand_like(logits).clamp_(1e-7, 1 - 1e-7)
             a = (logits - torch.log(-torch.log(u))).argmax(dim=1)  # Gumbel-max = a sample of Categorical(logits)
             act_buf[t, self.lo:self.hi].copy_(a)
@@ -83,6 +95,8 @@ class Part:
 
     def env_part(self, t):
         self.env.step(None, auto_reset=True, fetch=False)  # one launch; reward / done / obs are rewritten in place
+        if MASK:
+            self.env.action_mask(fetch=False)  # one launch: the mask of the next pending service, in place
         rew_buf[t, self.lo:self.hi].copy_(self.rew)
 
     def rollout(self):
@@ -134,6 +148,8 @@ def timed(fn, n=5):
 
 def update():
     logits = net(obs_buf.view(T * B, -1))
+    if MASK:  # (a large negative instead of -inf keeps 0 * log 0 out of the entropy)
+        logits = logits.masked_fill(~mask_buf.view(T * B, -1), -1e9)
     logp_all = torch.log_softmax(logits, dim=1)
     logp = logp_all.gather(1, act_buf.view(-1, 1)).view(T, B)
     entropy = -(logp_all.exp() * logp_all).sum(dim=1).mean()

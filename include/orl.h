@@ -263,6 +263,9 @@ int orl_host_free(void* p);
 #define ORL_BUF_OBS 4      /* f64   [n_envs][obs_dim] (DeepRMSA) */
 #define ORL_BUF_TERM_OBS 5 /* f64   [n_envs][obs_dim]: observation before an auto reset */
 #define ORL_BUF_PATHS 6    /* int32 [n_envs]: path column of ORL_POLICY_PATH_FF */
+#define ORL_BUF_ACTION_MASK 7 /* u8 [n_envs][pitch]: the rows of the last orl_batch_action_mask, in that call's layout (pitch of
+                               * orl_batch_action_mask_shape); each layout has a buffer of its own, allocated by its first call, so a
+                               * pointer taken after a JOINT call keeps showing JOINT rows; n_elements = 0 before any call */
 int orl_batch_device_buffer(orl_batch* b, int which, void** device_ptr, int64_t* n_elements);
 /* The HIP stream (hipStream_t) the batch queues its launches on.  An agent on the same GPU that queues ITS kernels on this
  * stream too (torch: `torch.cuda.ExternalStream(ptr)`) needs no synchronisation between its network and orl_batch_step: the
@@ -318,6 +321,26 @@ int orl_multi_n_shards(const orl_multi* m);
 orl_batch* orl_multi_shard(orl_multi* m, int shard, int64_t* first_env /*nullable*/, int64_t* n_envs /*nullable*/);
 int orl_multi_run(orl_multi* m, int policy_id, int64_t n_steps, orl_run_stats* stats);
 void orl_multi_destroy(orl_multi* m);
+
+/* Action masks of the pending service — what the next step() acts on, after any reset / step / policy_step / run / set_state,
+ * auto resets included — for every env, computed on the device next to the slot maps (sb3-contrib's MaskablePPO reads them
+ * through `action_masks()`; a torch agent fills the masked logits with -inf).  RMSA, DeepRMSA and RWA; RMCSA and
+ * QoSConstrainedRA return ORL_E_INVALID.  Per env a row of `dim` bytes, 0 or 1; the last column is the reject action and equals
+ * allow_rejection.  Layouts: */
+#define ORL_MASK_JOINT 0 /* RMSA / RWA: dim = k*S + 1, column i < dim-1 = action (i / S, i % S) (path, first slot / wavelength);
+                          * DeepRMSA: dim = k*j + 1, column i = action i.  1 iff stepping that action provisions the service:
+                          * rmsa_env.py:163-200 with is_path_free :623-636; deeprmsa_env.py:48-58 with get_available_blocks
+                          * rmsa_env.py:667-697; rwa_env.py:101-135.  A path index >= n_paths[src, dst] is 0 (IndexError there). */
+#define ORL_MASK_PATH 1  /* PathOnlyFirstFitAction (RMSA / RWA): dim = k + 1, column p = the wrapper's first fit finds a slot on
+                          * path p — RMSA searches range(0, S - n) (rmsa_env.py:848-871), RWA every wavelength (rwa_env.py:518-533). */
+/* Fallback: a row without a provisioning column gets, when allow_rejection == 0, every non-reject column set — every action of
+ * the space then has the same effect (rejection) and a masked categorical never meets a row of -inf only.
+ * orl_batch_action_mask_shape: *dim and the device pitch round_up(dim, 16) of ORL_BUF_ACTION_MASK's rows for `layout`.
+ * orl_batch_action_mask: one launch on the batch's stream into ORL_BUF_ACTION_MASK (no synchronisation, graph-capturable: the
+ * buffer is allocated by the first call, which should therefore come before a capture); with out != NULL ([n_envs][dim] bytes)
+ * the rows are then copied out densely and the call synchronises. */
+int orl_batch_action_mask_shape(const orl_batch* b, int layout, int32_t* dim, int32_t* pitch);
+int orl_batch_action_mask(orl_batch* b, int layout, uint8_t* out);
 
 /* Snapshot / restore of the complete simulation state of the batch (slot maps, pending releases, RNG, statistics,
  * counters).  The reference has no equivalent (no checkpointing); used for long PPO runs. */

@@ -358,6 +358,13 @@ static void launch_obs(orl_batch* b, int with_terminal) {
   ORL_DISPATCH_W(b, CALL)
 #undef CALL
 }
+static int launch_action_mask(orl_batch* b, int layout, unsigned char* out, int pitch) {
+  int r = 0;
+#define CALL(WW) r = orl_launch::action_mask<WW>(b, layout, out, pitch)
+  ORL_DISPATCH_W(b, CALL)
+#undef CALL
+  return r;
+}
 static void launch_persist(orl_batch* b, const DevParams& VP, hipStream_t st, int pol, int target, int* wg_step, unsigned int* unfinished,
                            unsigned int* clear_next, int finish) {
 #define CALL(WW) orl_launch::persist<WW>(b, VP, st, pol, target, wg_step, unfinished, clear_next, finish)
@@ -1097,6 +1104,14 @@ extern "C" int orl_host_free(void* p) try {
 }
 ORL_ABI_CATCH_INT
 
+// action masks (orl_mask.h): row length of `layout` for this batch's family, 0 = not supported
+static int mask_dim(const DevParams& P, int layout) {
+  if (P.env_type != ENV_RMSA && P.env_type != ENV_DEEPRMSA && P.env_type != ENV_RWA) return 0;
+  if (layout == ORL_MASK_JOINT) return P.K * (P.env_type == ENV_DEEPRMSA ? P.J : P.S) + 1;
+  if (layout == ORL_MASK_PATH && P.env_type != ENV_DEEPRMSA) return P.K + 1;
+  return 0;
+}
+
 extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_ptr, int64_t* n_elements) try {
   if (!b || !device_ptr || !n_elements) return fail(ORL_E_INVALID, "null argument");
   const int64_t B = b->P.B;
@@ -1108,6 +1123,11 @@ extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_pt
     case ORL_BUF_OBS: *device_ptr = b->P.obs; *n_elements = B * b->P.obs_dim; break;
     case ORL_BUF_TERM_OBS: *device_ptr = b->P.term_obs; *n_elements = B * b->P.obs_dim; break;
     case ORL_BUF_PATHS: *device_ptr = b->P.path_col; *n_elements = B; break;
+    case ORL_BUF_ACTION_MASK:
+      if (b->mask_last < 0) { *device_ptr = nullptr; *n_elements = 0; break; }
+      *device_ptr = b->mask_buf[b->mask_last];
+      *n_elements = B * ((mask_dim(b->P, b->mask_last) + 15) / 16 * 16);
+      break;
     default: return fail(ORL_E_INVALID, "unknown buffer %d", which);
   }
   return ORL_OK;
@@ -1139,6 +1159,48 @@ extern "C" int orl_batch_get_obs_f32(orl_batch* b, float* obs_out) try {
   HIPCHK(hipMemcpyAsync(obs_out, b->obs_f32, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
   HIPCHK(hipGetLastError());
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+static int mask_check(const orl_batch* b, int layout) {
+  const int t = b->P.env_type;
+  if (t == ENV_RMCSA || t == ENV_QOS)
+    return fail(ORL_E_INVALID, "action masks are not available for %s (RMSA, DeepRMSA and RWA only)", t == ENV_RMCSA ? "RMCSA" : "QoSConstrainedRA");
+  if (layout != ORL_MASK_JOINT && layout != ORL_MASK_PATH) return fail(ORL_E_INVALID, "unknown action-mask layout %d", layout);
+  if (!mask_dim(b->P, layout)) return fail(ORL_E_INVALID, "DeepRMSA has no path-only action space: use ORL_MASK_JOINT");
+  if (t == ENV_DEEPRMSA && b->P.J > 64) return fail(ORL_E_INVALID, "action masks support j <= 64 blocks per path (j = %d)", b->P.J);
+  return ORL_OK;
+}
+
+extern "C" int orl_batch_action_mask_shape(const orl_batch* b, int layout, int32_t* dim, int32_t* pitch) try {
+  if (!b || !dim || !pitch) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = mask_check(b, layout)) return rc;
+  *dim = mask_dim(b->P, layout);
+  *pitch = (*dim + 15) / 16 * 16;
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+extern "C" int orl_batch_action_mask(orl_batch* b, int layout, uint8_t* out) try {
+  if (!b) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = mask_check(b, layout)) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  const int dim = mask_dim(b->P, layout), pitch = (dim + 15) / 16 * 16;
+  const i64 B = b->P.B;
+  unsigned char*& buf = b->mask_buf[layout];  // one buffer per layout: a device view of one layout's rows never sees the other's
+  if (!buf) {
+    HIPCHK(hipMalloc((void**)&buf, (size_t)(B * (int64_t)pitch)));
+    b->allocs.push_back(buf);
+  }
+  if (launch_action_mask(b, layout, buf, pitch))
+    return fail(ORL_E_INVALID, "action masks of k = %d paths x %d columns exceed the kernel's LDS budget", b->P.K, dim - 1);
+  HIPCHK(hipGetLastError());
+  b->mask_last = layout;
+  if (out) {
+    HIPCHK(hipMemcpy2DAsync(out, (size_t)dim, buf, (size_t)pitch, (size_t)dim, (size_t)B, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+  }
   return ORL_OK;
 }
 ORL_ABI_CATCH_INT

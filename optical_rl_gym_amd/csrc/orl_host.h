@@ -84,6 +84,9 @@ struct orl_batch {
   int* ep_buf = nullptr;           // episode log buffer (orl_batch_episode_log): [B][ep_alloc] ints, armed with stride P.ep_cap <= ep_alloc
   int ep_alloc = 0;
   double* ep_rew_buf = nullptr;    // QoSConstrainedRA: the float64 reward sums beside it, same shape
+  unsigned char* mask_buf[2] = {nullptr, nullptr};  // action masks per layout (ORL_MASK_JOINT / _PATH): [B][pitch] bytes, allocated by
+                                                   // the first orl_batch_action_mask of that layout (a view of one stays that layout's)
+  int mask_last = -1;              // layout of the last launch: what ORL_BUF_ACTION_MASK hands out (-1: none yet)
 };
 
 #define ORL_TK(B_, NAME)                                                                 \
@@ -103,6 +106,7 @@ template <int W> void reset(orl_batch* b, int full, const unsigned char* dmask);
 template <int W> void policy(orl_batch* b, int pol);                       // stand-alone slot scan -> P.actions
 template <int W> void step64(orl_batch* b, int auto_reset, int want_info, int fused_policy);  // one wavefront per env
 template <int W> void obs(orl_batch* b, int with_terminal);                // DeepRMSA observation
+template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, int pitch);  // k_action_mask -> out [B][pitch]
 // k_persist over the env range of view VP up to step `target` of this run, then k_rel_tail, on stream st
 template <int W> void persist(orl_batch* b, const orl::DevParams& VP, hipStream_t st, int pol, int target, int* wg_step, unsigned int* unfinished,
                               unsigned int* clear_next, int finish);  // finish: this launch ends the run (DevParams::persist_finish)

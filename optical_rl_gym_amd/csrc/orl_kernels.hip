@@ -9,6 +9,7 @@
 //   k_rel_tail  two-kernel test form: the rare envs whose releases of a step did not fit the item form release them in place
 //               (k_persist does that itself at the start of the owning wavefront's next launch)
 //   k_obs8/k_obs DeepRMSA observation of the pending service
+//   k_action_mask action masks of the pending service (orl_mask.h)                      8 lanes per env, lane = path
 // Launchers (orl_launch::*<W>) are explicitly instantiated at the end; orl_api.hip dispatches on the batch's W.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -2080,6 +2081,10 @@ __global__ void __launch_bounds__(256) k_obs8(DevParams P, int with_terminal) {
   obs8_env<W>(P, P.bitmap + env * P.bm_words, P.scal + env * ORL_SCAL_WORDS, env, lane_id(), with_terminal && P.done[env]);
 }
 
+#ifndef ORL_SPEC_ONLY
+#include "orl_mask.h"  // k_action_mask: action masks of the pending service (RMSA, DeepRMSA, RWA)
+#endif
+
 // ---- QoSConstrainedRA for an agent in the loop: 8 lanes per env (round 5) --------------------------------------------------------
 // QoSConstrainedRA.step (qos_constrained_ra.py:100-157) with the layout of k_agent — 8 envs per wavefront, all state in global
 // memory — for batches of at least 20 480 envs (k_step, one wavefront per env, served every batch size until round 5; it stays for
@@ -2266,6 +2271,17 @@ template <int W> void obs(orl_batch* b, int with_terminal) {
     hipLaunchKernelGGL((k_obs<ENV_DEEPRMSA, W>), dim3((unsigned)VP.B), dim3(64), (size_t)VP.lds_bytes, b->stream, VP, with_terminal);
   }
   ORL_TK(b, "k_obs");
+}
+
+// k_action_mask (orl_mask.h) into `out` ([B][pitch] bytes on the device); -1 when the LDS rows of 32 envs exceed 48 KiB
+template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, int pitch) {
+  const DevParams& VP = b->P;
+  const size_t lds = (size_t)ORL_MASK_ENVS_PER_BLOCK * mask_env_words(layout, VP.env_type, W, VP.K) * sizeof(u32);
+  if (lds > 48 * 1024) return -1;
+  const unsigned grid = (unsigned)((VP.B + ORL_MASK_ENVS_PER_BLOCK - 1) / ORL_MASK_ENVS_PER_BLOCK);
+  hipLaunchKernelGGL((k_action_mask<W>), dim3(grid), dim3(256), lds, b->stream, VP, out, layout, pitch);
+  ORL_TK(b, "k_action_mask");
+  return 0;
 }
 
 // Forms of the persistent kernel: (what lives in LDS, waves per SIMD the registers are budgeted for).  The LDS window decides
@@ -2616,6 +2632,7 @@ template int prof_read<ORL_W>(unsigned long long*, int);
 template void policy<ORL_W>(orl_batch*, int);
 template void step64<ORL_W>(orl_batch*, int, int, int);
 template void obs<ORL_W>(orl_batch*, int);
+template int action_mask<ORL_W>(orl_batch*, int, unsigned char*, int);
 template void persist<ORL_W>(orl_batch*, const DevParams&, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);
 template int persist_resident<ORL_W>(orl_batch*, int);
 template int persist_uses_lds<ORL_W>(orl_batch*);

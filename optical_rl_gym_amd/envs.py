@@ -523,9 +523,35 @@ class BatchedOpticalEnv:
             if m is None or m[i]:
                 self.seeds[i] = int(sd[i])
 
+    # ---- action masks (include/orl.h, orl_batch_action_mask) -------------------------------------------
+    MASK_LAYOUTS = {"joint": 0, "path": 1}
+
+    def action_mask_shape(self, layout="joint"):
+        """(dim, pitch) of the rows of `layout`: dim columns per env, rows pitch bytes apart in the device buffer."""
+        d, p = C.c_int32(), C.c_int32()
+        self._ck(self.lib.orl_batch_action_mask_shape(self._h, self.MASK_LAYOUTS[layout], C.byref(d), C.byref(p)))
+        return d.value, p.value
+
+    def action_mask(self, layout="joint", fetch=True):
+        """Action mask of the pending service of every env, computed on the device: bool [num_envs, dim].  "joint": RMSA / RWA
+        column p * S + s = action (p, s), DeepRMSA column i = action i; "path": PathOnlyFirstFitAction's Discrete(k + 1).  The
+        last column is the reject action (= allow_rejection); a row without a provisioning action and allow_rejection=False is
+        all ones but for it (every action rejects then).  fetch=False only queues the launch on the batch's stream — read the
+        rows in place with device_array("action_mask") / device_tensor("action_mask")."""
+        lay = self.MASK_LAYOUTS[layout]
+        if not fetch:
+            self._ck(self.lib.orl_batch_action_mask(self._h, lay, None))
+            self._mask_layout = layout
+            return None
+        dim, _pitch = self.action_mask_shape(layout)
+        out = np.empty((self.num_envs, dim), np.uint8)
+        self._ck(self.lib.orl_batch_action_mask(self._h, lay, out.ctypes.data))
+        self._mask_layout = layout
+        return out.view(np.bool_)
+
     # ---- zero-copy device views (an agent on the same GPU: no PCIe in the loop) -------------------------
     _BUFFERS = {"actions": (0, "<i4", 4), "reward": (1, "<f8", 0), "done": (2, "|u1", 0), "info": (3, "<f8", -1),
-                "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0)}
+                "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0), "action_mask": (7, "|b1", -3)}
 
     def device_array(self, name):
         """The batch's device-resident I/O array `name` as an object with `__cuda_array_interface__` (what
@@ -534,12 +560,20 @@ class BatchedOpticalEnv:
         which, typestr, cols = self._BUFFERS[name]
         ptr, n = C.c_void_p(), C.c_int64()
         self._ck(self.lib.orl_batch_device_buffer(self._h, which, C.byref(ptr), C.byref(n)))
+        strides = None
+        if cols == -3:
+            # the rows of the last action_mask(), [num_envs, dim] at the device pitch.  Each layout has a buffer of its own: a view
+            # taken after a "joint" call keeps showing the joint rows (as the last "joint" call left them) after "path" calls
+            if n.value == 0 or not ptr.value:
+                raise _lib.OrlError("no action mask yet: call action_mask() (fetch=False only queues it) first")
+            cols, pitch = self.action_mask_shape(getattr(self, "_mask_layout", "joint"))
+            strides = (pitch, 1)
         cols = {-1: self.n_info, -2: self.obs_dim}.get(cols, cols)
         if n.value == 0 or not ptr.value:
             raise _lib.OrlError("this env family has no '%s' array" % name)
         shape = (self.num_envs, cols) if cols else (self.num_envs,)
 
-        cai = {"shape": shape, "typestr": typestr, "data": (int(ptr.value), False), "version": 2, "strides": None}
+        cai = {"shape": shape, "typestr": typestr, "data": (int(ptr.value), False), "version": 2, "strides": strides}
         device_id, owner = self.device_id, self
 
         class _Raw:  # what torch.as_tensor consumes

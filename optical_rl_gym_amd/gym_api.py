@@ -304,6 +304,13 @@ class _SingleEnv:
         ok = np.flatnonzero((values == 1) & (lengths >= slots))[: self.j]
         return starts[ok], lengths[ok]
 
+    def action_masks(self):
+        """Mask of the pending service over `action_space` in sb3-contrib's form (vec_env.sb3_action_masks), computed on the
+        device: bool [n] for Discrete, the per-dimension concatenation for MultiDiscrete."""
+        from .vec_env import sb3_action_masks
+
+        return sb3_action_masks(self.batch, self.batch.action_mask("joint"), self.action_space)[0]
+
     def policy_action(self, policy):
         """Action of the on-device heuristic `policy` for the pending service, in the reference's tuple form."""
         a = self.batch.policy(policy)[0]
@@ -575,6 +582,11 @@ class PathOnlyFirstFitAction(_Wrapper):
         u = env.unwrapped
         self.action_space = spaces.Discrete(u.k_paths + u.reject_action)
         self.observation_space = env.observation_space
+
+    def action_masks(self):
+        """bool [k + reject]: path p valid iff the first fit finds a slot on it (the "path" layout of action_mask)."""
+        u = self.env.unwrapped
+        return u.batch.action_mask("path")[0][: self.action_space.n]
 
     def action(self, action):
         u = self.env.unwrapped

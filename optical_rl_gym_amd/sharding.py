@@ -236,6 +236,10 @@ class MultiDeviceBatch:
     def matrix_observation(self):
         return self._cat(self._map(lambda r: self.shards[r].matrix_observation()))
 
+    def action_mask(self, layout="joint", fetch=True):
+        out = self._map(lambda r: self.shards[r].action_mask(layout, fetch=fetch))
+        return self._cat(out) if fetch else None
+
     def sync(self):
         self._map(lambda r: self.shards[r].sync())
 

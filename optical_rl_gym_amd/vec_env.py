@@ -15,6 +15,7 @@ stable-baselines3 itself is not a dependency: if it is importable the class regi
 For an agent on the same GPU, `device_obs()` / `device_tensors()` hand out zero-copy views (DLPack) of the batch's
 device-resident arrays; `obs_dtype=np.float32` casts observations for float32 policies.
 """
+import functools
 import os
 import time
 
@@ -53,6 +54,26 @@ def make_spaces(batch, obs_dtype=np.float64, mod=None):
         else:
             act = sp.MultiDiscrete((k + rej, S + rej))
     return obs, act
+
+
+def sb3_action_masks(batch, joint, action_space):
+    """The joint-layout rows of `batch.action_mask()` (bool [n, dim]) in the form sb3-contrib's MaskablePPO takes for
+    `action_space`: Discrete (DeepRMSA) — the row's first `n` columns; MultiDiscrete (RMSA, RWA: (k + rej, S + rej)) — the
+    per-dimension concatenation, path p valid iff some slot fits on it, slot s valid iff it fits on some path, the reject
+    entries equal allow_rejection.  A fallback row (no provisioning action, allow_rejection=False) is all ones."""
+    joint = np.asarray(joint, np.bool_)
+    if hasattr(action_space, "n") and not hasattr(action_space, "nvec"):
+        return joint[:, : int(action_space.n)]
+    k, S = batch.k_paths, batch.num_spectrum_resources
+    body = joint[:, : k * S].reshape(len(joint), k, S)
+    parts = [body.any(axis=2)]
+    rej = joint[:, k * S:k * S + 1]
+    if batch.allow_rejection:
+        parts.append(rej)
+    parts.append(body.any(axis=1))
+    if batch.allow_rejection:
+        parts.append(rej)
+    return np.concatenate(parts, axis=1)
 
 
 # Shared by every env without episode information in a step: an empty dict that REFUSES writes (a wrapper or callback that tries
@@ -444,6 +465,10 @@ class OpticalVecEnv:
             return [dict(zip(keys, svc[i])) for i in idx]
         if attr_name in ("render_mode",):
             return [None for _ in idx]
+        if attr_name == "action_masks":
+            # (sb3-contrib only probes for the method with get_attr; each of these computes and fetches the whole batch's masks —
+            # call action_masks() or env_method("action_masks") once for all envs instead)
+            return [functools.partial(self._env_action_masks, i) for i in idx]
         if hasattr(self, "_extra_attrs") and attr_name in self._extra_attrs:
             return [self._extra_attrs[attr_name][i] for i in idx]
         return [getattr(self.batch, attr_name) for _ in idx]
@@ -475,8 +500,19 @@ class OpticalVecEnv:
             return [None if obs is None else np.array(obs[i]) for i in idx]
         if method_name == "render":
             return [None for _ in idx]
+        if method_name == "action_masks":  # one row per env (np.stack of the list is MaskablePPO's mask array)
+            m = self.action_masks()
+            return [m[i] for i in idx]
         out = getattr(self.batch, method_name)(*method_args, **method_kwargs)
         return [out for _ in idx]
+
+    def action_masks(self):
+        """Action masks of every env's pending service in the form of `action_space` (sb3_action_masks), bool [num_envs, n]:
+        what sb3-contrib's MaskablePPO reads (`np.stack(venv.env_method("action_masks"))`).  Computed on the device."""
+        return sb3_action_masks(self.batch, self.batch.action_mask("joint"), self.action_space)
+
+    def _env_action_masks(self, i):
+        return self.action_masks()[i]
 
     def env_is_wrapped(self, wrapper_class, indices=None):
         return [False] * len(self._indices(indices))

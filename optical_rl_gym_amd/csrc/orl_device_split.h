@@ -3,7 +3,7 @@
 // Persistent kernel k_persist (orl_kernels.hip; the device-resident loop): one wavefront owns 8 envs for a whole launch and
 // alternates the two phases below; k_agent runs them once, for an agent-driven step, and adds validation, info and the
 // observation; the two-kernel test form (-DORL_ALT_IMPLS) runs them as separate launches:
-//   control     8 lanes per env (ctrl_a): the slot scan (policy) or the agent's action, decode + validate, counters, reward,
+//   control     8 lanes per env (ctrl_phase): the slot scan (policy) or the agent's action, decode + validate, counters, reward,
 //               the release push, network throughput, the next service (RNG, node pair, bit rate), done / auto reset, and
 //               the due releases of the step through the env's soon list (release_soon).  Output: work items in an LDS
 //               sink, one per touched link — the provision's mask first, then the release masks (single-core families: one
@@ -304,6 +304,17 @@ struct SvcBuf {
   int cnt;       // group-uniform: services in the batch << 8 | next one to take
 };
 __device__ __forceinline__ bool svc_empty(const SvcBuf& b) { return (b.cnt & 0xff) >= (b.cnt >> 8); }
+// the next service of the batch, from the lane of the group that holds it: inter-arrival time, holding time, packed descriptor
+struct SvcNext { double q, ht; u32 pk; };
+__device__ __forceinline__ SvcNext svc_take(SvcBuf& b, int lane) {
+  const int k = b.cnt & 0xff;
+  SvcNext s;
+  s.q = gget(b.q, k, lane);
+  s.ht = gget(b.ht, k, lane);
+  s.pk = gget(b.pk, k, lane);
+  b.cnt += 1;
+  return s;
+}
 // i mod 624 for 0 <= i < 1248 (a subtraction and an unsigned minimum: below 624 the difference wraps to a huge value)
 __device__ __forceinline__ int svc_wrap(int i) { const u32 u = (u32)i, d = u - 624u; return (int)(d < u ? d : u); }
 // bisect(cum_weights, x, 0, n - 1) of random.choices: the number of entries cum[0 .. n-2] that are <= x (cum is non-decreasing).
@@ -484,11 +495,9 @@ __device__ __forceinline__ void sink_compact(const SinkEntryC* tab, int E, int l
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// control kernel A: everything of step() up to (and excluding) the effects of the provision on the link rows
+// the control phase (ctrl_phase): everything of step() up to (and excluding) the effects of the provision and the releases on
+// the link rows
 // ---------------------------------------------------------------------------------------------------------------
-template <int ENV, int W>
-__device__ __forceinline__ bool service_part(const DevParams& P, EnvG& e, i64 env, int lane, int auto_reset, bool accepted, int core,
-                                             bool write_io, g8::RngG& rng, Prof& prof, SvcBuf* svc);
 #ifndef ORL_SCAN_BATCH
 #define ORL_SCAN_BATCH 8  // release times a lane requests per round of the rebuild scan
 #endif
@@ -518,7 +527,7 @@ struct Wmem {
   u32* ocg;      // GLOBAL [8][E]: the same words as oc0 where they do not fit the LDS window (the wavefront's level-2 area of
                  // DevParams::row_cache, live during the launch), or nullptr; indexed with cenv0
   double* evl0;  // LDS [8][ev_cap]: the pending release times of the wavefront's envs (small batches, two-wavefront form), or nullptr
-  u64* mini;     // LDS [8][ORL_MINI_STRIDE]: the record words ctrl_d works on (deferred statistics, records in global memory), or nullptr
+  u64* mini;     // LDS [8][ORL_MINI_STRIDE]: the record words the DS control phase works on (records in global memory), or nullptr
   i64 mini_env0; // index base of mini
 };
 __device__ __forceinline__ Wmem wmem_global(const DevParams& P) {
@@ -539,351 +548,54 @@ struct CtrlOpts {
   bool prefetch;    // request the Mersenne-Twister window at the start of the phase (costs registers: 3-wave forms only)
   bool auto_reset;  // an env that reports done is soft-reset right away (the device-resident loop, SB3's VecEnv); k_agent: the caller's choice
   bool rank_pairs;  // (soon list in registers) rank the due releases all-pairs over DPP: needs the 168-VGPR budget
+  int parity;       // two-kernel form: which of the two deferral lists this step appends to (P.q_def)
+};
+// The wavefront's LDS tables of the control phase, laid out once per wavefront (each pointer the workgroup's base: the phase
+// finds its wavefront's and env's part)
+template <bool CP> struct CtrlLds {
+  typename SinkEntryOf<CP>::type* tab;  // sink tables, E entries per env
+  u32* tally;                           // !CP: per-link touch counters, `tw` words per env
+  int tw;
+  unsigned short* mtab;                 // CP: mask tables, ORL_MTAB entries per env
+  unsigned short* list;                 // the wavefront's item list (persistent forms, else nullptr) ...
+  u32* list_n;                          // ... and its length
+  int* deferred;                        // set when an env's releases do not fit the item form (persistent forms, else nullptr)
+  const u32* rw_sync;                   // RW: the pair's counters — [1] steps whose items the row wavefront has read (sink table,
+                                        // mask table, clocks and rows: they may be overwritten), [2] steps whose statistics are
+                                        // complete (the sums)
+};
+// What the persistent loop carries from step to step (k_persist; k_agent: the soon list at most).  A null pointer: not carried —
+// the soon list stays in memory, the step draws its own service.
+struct StepCarry {
+  SoonRegs* soon = nullptr;  // this lane's entries of the env's soon list, in registers
+  SvcBuf* svc = nullptr;     // the group's batch of services drawn ahead (svc_generate; DS: always)
+  u64 desc = 0ull;           // the pending service's descriptor (read by DS); the new one when the phase returns
+  int esp = 0;               // DS: the env's episode step counter (done / observation need it)
+  int prev_core = 0;         // DS, RMCSA: the core of the env's last accepted provision — the sums logged are that core's
+  int ecur = 0;              // RD: the env's events logged so far in this launch
+  int t = 0;                 // DS: the step's number within the launch (its row of the log; RD: its events' stamp)
+  u32 rw_k = 0u;             // RW: steps handed over to the row wavefront so far
 };
 template <int ENV, int W, bool CP, bool RD = false>
 __device__ __forceinline__ void release_soon(const DevParams& P, EnvG& e, int lane, SinkT<CP, RD>& sink, SoonRegs& out, Prof& prof,
                                              int extra = 0, int pushed_idx = -1, u64 pushed_info = 0ull, int pre_idx = -1,
                                              u64 pre_info = 0ull);
 
-// The provision and the releases of the step go into ONE queue as mixed items (per link: the provision mask first, then the
-// release masks) and one row phase applies them.  The network-compactness average, which needs the sums between the
-// provision and the releases, is finished by the NEXT step from totals - (what the releases added): the row phase keeps
-// the latter in rel_sums.
-// Returns the service descriptor of the NEW pending service (what the next slot scan needs: pair base, bit-rate index,
-// number of paths), and through *n_items_out the number of items this env's step left in its sink table.
-// CP: compact sink entries (SinkEntryC); tw: tally words per env (>= ceil(E / 4))
 // Host- or agent-driven single steps through these phases (k_agent): what info of step() needs beyond the device-resident
 // loop's state (rmsa_env.py:228-264) — the network compactness before the provision, the occupied-slot sum right after it —
 // carried from the control phase to the end of the step; the four blocking rates are stored by the control phase itself.
 struct InfoCarry { double prev_comp; i64 s_nh_prov; };
 
-template <int ENV, int W, bool CP = false>
-__device__ __forceinline__ u64 ctrl_a(const DevParams& P, const Wmem& M, const CtrlOpts& O, i64 env, bool valid, int lane, Prof& prof,
-                                      const int4* given, u32* s_tally, typename SinkEntryOf<CP>::type* s_tab, int parity,
-                                      int* s_deferred, int* done_out, unsigned short* s_list = nullptr, u32* s_list_n = nullptr,
-                                      int tw = 32, SoonRegs* carried = nullptr, unsigned short* s_mtab = nullptr,
-                                      InfoCarry* ic = nullptr, SvcBuf* svc = nullptr) {
-  // `svc` (persistent kernel): the group's batch of services drawn ahead (svc_generate); else the step draws its own
-  const int K = P.K, S = P.S, rej = P.allow_rejection ? 1 : 0, gl = lane & 7;
-  if (!O.persistent && blockIdx.x == 0 && threadIdx.x == 0) P.q_def[(size_t)(parity ^ 1) * P.q_def_stride] = 0u;  // the buffer the next step appends to
-  u64 desc_out = 0ull;
-  int cnt = 0, core = 0, slot = 0, n = 1;
-  PathRec rec;
-  rec.q[0] = rec.q[1] = rec.q[2] = rec.q[3] = 0;
-  SinkT<CP> sink;
-  sink.tab = nullptr; sink.tally = nullptr; sink.tw = tw; sink.active = false; sink.deferred = false; sink.cnt = 0;
-  sink.list = s_list; sink.list_n = s_list_n; sink.mtab = nullptr; sink.nrel = 0; sink.rows = nullptr; sink.roww = 0;
-  if (s_list_n && lane == 0) *s_list_n = 0u;
-  {  // every wavefront clears the tables of its own 8 envs: no workgroup barrier
-    typename SinkEntryOf<CP>::type* tb = s_tab + P.E * 8 * (int)(threadIdx.x >> 6);
-    if constexpr (!CP) {
-      u32* ty = s_tally + tw * 8 * (int)(threadIdx.x >> 6);
-      for (int i = lane; i < 8 * tw; i += 64) ty[i] = 0u;
-      sink.tally = s_tally + tw * (int)(threadIdx.x >> 3);
-    } else {
-      sink.mtab = s_mtab + ORL_MTAB * (int)(threadIdx.x >> 3);  // (entries are written before they are read: nothing to clear)
-    }
-    for (int i = lane; i < 8 * P.E; i += 64) sink_entry_clear(tb[i]);
-    wave_fence();
-    sink.tab = s_tab + P.E * (int)(threadIdx.x >> 3);
-  }
-  if (valid) {
-    EnvG e;
-    g8::env_load(P, e, env, wm_scal(P, M, env));
-    // the Mersenne-Twister window the next service draws from: requested now, used after the provision
-    if (carried) {  // persistent kernel: the soon list stays in registers from step to step
-      e.sr_on = true;
-      e.rank_pairs = O.rank_pairs;
-#pragma unroll
-      for (int k = 0; k < ORL_SOON_PER_LANE; k++) { e.sr_t[k] = carried->t[k]; e.sr_i[k] = carried->i[k]; }
-    }
-    // the info word of this lane's earliest list entry, if it may come due in this step: requested now, the release
-    // detection at the end of the phase finds it in a register
-    int pre_idx = -1;
-    u64 pre_info = 0ull;
-    if (carried && O.prefetch) {
-      double pt = e.sr_t[0];
-      int pi = e.sr_i[0];
-#pragma unroll
-      for (int k = 1; k < ORL_SOON_PER_LANE; k++)
-        if (e.sr_t[k] < pt || (e.sr_t[k] == pt && e.sr_i[k] < pi)) { pt = e.sr_t[k]; pi = e.sr_i[k]; }
-      // (t_soon == -inf: the list is stale — after a reset or the serial tail — and its entries mean nothing)
-      if (pt <= e.now + P.pf_window && e.t_soon > -__builtin_inf() && (u32)pi < (u32)P.ev_cap) { pre_idx = pi; pre_info = e.ev_info[pi]; }
-    }
-    g8::RngG rng;
-    rng.used = 0; rng.pend_used = 0;
-    if (O.prefetch && !svc) g8::rng_fill(e, rng, gl);
-    e.bm = wm_bm(P, M, env);
-    e.ls = wm_ls(P, M, env);
-    e.cs = wm_cs(P, M, env);
-    int* rs = e.cs + 2 * P.C;
-    {
-      const u64 acc0 = e.scal[SC_ACC];
-      if ((u32)acc0 & 2u) {
-        // network compactness update the previous step left pending: the sums right after ITS provision are the totals
-        // minus what its releases added (rmsa_env.py:439-462 with _get_network_compactness at provision time)
-        const int c0 = (int)((acc0 >> 32) & 31);
-        const i64 s_nh_prov = (i64)(acc0 >> 37);
-        // (the sums are updated by L2 atomics: in the persistent kernel, where no kernel boundary invalidates the L1 in
-        // between, they are read through L2 as well)
-        int occ, fb;
-        if (O.persistent && !M.cs_lds) {
-          occ = atomicAdd(e.cs + 2 * c0, 0) - atomicAdd(rs + 2 * c0, 0);
-          fb = atomicAdd(e.cs + 2 * c0 + 1, 0) - atomicAdd(rs + 2 * c0 + 1, 0);
-        } else {
-          occ = e.cs[2 * c0] - rs[2 * c0];
-          fb = e.cs[2 * c0 + 1] - rs[2 * c0 + 1];
-        }
-        const double a0 = __longlong_as_double((i64)e.scal[SC_GC_A]), td = __longlong_as_double((i64)e.scal[SC_GC_TD]);
-        const double now_a = __longlong_as_double((i64)e.scal[SC_NOWA]);
-        const double cmp = (fb > 0) ? div_pos((double)occ, (double)s_nh_prov) * div_pos((double)P.E, (double)fb) : 1.0;
-        e.g_comp = div_pos(a0 + (cmp * td), now_a);
-      }
-      for (int i = gl; i < 2 * P.C; i += 8) {  // this step's releases start from zero
-        if (O.persistent && !M.cs_lds) atomicExch(rs + i, 0);
-        else rs[i] = 0;
-      }
-    }
-    if (ic && (ENV == ENV_RMSA || ENV == ENV_DEEPRMSA)) {  // _get_network_compactness before the provision (rmsa_env.py:189)
-      int occ, fb;
-      if (O.persistent && !M.cs_lds) { occ = atomicAdd(e.cs, 0); fb = atomicAdd(e.cs + 1, 0); }
-      else { occ = e.cs[0]; fb = e.cs[1]; }
-      ic->prev_comp = (fb > 0) ? ((double)occ / (double)e.s_nh) * ((double)P.E / (double)fb) : 1.0;
-    }
-    const int4 av = given ? *given : *(const int4*)(P.actions + env * 4);
-    int path, mod = 0;
-    bool bad = false;
-    if (ENV == ENV_DEEPRMSA) {  // deeprmsa_env.py:48-58
-      int aa = av.x;
-      path = K; slot = S;
-      if (O.trusted && given) {  // decoded by the in-kernel scan, on this slot map (policy_g)
-        path = av.y; slot = av.z;
-      } else if (aa >= 0 && aa < K * P.J) {
-        int route = aa / P.J, block = aa - route * P.J;
-        int start = 0;
-        int pidx = pair_base(P, e.src, e.dst) + route;
-        int nb = 0;
-        if (route < P.n_paths[e.src * P.N + e.dst]) {
-          Row<W> m = g8::path_and_global<W>(P, e, pidx);
-          nb = nth_block<W>(m, S, P.nslots_path[(size_t)pidx * P.n_br + e.br_idx], block + 1, start);
-        }
-        if (block < nb) { path = route; slot = start; }
-      }
-    } else if (ENV == ENV_RMCSA) {
-      path = av.x; mod = av.y; core = av.z; slot = av.w;
-      bad = path < 0 || path > K || mod < 0 || mod > P.M || core < 0 || core > P.C || slot < 0 || slot > S;
-    } else if (ENV == ENV_RWA) {
-      path = av.x; slot = av.y;
-      bad = path < 0 || path >= K + rej || slot < 0 || slot >= S + rej;
-    } else {
-      path = av.x; slot = av.y;
-      bad = path < 0 || path > K || slot < 0 || slot > S;
-    }
-    if (bad) {
-      e.flags |= ORL_FLAG_BAD_ACTION;
-      path = K; slot = S; mod = P.M; core = P.C;
-    }
-    const int path0 = path, slot0 = slot, mod0 = mod, core0 = core;
-    ORL_PROFA(2);
-    bool accepted = false;
-    int pushed_idx = -1;
-    u64 pushed_info = 0ull;
-    double pushed_t = 0.0;
-    bool in_range = (ENV == ENV_RMCSA) ? (path < K && mod < P.M && core < P.C && slot < S) : (path < K && slot < S);
-    if (in_range && path < P.n_paths[e.src * P.N + e.dst]) {
-      int pidx = pair_base(P, e.src, e.dst) + path;
-      if (ENV == ENV_RMCSA) n = P.nslots[e.br_idx * P.M + mod];
-      else if (ENV != ENV_RWA) n = P.nslots_path[(size_t)pidx * P.n_br + e.br_idx];
-      rec = path_rec_load(P, pidx);
-      bool ok = O.trusted && (ENV != ENV_DEEPRMSA || given != nullptr);
-      if (!ok && slot + n <= S) {  // is_path_free: lane w checks word w of every link row of the path
-        const int hops = path_rec_byte(rec, 0);
-        bool busy = false;
-        if (gl < W) {
-          const u64 m = word_range(slot - 64 * gl, slot + n - 64 * gl);
-          const u64* rowbase = e.bm + (size_t)core * P.E * W + gl;
-          u64 miss = 0;
-          for (int h = 0; h < hops; h += 4) {  // four independent row-word loads in flight
-            const u64 r0 = rowbase[path_rec_byte(rec, 2 + h) * W];
-            const u64 r1 = (h + 1 < hops) ? rowbase[path_rec_byte(rec, 3 + h) * W] : ~0ull;
-            const u64 r2 = (h + 2 < hops) ? rowbase[path_rec_byte(rec, 4 + h) * W] : ~0ull;
-            const u64 r3 = (h + 3 < hops) ? rowbase[path_rec_byte(rec, 5 + h) * W] : ~0ull;
-            miss |= m & ~(r0 & r1 & r2 & r3);
-          }
-          busy = miss != 0ull;
-        }
-        ok = gballot(busy, lane) == 0u;
-      }
-      if (ok && ENV == ENV_RMCSA) {
-        double len = P.path_length[pidx];
-        ok = (len < P.lmax_xt[mod]) && (len < P.lmax_snr[mod * P.n_br + e.br_idx]);
-      }
-      ORL_PROFA(3);
-      if (ok) {
-        const int hops = path_rec_byte(rec, 0);
-        cnt = hops;
-        e.s_br += e.bit_rate;
-        e.s_nh += (i64)n * hops;
-        if (ENV != ENV_RWA) {
-          e.brp += e.bit_rate;
-          e.ebrp += e.bit_rate;
-          if (P.bit_rate_mode == 1 && gl == 0) P.br_hist[env * 2 * P.n_br + P.n_br + e.br_idx] += 1;
-        }
-        e.sa += 1;
-        e.esa += 1;
-        accepted = true;
-        pushed_info = ev_pack(pidx, slot, n, core, e.bit_rate);
-        pushed_t = e.at + e.ht;
-        pushed_idx = g8::ev_push(P, e, lane, pushed_t, pushed_info, false);  // (its two stores: after the next service's loads)
-        {  // the provision's rows: first mask of their items; they also count towards the per-link limit
-          sink_add(sink, rec, core, slot, n, lane, true);
-          if constexpr (!CP)
-            for (int h = gl; h < hops; h += 8) {
-              const int link = path_rec_byte(rec, 2 + h);
-              atomicAdd(sink.tally + (link >> 2), 1u << (8 * (link & 3)));
-            }
-        }
-        ORL_PROFA(4);
-      }
-    }
-    if (ENV == ENV_RWA) { e.sp += 1; e.esp += 1; }
-    if (ENV == ENV_RMCSA) { e.sp += 1; e.esp += 1; e.brq += e.bit_rate; e.ebrq += e.bit_rate; }
-    if (ENV != ENV_RMCSA && P.act2d && !bad && gl == 0) act2d_count(P, env, path0, slot0, accepted);
-    if (ENV == ENV_RMCSA && P.act2d && !bad && gl == 0) act4d_count(P, env, path0, mod0, core0, slot0, accepted);
-    if (ENV == ENV_RWA) {  // actions_output marginals (rwa_env.py:103, 148-151)
-      i64* h = P.act_hist + env * ((K + 1) + (S + 1));
-      const int npa = K + rej, nsa = S + rej;
-      for (int i = gl; i < npa + nsa; i += 8) {
-        int hi = (i < npa) ? i : (K + 1) + (i - npa);
-        bool hit = !bad && ((i < npa) ? (i == path0) : (i - npa == slot0));
-        if (ic) {  // k_agent: path_action_probability / wavelength_action_probability of info (rwa_env.py:148-151): updated count / services_processed
-          const i64 v = h[hi] + (hit ? 1 : 0);
-          if (hit) h[hi] = v;
-          P.info[env * P.n_info + 2 + i] = (double)v / (double)e.sp;
-        } else if (hit) {
-          h[hi] += 1;
-        }
-      }
-    }
-    if (gl == 0) {
-      if (O.write_io) {
-        P.reward[env] = accepted ? 1.0 : (ENV == ENV_DEEPRMSA ? -1.0 : 0.0);
-        if (given) *(int4*)(P.actions + env * 4) = (ENV == ENV_DEEPRMSA) ? make_int4(av.x, 0, 0, 0) : av;
-      }
-      e.scal[SC_ACC] = pack2(accepted ? 1 : 0, core);
-      e.scal[SC_NOWA] = (u64)__double_as_longlong(e.now);
-      if (M.clk) M.clk[2 * (env - M.clk_env0)] = e.now;
-    }
-    ORL_PROFA(5);
-    // the word service_part leaves in SC_ACC (recomputed here so that the deferral below need not read it back)
-    const u64 acc_after = (accepted && ENV != ENV_RWA && e.now > 0)
-                              ? (3ull | ((u64)(u32)core << 32) | ((u64)e.s_nh << 37))
-                              : pack2(accepted ? 1 : 0, core);
-    if (ic) {  // the counters as info sees them: after this step's decision, before the next service is counted (rmsa_env.py:234-249)
-      ic->s_nh_prov = e.s_nh;
-      if (gl == 0) {
-        double* io = P.info + env * P.n_info;
-        io[0] = (double)(e.sp - e.sa) / (double)e.sp;
-        io[1] = (double)(e.esp - e.esa) / (double)e.esp;
-        if (ENV != ENV_RWA) {  // (RWA: info goes on with the action probabilities, written beside the histogram update)
-          io[2] = (double)(e.brq - e.brp) / (double)e.brq;
-          io[3] = (double)(e.ebrq - e.ebrp) / (double)e.ebrq;
-        }
-        if ((ENV == ENV_RMSA || ENV == ENV_DEEPRMSA) && P.bit_rate_mode == 1) {  // discrete bit rates: blocking per rate + fairness (rmsa_env.py:217-227, 268-273)
-          const i64* rq = P.br_hist + env * 2 * P.n_br;
-          const i64* pv = rq + P.n_br;
-          double mxv = -__builtin_inf(), mnv = __builtin_inf();
-          for (int i = 0; i < P.n_br; i++) {
-            double bl = 0.0;
-            if (rq[i] > 0) bl = (double)(rq[i] - pv[i]) / (double)rq[i];
-            io[8 + i] = bl;
-            mxv = bl > mxv ? bl : mxv;
-            mnv = bl < mnv ? bl : mnv;
-          }
-          io[8 + P.n_br] = mxv - mnv;
-        }
-      }
-    }
-    if (!O.prefetch && !svc) g8::rng_fill(e, rng, gl);
-    const bool done = service_part<ENV, W>(P, e, env, lane, O.auto_reset ? 1 : 0, accepted, core, O.write_io, rng, prof, svc);
-    if (done_out) *done_out = done ? 1 : 0;
-    // the pending-release slot of this step's provision (the rebuild scan of the release detection must find it in memory)
-    if (pushed_idx >= 0 && gl == (pushed_idx & 7)) { e.ev_time[pushed_idx] = pushed_t; e.ev_info[pushed_idx] = pushed_info; }
-    desc_out = g8::env_store(P, e, gl, O.write_io);
-    if (M.clk && gl == 0) M.clk[2 * (env - M.clk_env0) + 1] = e.now;
-    ORL_PROFA(8);
-    {
-      // due releases of the step (rmsa_env.py:590-597) -> masks behind the provision's in the same table.  The env record
-      // has gone back already (so that only the handful of release-related fields stays in registers through the
-      // detection); those fields are written again below when the detection changed them.
-      SoonRegs soon;
-#ifdef ORL_DIAG_INSTEAD_OF_RELEASES
-      ORL_DIAG_INSTEAD_OF_RELEASES
-#else
-      release_soon<ENV, W, CP>(P, e, lane, sink, soon, prof, accepted ? 1 : 0, pushed_idx, pushed_info, pre_idx, pre_info);
-#endif
-      if (!svc) g8::rng_commit_stores(e, rng, gl);  // the Mersenne-Twister words of next_service: behind the detection's loads
-      ORL_PROFA(10);
-      if (sink.deferred) {
-        // more releases meet on one link than an item holds masks for: the release state stays as stored and the
-        // serial path (rel_serial: k_rel_tail, or the start of the persistent kernel's next launch) releases them in
-        // place after this step's items
-        if (gl == 0) {
-          if (!O.persistent) {  // two-kernel form: the list k_rel_tail works through
-            u32* dq = P.q_def + (size_t)parity * P.q_def_stride;
-            dq[16 + atomicAdd(dq, 1u)] = (u32)env;
-          }
-          if (s_deferred) *s_deferred = 1;  // persistent kernel: this workgroup stops after the row phase
-          e.scal[SC_ACC] = acc_after | (1ull << 16);
-          e.scal[SC_HINT] = pack2(e.nfree, 0);  // a rebuild may have rewritten the free-slot stack
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < ORL_SOON_PER_LANE; k++) {
-          if (e.sr_on) {
-            if (soon.dirty) { e.sr_t[k] = soon.t[k]; e.sr_i[k] = soon.i[k]; }  // (dirty == 0: returned untouched)
-          } else if ((soon.dirty >> k) & 1) {
-            e.soon_t[gl + 8 * k] = soon.t[k];
-            e.soon_i[gl + 8 * k] = (u32)soon.i[k];
-          }
-        }
-        if (gl == 0) {
-          e.scal[SC_NEXTREL] = (u64)__double_as_longlong(e.next_rel);
-          e.scal[SC_TSOON] = (u64)__double_as_longlong(e.t_soon);
-          e.scal[SC_SBR] = (u64)e.s_br;
-          e.scal[SC_SNH] = (u64)e.s_nh;
-          e.scal[SC_EV] = pack2(e.ev_hwm, e.ev_cnt);
-          e.scal[SC_HINT] = pack2(e.nfree, 0);
-        }
-      }
-    }
-    if (carried) {
-#pragma unroll
-      for (int k = 0; k < ORL_SOON_PER_LANE; k++) { carried->t[k] = e.sr_t[k]; carried->i[k] = e.sr_i[k]; }
-    }
-  }
-  ORL_PROFA(11);
-  if constexpr (!CP) { if (O.emit_queue) emit_items(P, env, sink, true, lane, P.q_a, P.q_cnt_a); }
-  if constexpr (CP) {
-    if (s_list) {
-      wave_fence();
-      sink_compact(s_tab + P.E * 8 * (int)(threadIdx.x >> 6), P.E, lane, s_list, s_list_n);
-    }
-  }
-  ORL_PROFA(9);
-  return desc_out;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// Deferred statistics (round 5).  Most of what ctrl_a does per env is bookkeeping that nothing in the loop reads back: the
-// eight service / bit-rate counters, the running averages of network throughput and compactness, the done / soft-reset
-// logic on them, and the 32-word record that carries them in and out of registers every step — the same arithmetic on all
-// 8 lanes of a group, ~350 VALU instructions and 31 loads + 13 stores per wavefront-step for 8 envs.  The dynamics of an env
-// (slot maps, pending releases, clock, generator) never depend on it.  So the persistent kernel does
-// not do it at all: ctrl_d keeps the clock, the pending service and the release queue's fields, and LOGS per env-step the
-// three words the bookkeeping needs (DevParams::slog); k_stats (orl_kernels.hip) replays the log after the launch with one
-// LANE per env — 64 envs per instruction instead of 8 — in the reference's operation order (rmsa_env.py:163-282, 439-462,
-// 545-597), leaving the record exactly as ctrl_a would have.  Log words of a step:
+// Deferred statistics (round 5).  Most of what the control phase does per env is bookkeeping that nothing in the loop reads
+// back: the eight service / bit-rate counters, the running averages of network throughput and compactness, the done /
+// soft-reset logic on them, and the 32-word record that carries them in and out of registers every step — the same arithmetic
+// on all 8 lanes of a group, ~350 VALU instructions and 31 loads + 13 stores per wavefront-step for 8 envs.  The dynamics of an
+// env (slot maps, pending releases, clock, generator) never depend on it.  So the persistent kernel does not do it at all: its
+// control phase (ctrl_phase<..., DS = true>) keeps the clock, the pending service and the release queue's fields, and LOGS per
+// env-step the three words the bookkeeping needs (DevParams::slog); k_stats (orl_kernels.hip) replays the log after the launch
+// with one LANE per env — 64 envs per instruction instead of 8 — in the reference's operation order (rmsa_env.py:163-282,
+// 439-462, 545-597), leaving the record exactly as the bookkeeping in the step (DS == false) would have.  Log words of a step:
 //   w0  the clock after the step's next service was created (float64 bits)
 //   w1  accepted:1 | n x hops of the provision:12 | bit-rate index of the NEW service:12 | the per-core sums at the START of the
 //       step minus what the previous step's releases added — the network compactness right after the previous step's provision —
@@ -903,9 +615,13 @@ __device__ __forceinline__ u64 slog_w1(bool accepted, int n_hops, int br_new, in
 __device__ __forceinline__ u64 slog_w1_rwa(bool accepted, int n_hops, int path, int slot) {
   return (u64)(accepted ? 1u : 0u) | ((u64)(u32)n_hops << 1) | ((u64)(u32)path << 25) | ((u64)(u32)slot << 29);
 }
+template <int ENV>
+__device__ __forceinline__ u64 slog_w1_of(bool accepted, int n_hops, int path, int slot, int br_new, int occ, int fb, int core) {
+  return (ENV == ENV_RWA) ? slog_w1_rwa(accepted, n_hops, path, slot) : slog_w1(accepted, n_hops, br_new, occ, fb, core);
+}
 __device__ __forceinline__ u64 slog_w2(int d_nh, int d_br) { return (u64)(u32)d_nh | ((u64)(u32)d_br << 20); }
 
-// The six record words ctrl_d reads and writes every step — clock, the pending service's holding time, the release queue's
+// The six record words the DS control phase reads and writes every step — clock, the pending service's holding time, the release queue's
 // bound, horizon, window and free-slot count — live in the wavefront's LDS window for the launch where the records themselves
 // stay in global memory (Wmem::mini: 7 words per env, the seventh for the banks): six loads and nine stores per wavefront-step
 // that went through L2 in the step's dependent chain become LDS accesses or disappear (the pending service's source /
@@ -927,19 +643,31 @@ template <int ENV> __device__ __forceinline__ void svc_words(const DevParams& P,
   sd = pack2(src, dst);
   br = pack2(bit_rate, br_idx);
 }
+// The per-core sums of core c right after the previous step's provision: the totals minus what its releases added (the second
+// half of the env's sums, nc cores) — read through L2 (`l2`) where the row phase updates them with L2 atomics and no kernel boundary
+// invalidates the L1 in between.  A step's releases start from zero.
+__device__ __forceinline__ void sums_after_prov(int* cs, int nc, int c, bool l2, int& occ, int& fb) {
+  int* rs = cs + 2 * nc;
+  if (l2) {
+    occ = atomicAdd(cs + 2 * c, 0) - atomicAdd(rs + 2 * c, 0);
+    fb = atomicAdd(cs + 2 * c + 1, 0) - atomicAdd(rs + 2 * c + 1, 0);
+  } else {
+    occ = cs[2 * c] - rs[2 * c];
+    fb = cs[2 * c + 1] - rs[2 * c + 1];
+  }
+}
+__device__ __forceinline__ void clear_rel_sums(int* cs, int nc, int gl, bool l2) {
+  int* rs = cs + 2 * nc;
+  for (int i = gl; i < 2 * nc; i += 8) {
+    if (l2) atomicExch(rs + i, 0);
+    else rs[i] = 0;
+  }
+}
 // (MINI is a template parameter: a pointer chosen at run time between the LDS window and global memory would be a flat one)
 template <bool MINI> __device__ __forceinline__ u64* mrec(const Wmem& M, u64* rec, i64 env, int slot) {
   if constexpr (MINI) return M.mini + (env - M.mini_env0) * ORL_MINI_STRIDE + mini_index(slot);
   else return rec + slot;
 }
-// the control phase of the persistent kernel without the bookkeeping (services drawn ahead; CP: the single-core families'
-// compact sink, else RMCSA's entries with a core per mask).  `esp`: the env's episode step counter, kept by the caller for the
-// whole launch (done / observation need it); `prev_core` (RMCSA): the core of the env's last accepted provision — the sums
-// logged are that core's; `slog`: this step's log slot, at the env's column.  Returns the descriptor of the new pending service.
-// RW (the two-wavefront form, k_persist): this wavefront applies the masks to the slot maps itself as it appends them (LDS
-// atomics without a return value) and hands the row wavefront only the statistics; `rw_sync` are the pair's counters — [1] steps
-// whose items the row wavefront has read (sink table, mask table, clocks and rows: they may be overwritten), [2] steps whose
-// statistics are complete (the sums) — and `rw_k` the number of steps handed over so far.
 // The hand-over between the two wavefronts of the pair form goes through LDS only: release / acquire at workgroup scope restricted to
 // the LOCAL address space (clang's address-space MMRA on the fence builtin) — on gfx950 an s_waitcnt lgkmcnt(0) before the counter's
 // store, and none of the vmcnt wait a full workgroup-scope release would add for global stores nobody in the pair reads.
@@ -955,54 +683,71 @@ __device__ __forceinline__ void rw_wait_for(const u32* p, u32 want) {
   rw_acquire_lds();
   ORL_DIAG_JITTER();
 }
-// RD (rows deferred, round 6): as RW, this phase changes the slot maps itself — but there is no row phase at all in the loop: every
-// provision and release is logged as an event (SinkT<CP, true>, DevParams::elog; `ecur`: the env's event count so far in this
-// launch, `t_log`: the step's number within the launch) and k_rowstats replays the link statistics and the compactness sums after
-// the launch; the sums fields of log word w1 are left zero here and filled in by that kernel before k_stats reads them.
-template <int ENV, int W, bool CP, bool MINI, bool RW = false, bool RD = false>
-__device__ __forceinline__ u64 ctrl_d(const DevParams& P, const Wmem& M, const CtrlOpts& O, i64 env, bool valid, int lane, Prof& prof,
-                                      const int4& av, u64 desc, typename SinkEntryOf<CP>::type* s_tab, u32* s_tally, int tw, int* s_deferred,
-                                      int* done_out, unsigned short* s_list, u32* s_list_n, SoonRegs* carried, unsigned short* s_mtab,
-                                      SvcBuf& svc, int& esp, int& prev_core, u64* slog, const ScanHand* hand = nullptr, int pop_pre = -2,
-                                      const u32* rw_sync = nullptr, u32 rw_k = 0u, int* ecur = nullptr, int t_log = 0) {
+// The control phase: one env-step of step() for the 8 envs of a wavefront, 8 lanes per env, up to (and excluding) the effects
+// of the provision and the releases on the link rows.  Every part of the step is written once, in the reference's order; the
+// forms differ only where `if constexpr` says so:
+//   DS == false  the bookkeeping stays in the step (k_agent, the two-kernel form k_step_a2, -DORL_PERSIST_DS=0 builds of
+//                k_persist): the full env record in and out of registers (g8::env_load / env_store), counters, network
+//                statistics, done / auto reset; untrusted actions are decoded and validated; `ic` (k_agent) carries what info
+//                needs beyond the record; without a batch of services the step draws its own (g8::next_service)
+//   DS == true   deferred statistics (every production form of k_persist): services drawn ahead; only the clock, the pending
+//                service and the release queue's fields (the six mrec<MINI> words); the three log words of the step for k_stats
+//                (slog).  RW (the pair form): this wavefront applies the masks to the slot maps itself as it appends them (LDS
+//                atomics without a return value) and hands the row wavefront only the statistics, waiting on T.rw_sync.  RD (rows
+//                deferred): it changes the slot maps itself too, but there is no row phase in the loop: every provision and
+//                release is logged as an event (SinkT<CP, true>, DevParams::elog) and k_rowstats replays the link statistics and
+//                the compactness sums after the launch — the sums fields of log word w1 stay zero here, that kernel fills them in
+// The provision and the releases of the step go into ONE queue as mixed items (per link: the provision mask first, then the
+// release masks) and one row phase applies them.  The network-compactness average, which needs the sums between the provision
+// and the releases, is finished by the NEXT step from totals - (what the releases added): the row phase keeps the latter in
+// rel_sums.  `given`: the action (nullptr: P.actions); `hand` / `pop_pre` (DS): the chosen path's slot count and record from the
+// scan's winning lane (single-core families) and the top entry of the env's free-slot stack (-1: empty, -2: not given), requested
+// by the caller before the scan — with both, nothing the decision needs is fetched from global memory behind the scan.
+// C.desc is left the descriptor of the NEW pending service (what the next slot scan needs: pair base, bit-rate index, number of
+// paths).  CP: compact sink entries (SinkEntryC); T.tw: tally words per env (>= ceil(E / 4)).
+template <int ENV, int W, bool CP, bool DS = false, bool MINI = false, bool RW = false, bool RD = false>
+__device__ __forceinline__ void ctrl_phase(const DevParams& P, const Wmem& M, const CtrlOpts& O, const CtrlLds<CP>& T, StepCarry& C,
+                                           i64 env, bool valid, int lane, Prof& prof, const int4* given, int* done_out,
+                                           InfoCarry* ic = nullptr, const ScanHand* hand = nullptr, int pop_pre = -2) {
   static_assert(!RD || (CP && !RW), "rows deferred: single-core families, one wavefront per 8 envs");
-  // `hand`: the chosen path's slot count and record from the scan's winning lane (single-core families); `pop_pre`: the top entry
-  // of the env's free-slot stack (-1: empty), requested by the caller before the scan (-2: not given) — with both, nothing the
-  // decision needs is fetched from global memory behind the scan
-  const int K = P.K, S = P.S, gl = lane & 7;
+  static_assert(DS || (!MINI && !RW && !RD), "record words in LDS, the pair form, rows deferred: deferred statistics only");
+  const int K = P.K, S = P.S, rej = P.allow_rejection ? 1 : 0, gl = lane & 7;
+  if (!O.persistent && blockIdx.x == 0 && threadIdx.x == 0) P.q_def[(size_t)(O.parity ^ 1) * P.q_def_stride] = 0u;  // the buffer the next step appends to
+  const bool clk = DS ? !RD : M.clk != nullptr;  // the clock pair of the row phase (every deferred-statistics form but RD has it)
   u64 desc_out = 0ull;
   SinkT<CP, RD> sink;
-  sink.tab = nullptr; sink.tally = nullptr; sink.tw = tw; sink.active = false; sink.deferred = false; sink.cnt = 0;
-  sink.list = s_list; sink.list_n = s_list_n; sink.mtab = nullptr; sink.nrel = 0; sink.rows = nullptr; sink.roww = 0;
-  sink.ev = nullptr; sink.ev_at = 0; sink.ev_rel0 = 0; sink.ev_t = t_log; sink.ev_clock = 0.0;
-  if constexpr (RW) { rw_wait_for(rw_sync + 1, rw_k); ORL_PROFA(14); }  // (the row wavefront has read the previous step's tables and rows)
-  if (!RW && !RD && lane == 0) *s_list_n = 0u;  // (RW: the list is the row wavefront's)
-  if constexpr (!RD) {
-    typename SinkEntryOf<CP>::type* tb = s_tab + P.E * 8 * (int)(threadIdx.x >> 6);
+  sink.tab = nullptr; sink.tally = nullptr; sink.tw = T.tw; sink.active = false; sink.deferred = false; sink.cnt = 0;
+  sink.list = T.list; sink.list_n = T.list_n; sink.mtab = nullptr; sink.nrel = 0; sink.rows = nullptr; sink.roww = 0;
+  sink.ev = nullptr; sink.ev_at = 0; sink.ev_rel0 = 0; sink.ev_t = C.t; sink.ev_clock = 0.0;
+  if constexpr (RW) { rw_wait_for(T.rw_sync + 1, C.rw_k); ORL_PROFA(14); }  // (the row wavefront has read the previous step's tables and rows)
+  if (!RW && !RD && (DS || T.list_n) && lane == 0) *T.list_n = 0u;  // (RW: the list is the row wavefront's)
+  if constexpr (!RD) {  // every wavefront clears the tables of its own 8 envs: no workgroup barrier
+    typename SinkEntryOf<CP>::type* tb = T.tab + P.E * 8 * (int)(threadIdx.x >> 6);
     if constexpr (!CP) {
-      u32* ty = s_tally + tw * 8 * (int)(threadIdx.x >> 6);
-      for (int i = lane; i < 8 * tw; i += 64) ty[i] = 0u;
-      sink.tally = s_tally + tw * (int)(threadIdx.x >> 3);
+      u32* ty = T.tally + T.tw * 8 * (int)(threadIdx.x >> 6);
+      for (int i = lane; i < 8 * T.tw; i += 64) ty[i] = 0u;
+      sink.tally = T.tally + T.tw * (int)(threadIdx.x >> 3);
     } else {
-      sink.mtab = s_mtab + ORL_MTAB * (int)(threadIdx.x >> 3);
+      sink.mtab = T.mtab + ORL_MTAB * (int)(threadIdx.x >> 3);  // (entries are written before they are read: nothing to clear)
     }
     for (int i = lane; i < 8 * P.E; i += 64) sink_entry_clear(tb[i]);
     wave_fence();
-    sink.tab = s_tab + P.E * (int)(threadIdx.x >> 3);
+    sink.tab = T.tab + P.E * (int)(threadIdx.x >> 3);
   }
   if (valid) {
     u64* rec = wm_scal(P, M, env);
     EnvG e;
-    e.scal = rec;
-    e.env = env;
-    // what the loop itself needs of the record: clock, the pending service's holding time, the release queue
-    {
+    if constexpr (!DS) {
+      g8::env_load(P, e, env, rec);
+    } else {  // what the loop itself needs of the record: clock, the pending service's holding time, the release queue
+      e.scal = rec;
+      e.env = env;
       const u64 w_now = *mrec<MINI>(M, rec, env, SC_NOW), w_ht = *mrec<MINI>(M, rec, env, SC_HT), w_nr = *mrec<MINI>(M, rec, env, SC_NEXTREL);
       const u64 w_ts = *mrec<MINI>(M, rec, env, SC_TSOON), w_ev = *mrec<MINI>(M, rec, env, SC_EV), w_hint = *mrec<MINI>(M, rec, env, SC_HINT);
       e.now = __longlong_as_double((i64)w_now); e.ht = __longlong_as_double((i64)w_ht);
       e.next_rel = __longlong_as_double((i64)w_nr); e.t_soon = __longlong_as_double((i64)w_ts);
       // (the pending service's bit rate from its descriptor: no load)
-      e.br_idx = (int)((desc >> 32) & 0xffffu);
+      e.br_idx = (int)((C.desc >> 32) & 0xffffu);
       e.bit_rate = (ENV == ENV_RWA) ? 0 : ((P.bit_rate_mode == 0) ? P.br_lo + e.br_idx : P.bit_rates[e.br_idx]);
       e.ev_hwm = (int)(u32)w_ev; e.ev_cnt = (int)(w_ev >> 32);
       e.nfree = (int)(u32)w_hint;
@@ -1014,71 +759,120 @@ __device__ __forceinline__ u64 ctrl_d(const DevParams& P, const Wmem& M, const C
         const u64 w = (top >> 2) == 0 ? f0 : (top >> 2) == 1 ? f1 : (top >> 2) == 2 ? f2 : f3;
         e.pop_idx = (top >= 0) ? (int)((w >> (16 * (top & 3))) & 0xffffu) : -1;
       }
+      e.flags = 0;
+      e.s_br = 0; e.s_nh = 0;  // (here: minus what this step's releases take off the sums)
+      e.ev_time = M.evl0 ? M.evl0 + (env - M.env0) * P.ev_cap : P.ev_time + env * P.ev_cap;
+      e.ev_info = P.ev_info + env * P.ev_cap;
+      e.soon_t = P.soon_t + env * ORL_SOON;
+      e.soon_i = P.soon_i + env * ORL_SOON;
+      e.sr_on = false;
+      e.rank_pairs = false;
     }
-    e.flags = 0;
-    e.s_br = 0; e.s_nh = 0;  // (here: minus what this step's releases take off the sums)
-    e.ev_time = M.evl0 ? M.evl0 + (env - M.env0) * P.ev_cap : P.ev_time + env * P.ev_cap;
-    e.ev_info = P.ev_info + env * P.ev_cap;
-    e.soon_t = P.soon_t + env * ORL_SOON;
-    e.soon_i = P.soon_i + env * ORL_SOON;
-    e.sr_on = false;
-    e.rank_pairs = false;
-    if (carried) {
+    if (C.soon) {  // the soon list stays in registers from step to step
       e.sr_on = true;
       e.rank_pairs = O.rank_pairs;
 #pragma unroll
-      for (int k = 0; k < ORL_SOON_PER_LANE; k++) { e.sr_t[k] = carried->t[k]; e.sr_i[k] = carried->i[k]; }
+      for (int k = 0; k < ORL_SOON_PER_LANE; k++) { e.sr_t[k] = C.soon->t[k]; e.sr_i[k] = C.soon->i[k]; }
     }
+    // the info word of this lane's earliest list entry, if it may come due in this step: requested now, the release
+    // detection at the end of the phase finds it in a register
     int pre_idx = -1;
     u64 pre_info = 0ull;
-    if (carried && O.prefetch) {  // (as ctrl_a: the info word of this lane's earliest list entry, if it may come due in this step)
+    if (C.soon && O.prefetch) {
       double pt = e.sr_t[0];
       int pi = e.sr_i[0];
 #pragma unroll
       for (int k = 1; k < ORL_SOON_PER_LANE; k++)
         if (e.sr_t[k] < pt || (e.sr_t[k] == pt && e.sr_i[k] < pi)) { pt = e.sr_t[k]; pi = e.sr_i[k]; }
+      // (t_soon == -inf: the list is stale — after a reset or the serial tail — and its entries mean nothing)
       if (pt <= e.now + P.pf_window && e.t_soon > -__builtin_inf() && (u32)pi < (u32)P.ev_cap) { pre_idx = pi; pre_info = e.ev_info[pi]; }
     }
+    // (!DS without a batch of services: the Mersenne-Twister window the next service draws from, requested now or after the
+    // decision, used after the provision)
+    g8::RngG rng;
+    rng.used = 0; rng.pend_used = 0;
+    if constexpr (!DS) { if (O.prefetch && !C.svc) g8::rng_fill(e, rng, gl); }
     e.bm = wm_bm(P, M, env);
     e.ls = wm_ls(P, M, env);
     e.cs = wm_cs(P, M, env);
     if constexpr ((RW || RD) && CP) { sink.rows = e.bm; sink.roww = W; }
-    if constexpr (RD) { sink.ev = P.elog + env * (i64)(2 * P.elog_cap); sink.ev_at = *ecur; sink.ev_rel0 = *ecur; sink.ev_clock = e.now; }
+    if constexpr (RD) { sink.ev = P.elog + env * (i64)(2 * P.elog_cap); sink.ev_at = C.ecur; sink.ev_rel0 = C.ecur; sink.ev_clock = e.now; }
+    const bool l2 = O.persistent && !M.cs_lds;  // (sums_after_prov)
+    // DS: the sums logged — of the core the env's previous accepted provision went to (its pending network-compactness update,
+    // rmsa_env.py:439-462, is finished by the replay from them)
     int occ_s = 0, fb_s = 0;
-    const int pc_s = (ENV == ENV_RMCSA) ? prev_core : 0;
+    const int pc_s = (ENV == ENV_RMCSA) ? C.prev_core : 0;
     auto read_sums = [&]() {
-      if (ENV != ENV_RWA && !RD) {
-        // the sums right after the previous step's provision — of the core it went to — (its pending network-compactness update,
-        // rmsa_env.py:439-462, is finished by the replay from them); this step's releases start from zero
-        int* rs = e.cs + 2 * P.C;
-        const int pc = pc_s;
-        if (!M.cs_lds) {
-          occ_s = atomicAdd(e.cs + 2 * pc, 0) - atomicAdd(rs + 2 * pc, 0);
-          fb_s = atomicAdd(e.cs + 2 * pc + 1, 0) - atomicAdd(rs + 2 * pc + 1, 0);
-          for (int i = gl; i < 2 * P.C; i += 8) atomicExch(rs + i, 0);
-        } else {
-          occ_s = e.cs[2 * pc] - rs[2 * pc];
-          fb_s = e.cs[2 * pc + 1] - rs[2 * pc + 1];
-          for (int i = gl; i < 2 * P.C; i += 8) rs[i] = 0;
+      if constexpr (ENV != ENV_RWA && !RD) { sums_after_prov(e.cs, P.C, pc_s, l2, occ_s, fb_s); clear_rel_sums(e.cs, P.C, gl, l2); }
+    };
+    if constexpr (!DS) {
+      const u64 acc0 = e.scal[SC_ACC];
+      if ((u32)acc0 & 2u) {
+        // network compactness update the previous step left pending (rmsa_env.py:439-462 with _get_network_compactness at
+        // provision time)
+        const int c0 = (int)((acc0 >> 32) & 31);
+        const i64 s_nh_prov = (i64)(acc0 >> 37);
+        int occ, fb;
+        sums_after_prov(e.cs, P.C, c0, l2, occ, fb);
+        const double a0 = __longlong_as_double((i64)e.scal[SC_GC_A]), td = __longlong_as_double((i64)e.scal[SC_GC_TD]);
+        const double now_a = __longlong_as_double((i64)e.scal[SC_NOWA]);
+        const double cmp = (fb > 0) ? div_pos((double)occ, (double)s_nh_prov) * div_pos((double)P.E, (double)fb) : 1.0;
+        e.g_comp = div_pos(a0 + (cmp * td), now_a);
+      }
+      clear_rel_sums(e.cs, P.C, gl, l2);
+      if (ic && (ENV == ENV_RMSA || ENV == ENV_DEEPRMSA)) {  // _get_network_compactness before the provision (rmsa_env.py:189)
+        int occ, fb;
+        if (l2) { occ = atomicAdd(e.cs, 0); fb = atomicAdd(e.cs + 1, 0); }
+        else { occ = e.cs[0]; fb = e.cs[1]; }
+        ic->prev_comp = (fb > 0) ? ((double)occ / (double)e.s_nh) * ((double)P.E / (double)fb) : 1.0;
+      }
+    } else if constexpr (!RW) {
+      read_sums();  // (RW: at the end of the phase, when the row wavefront has long finished the previous step)
+    }
+    // the action: from the in-kernel slot scan on this slot map (trusted; DeepRMSA's decoded, policy_g) or the agent's
+    const int4 av = given ? *given : *(const int4*)(P.actions + env * 4);
+    int path, slot, mod = 0, core = 0;
+    bool bad = false;
+    if constexpr (ENV == ENV_DEEPRMSA) {  // deeprmsa_env.py:48-58
+      path = K; slot = S;
+      if (DS || (O.trusted && given)) {
+        path = av.y; slot = av.z;
+      } else if constexpr (!DS) {
+        if (av.x >= 0 && av.x < K * P.J) {
+          const int route = av.x / P.J, block = av.x - route * P.J;
+          int start = 0, nb = 0;
+          const int pidx = pair_base(P, e.src, e.dst) + route;
+          if (route < P.n_paths[e.src * P.N + e.dst]) {
+            Row<W> m = g8::path_and_global<W>(P, e, pidx);
+            nb = nth_block<W>(m, S, P.nslots_path[(size_t)pidx * P.n_br + e.br_idx], block + 1, start);
+          }
+          if (block < nb) { path = route; slot = start; }
         }
       }
-    };
-    if constexpr (!RW) read_sums();  // (RW: at the end of the phase, when the row wavefront has long finished the previous step)
-    int path, slot, mod = 0, core = 0;
-    if (ENV == ENV_DEEPRMSA) { path = av.y; slot = av.z; }  // (decoded by the in-kernel scan on this slot map, policy_g)
-    else if (ENV == ENV_RMCSA) { path = av.x; mod = av.y; core = av.z; slot = av.w; }
-    else { path = av.x; slot = av.y; }
-    const int path0 = path, slot0 = slot;
+    } else if constexpr (ENV == ENV_RMCSA) {
+      path = av.x; mod = av.y; core = av.z; slot = av.w;
+      bad = !DS && (path < 0 || path > K || mod < 0 || mod > P.M || core < 0 || core > P.C || slot < 0 || slot > S);
+    } else if constexpr (ENV == ENV_RWA) {
+      path = av.x; slot = av.y;
+      bad = !DS && (path < 0 || path >= K + rej || slot < 0 || slot >= S + rej);
+    } else {
+      path = av.x; slot = av.y;
+      bad = !DS && (path < 0 || path > K || slot < 0 || slot > S);
+    }
+    if (bad) {
+      e.flags |= ORL_FLAG_BAD_ACTION;
+      path = K; slot = S; mod = P.M; core = P.C;
+    }
+    const int path0 = path, slot0 = slot, mod0 = mod, core0 = core;
     ORL_PROFA(2);
-    const int pb = (int)(u32)desc, np_ = (int)((desc >> 48) & 0xffu);
     bool accepted = false;
     int n = 1, n_hops = 0;
     int pushed_idx = -1;
     u64 pushed_info = 0ull;
     double pushed_t = 0.0;
     const bool in_range = (ENV == ENV_RMCSA) ? (path < K && mod < P.M && core < P.C && slot < S) : (path < K && slot < S);
-    if (in_range && path < np_) {
-      const int pidx = pb + path;
+    if (in_range && path < (DS ? (int)((C.desc >> 48) & 0xffu) : P.n_paths[e.src * P.N + e.dst])) {
+      const int pidx = (DS ? (int)(u32)C.desc : pair_base(P, e.src, e.dst)) + path;
       PathRec prec;
       if (ENV != ENV_RMCSA && hand) {  // (the scan's winning lane had both)
         n = hand->n;
@@ -1089,7 +883,28 @@ __device__ __forceinline__ u64 ctrl_d(const DevParams& P, const Wmem& M, const C
         prec = path_rec_load(P, pidx);
       }
       bool ok = true;
-      if (ENV == ENV_RMCSA) {  // _crosstalk_is_acceptable: the two reach limits (rmcsa_env.py:341-384), as ctrl_a
+      if constexpr (!DS) {
+        ok = O.trusted && (ENV != ENV_DEEPRMSA || given != nullptr);
+        if (!ok && slot + n <= S) {  // is_path_free: lane w checks word w of every link row of the path
+          const int hops = path_rec_byte(prec, 0);
+          bool busy = false;
+          if (gl < W) {
+            const u64 m = word_range(slot - 64 * gl, slot + n - 64 * gl);
+            const u64* rowbase = e.bm + (size_t)core * P.E * W + gl;
+            u64 miss = 0;
+            for (int h = 0; h < hops; h += 4) {  // four independent row-word loads in flight
+              const u64 r0 = rowbase[path_rec_byte(prec, 2 + h) * W];
+              const u64 r1 = (h + 1 < hops) ? rowbase[path_rec_byte(prec, 3 + h) * W] : ~0ull;
+              const u64 r2 = (h + 2 < hops) ? rowbase[path_rec_byte(prec, 4 + h) * W] : ~0ull;
+              const u64 r3 = (h + 3 < hops) ? rowbase[path_rec_byte(prec, 5 + h) * W] : ~0ull;
+              miss |= m & ~(r0 & r1 & r2 & r3);
+            }
+            busy = miss != 0ull;
+          }
+          ok = gballot(busy, lane) == 0u;
+        }
+      }
+      if (ok && ENV == ENV_RMCSA) {  // _crosstalk_is_acceptable: the two reach limits (rmcsa_env.py:341-384)
         const double len = P.path_length[pidx];
         ok = (len < P.lmax_xt[mod]) && (len < P.lmax_snr[mod * P.n_br + e.br_idx]);
       }
@@ -1097,13 +912,25 @@ __device__ __forceinline__ u64 ctrl_d(const DevParams& P, const Wmem& M, const C
       if (ok) {
         const int hops = path_rec_byte(prec, 0);
         n_hops = n * hops;
+        if constexpr (!DS) {
+          e.s_br += e.bit_rate;
+          e.s_nh += (i64)n * hops;
+          if (ENV != ENV_RWA) {
+            e.brp += e.bit_rate;
+            e.ebrp += e.bit_rate;
+            if (P.bit_rate_mode == 1 && gl == 0) P.br_hist[env * 2 * P.n_br + P.n_br + e.br_idx] += 1;
+          }
+          e.sa += 1;
+          e.esa += 1;
+        }
         accepted = true;
         if constexpr (RD) sink.ev_rel0 = sink.ev_at + 1;
         pushed_info = ev_pack(pidx, slot, n, core, e.bit_rate);
-        pushed_t = e.now + e.ht;  // (arrival time + holding time: the clock stands at the pending service's arrival)
+        pushed_t = (DS ? e.now : e.at) + e.ht;  // (DS: the clock stands at the pending service's arrival)
 #ifndef ORL_DIAG_NO_PUSH
-        pushed_idx = g8::ev_push(P, e, lane, pushed_t, pushed_info, false);
+        pushed_idx = g8::ev_push(P, e, lane, pushed_t, pushed_info, false);  // (its two stores: after the next service's loads)
 #endif
+        // the provision's rows: first mask of their items; they also count towards the per-link limit
         sink_add(sink, prec, core, slot, n, lane, true);
         if constexpr (!CP)
           for (int h = gl; h < hops; h += 8) {
@@ -1113,88 +940,212 @@ __device__ __forceinline__ u64 ctrl_d(const DevParams& P, const Wmem& M, const C
         ORL_PROFA(4);
       }
     }
-    if (ENV != ENV_RMCSA && P.act2d && gl == 0) act2d_count(P, env, path0, slot0, accepted);
-    if (ENV == ENV_RMCSA && P.act2d && gl == 0) act4d_count(P, env, path0, mod, core, slot0, accepted);
+    if constexpr (!DS) {
+      if (ENV == ENV_RWA) { e.sp += 1; e.esp += 1; }
+      if (ENV == ENV_RMCSA) { e.sp += 1; e.esp += 1; e.brq += e.bit_rate; e.ebrq += e.bit_rate; }
+    }
+    if (ENV != ENV_RMCSA && P.act2d && !bad && gl == 0) act2d_count(P, env, path0, slot0, accepted);
+    if (ENV == ENV_RMCSA && P.act2d && !bad && gl == 0) act4d_count(P, env, path0, mod0, core0, slot0, accepted);
+    if constexpr (!DS && ENV == ENV_RWA) {  // actions_output marginals (rwa_env.py:103, 148-151; DS: logged, w1)
+      i64* h = P.act_hist + env * ((K + 1) + (S + 1));
+      const int npa = K + rej, nsa = S + rej;
+      for (int i = gl; i < npa + nsa; i += 8) {
+        int hi = (i < npa) ? i : (K + 1) + (i - npa);
+        bool hit = !bad && ((i < npa) ? (i == path0) : (i - npa == slot0));
+        if (ic) {  // k_agent: path_action_probability / wavelength_action_probability of info (rwa_env.py:148-151): updated count / services_processed
+          const i64 v = h[hi] + (hit ? 1 : 0);
+          if (hit) h[hi] = v;
+          P.info[env * P.n_info + 2 + i] = (double)v / (double)e.sp;
+        } else if (hit) {
+          h[hi] += 1;
+        }
+      }
+    }
     if (gl == 0) {
       if (O.write_io) {
         P.reward[env] = accepted ? 1.0 : (ENV == ENV_DEEPRMSA ? -1.0 : 0.0);
-        *(int4*)(P.actions + env * 4) = (ENV == ENV_DEEPRMSA) ? make_int4(av.x, 0, 0, 0) : av;
+        if (given) *(int4*)(P.actions + env * 4) = (ENV == ENV_DEEPRMSA) ? make_int4(av.x, 0, 0, 0) : av;
       }
-      if constexpr (!RD) M.clk[2 * (env - M.clk_env0)] = e.now;  // (SC_NOWA is the replay's: every form with this control phase has the clock pair)
+      if constexpr (!DS) {
+        e.scal[SC_ACC] = pack2(accepted ? 1 : 0, core);
+        e.scal[SC_NOWA] = (u64)__double_as_longlong(e.now);
+      }
+      if (clk) M.clk[2 * (env - M.clk_env0)] = e.now;  // (DS: SC_NOWA is the replay's)
     }
     ORL_PROFA(5);
-    // the next service, drawn ahead by svc_generate: from the lane of the group that holds it
-    int br_new;
-    {
-      const int k = svc.cnt & 0xff;
-      const double q = gget(svc.q, k, lane), ht = gget(svc.ht, k, lane);
-      const u32 pk = gget(svc.pk, k, lane);
-      svc.cnt += 1;
-      e.now = e.now + q;
-      br_new = (int)(pk >> 20);
-      int bit_rate = 0;
-      if (ENV != ENV_RWA) bit_rate = (P.bit_rate_mode == 0) ? P.br_lo + br_new : P.bit_rates[br_new];
-      const int src = (int)(pk & 0x3ffu), dst = (int)((pk >> 10) & 0x3ffu);
-      const u64 npn = (u64)(u32)P.n_paths[src * P.N + dst];
-      desc_out = (u64)(u32)((src * P.N + dst) * K) | ((u64)(u32)(ENV != ENV_RWA ? br_new : 0) << 32) | (npn << 48);
-      if (gl == 0) {
-        *mrec<MINI>(M, rec, env, SC_NOW) = (u64)__double_as_longlong(e.now);
-        if (!MINI) rec[SC_AT] = (u64)__double_as_longlong(e.now);  // (with the words in LDS: written back with them at the end of the launch)
-        *mrec<MINI>(M, rec, env, SC_HT) = (u64)__double_as_longlong(ht);
-        if (!MINI) {  // (MINI: the caller writes them from the descriptor when the launch ends)
-          rec[SC_SRC_DST] = pack2(src, dst);
-          rec[SC_BR_IDX] = pack2(bit_rate, ENV != ENV_RWA ? br_new : 0);
+    u64 acc_after = 0ull;
+    if constexpr (!DS) {
+      // the word the network statistics below leave in SC_ACC (recomputed here so that the deferral below need not read it back)
+      acc_after = (accepted && ENV != ENV_RWA && e.now > 0) ? (3ull | ((u64)(u32)core << 32) | ((u64)e.s_nh << 37))
+                                                            : pack2(accepted ? 1 : 0, core);
+      if (ic) {  // the counters as info sees them: after this step's decision, before the next service is counted (rmsa_env.py:234-249)
+        ic->s_nh_prov = e.s_nh;
+        if (gl == 0) {
+          double* io = P.info + env * P.n_info;
+          io[0] = (double)(e.sp - e.sa) / (double)e.sp;
+          io[1] = (double)(e.esp - e.esa) / (double)e.esp;
+          if (ENV != ENV_RWA) {  // (RWA: info goes on with the action probabilities, written beside the histogram update)
+            io[2] = (double)(e.brq - e.brp) / (double)e.brq;
+            io[3] = (double)(e.ebrq - e.ebrp) / (double)e.ebrq;
+          }
+          if ((ENV == ENV_RMSA || ENV == ENV_DEEPRMSA) && P.bit_rate_mode == 1) {  // discrete bit rates: blocking per rate + fairness (rmsa_env.py:217-227, 268-273)
+            const i64* rq = P.br_hist + env * 2 * P.n_br;
+            const i64* pv = rq + P.n_br;
+            double mxv = -__builtin_inf(), mnv = __builtin_inf();
+            for (int i = 0; i < P.n_br; i++) {
+              double bl = 0.0;
+              if (rq[i] > 0) bl = (double)(rq[i] - pv[i]) / (double)rq[i];
+              io[8 + i] = bl;
+              mxv = bl > mxv ? bl : mxv;
+              mnv = bl < mnv ? bl : mnv;
+            }
+            io[8 + P.n_br] = mxv - mnv;
+          }
         }
-        if (O.write_io) P.svc_desc[env] = desc_out;
       }
-    }
-    if constexpr (!RW) {
-      if (gl < 2) {
-        const u64 w1 = (ENV == ENV_RWA) ? slog_w1_rwa(accepted, n_hops, path0, slot0) : slog_w1(accepted, n_hops, br_new, occ_s, fb_s, core);
-        slog[(size_t)gl * (size_t)P.log_stride] = gl == 0 ? (u64)__double_as_longlong(e.now) : w1;
+      if (!O.prefetch && !C.svc) g8::rng_fill(e, rng, gl);
+      if (accepted && ENV != ENV_RWA) {  // _update_network_stats (rmsa_env.py:439-462)
+        double last_update = e.g_last, time_diff = e.now - last_update;
+        if (e.now > 0) {
+          double cur_thr = (double)e.s_br;
+          e.g_thr = div_pos((e.g_thr * last_update) + (cur_thr * time_diff), e.now);
+          // the compactness term needs the sums after the provision's row updates: the next step finishes
+          // g_comp = (g_comp * last_update + compactness * time_diff) / now from these two stashed factors
+          if (gl == 0) {
+            e.scal[SC_GC_A] = (u64)__double_as_longlong(e.g_comp * last_update);
+            e.scal[SC_GC_TD] = (u64)__double_as_longlong(time_diff);
+            e.scal[SC_ACC] = acc_after;  // (s_nh at provision time: < 2^27)
+          }
+        }
+        e.g_last = e.now;
       }
-    } else if (gl == 0) {
-      slog[0] = (u64)__double_as_longlong(e.now);
+      e.new_service = 0;
+      ORL_PROFA(6);
     }
-    if (ENV == ENV_RMCSA && accepted) prev_core = core;
+    // _next_service (rmsa_env.py:545-597): with the draws done ahead (svc_generate) from the lane of the group that holds the
+    // service, else drawn here (the due releases are release_soon's job)
+    int br_new = 0;  // (DS: the bit-rate index of the new service, logged)
+    if (DS || C.svc) {
+      const SvcNext s = svc_take(*C.svc, lane);
+      e.now = e.now + s.q;
+      const int br_idx = (ENV != ENV_RWA) ? (int)(s.pk >> 20) : 0;
+      int bit_rate = 0;
+      if (ENV != ENV_RWA) bit_rate = (P.bit_rate_mode == 0) ? P.br_lo + br_idx : P.bit_rates[br_idx];
+      const int src = (int)(s.pk & 0x3ffu), dst = (int)((s.pk >> 10) & 0x3ffu);
+      if constexpr (DS) {
+        br_new = br_idx;
+        const u64 npn = (u64)(u32)P.n_paths[src * P.N + dst];
+        desc_out = (u64)(u32)((src * P.N + dst) * K) | ((u64)(u32)br_idx << 32) | (npn << 48);
+        if (gl == 0) {
+          *mrec<MINI>(M, rec, env, SC_NOW) = (u64)__double_as_longlong(e.now);
+          if (!MINI) rec[SC_AT] = (u64)__double_as_longlong(e.now);  // (with the words in LDS: written back with them at the end of the launch)
+          *mrec<MINI>(M, rec, env, SC_HT) = (u64)__double_as_longlong(s.ht);
+          if (!MINI) {  // (MINI: the caller writes them from the descriptor when the launch ends)
+            rec[SC_SRC_DST] = pack2(src, dst);
+            rec[SC_BR_IDX] = pack2(bit_rate, br_idx);
+          }
+          if (O.write_io) P.svc_desc[env] = desc_out;
+        }
+      } else {
+        e.id = (int)e.esp;
+        e.src = src; e.dst = dst; e.at = e.now; e.ht = s.ht;
+        e.bit_rate = bit_rate; e.br_idx = br_idx;
+        e.new_service = 1;
+        if (ENV == ENV_RMSA || ENV == ENV_DEEPRMSA) { e.sp += 1; e.esp += 1; }
+        if (ENV != ENV_RWA) {
+          e.brq += bit_rate;
+          e.ebrq += bit_rate;
+          if (P.bit_rate_mode == 1 && gl == 0) P.br_hist[e.env * 2 * P.n_br + br_idx] += 1;
+        }
+      }
+    } else if constexpr (!DS) {
+      g8::next_service<ENV, W>(P, e, lane, rng);
+    }
+    u64* const slog = DS ? P.slog + (size_t)C.t * ORL_SLOG_WORDS * (size_t)P.log_stride + (size_t)env : nullptr;  // this step's log slot
+    if constexpr (DS) {
+      if constexpr (!RW) {
+        if (gl < 2) {
+          const u64 w1 = slog_w1_of<ENV>(accepted, n_hops, path0, slot0, br_new, occ_s, fb_s, core);
+          slog[(size_t)gl * (size_t)P.log_stride] = gl == 0 ? (u64)__double_as_longlong(e.now) : w1;
+        }
+      } else if (gl == 0) {
+        slog[0] = (u64)__double_as_longlong(e.now);
+      }
+      if (ENV == ENV_RMCSA && accepted) C.prev_core = core;
+    }
     ORL_PROFA(7);
     // episode end (rmsa_env.py:263, 310-315: the soft reset re-counts the pending service; rwa_env.py:141, rmcsa_env.py:294: RWA
     // and RMCSA count at the decision)
-    esp += 1;
-    const bool done = (esp == P.episode_length);
-    if (done) esp = (ENV == ENV_RWA) ? 0 : 1;
+    bool done;
+    if constexpr (DS) {
+      C.esp += 1;
+      done = (C.esp == P.episode_length);
+      if (done) C.esp = (ENV == ENV_RWA) ? 0 : 1;
+    } else {
+      done = (e.esp == (i64)P.episode_length);
+      if (done && P.ep_log && gl == 0) episode_log(P, env, e.esa);
+      if (done && O.auto_reset) {
+        e.ebrq = 0; e.ebrp = 0; e.esp = 0; e.esa = 0;
+        if (ENV != ENV_RWA && e.new_service) { e.esp += 1; e.ebrq += e.bit_rate; }
+      }
+    }
     if (gl == 0 && O.write_io) P.done[env] = done ? 1 : 0;
     if (done_out) *done_out = done ? 1 : 0;
+    // the pending-release slot of this step's provision (the rebuild scan of the release detection must find it in memory)
     if (pushed_idx >= 0 && gl == (pushed_idx & 7)) { e.ev_time[pushed_idx] = pushed_t; e.ev_info[pushed_idx] = pushed_info; }
-    if constexpr (!RD) { if (gl == 0) M.clk[2 * (env - M.clk_env0) + 1] = e.now; }
+    if constexpr (!DS) desc_out = g8::env_store(P, e, gl, O.write_io);
+    if (clk && gl == 0) M.clk[2 * (env - M.clk_env0) + 1] = e.now;
     ORL_PROFA(8);
     {
+      // due releases of the step (rmsa_env.py:590-597) -> masks behind the provision's in the same table.  The env record
+      // has gone back already (so that only the handful of release-related fields stays in registers through the
+      // detection); those fields are written again below when the detection changed them.
       SoonRegs soon;
 #ifdef ORL_DIAG_INSTEAD_OF_RELEASES
       ORL_DIAG_INSTEAD_OF_RELEASES
 #else
       release_soon<ENV, W, CP, RD>(P, e, lane, sink, soon, prof, accepted ? 1 : 0, pushed_idx, pushed_info, pre_idx, pre_info);
 #endif
-      if constexpr (RD) *ecur = sink.ev_rel0 + sink.nrel;
+      if constexpr (RD) C.ecur = sink.ev_rel0 + sink.nrel;
+      if constexpr (!DS) { if (!C.svc) g8::rng_commit_stores(e, rng, gl); }  // the Mersenne-Twister words of next_service: behind the detection's loads
       ORL_PROFA(10);
       if (sink.deferred) {
-        // (as ctrl_a) the releases stay pending; rel_serial does them in place at the start of this wavefront's next launch
+        // more releases meet on one link than an item holds masks for: the release state stays as stored and the
+        // serial path (rel_serial: k_rel_tail, or the start of the persistent kernel's next launch) releases them in
+        // place after this step's items
         if (gl == 0) {
-          *s_deferred = 1;
-          rec[SC_ACC] = rec[SC_ACC] | (1ull << 16);
+          if (!O.persistent) {  // two-kernel form: the list k_rel_tail works through
+            u32* dq = P.q_def + (size_t)O.parity * P.q_def_stride;
+            dq[16 + atomicAdd(dq, 1u)] = (u32)env;
+          }
+          if (DS || T.deferred) *T.deferred = 1;  // persistent kernel: this workgroup stops after the row phase
+          if constexpr (DS) {
+            rec[SC_ACC] = rec[SC_ACC] | (1ull << 16);
+          } else {
+            e.scal[SC_ACC] = acc_after | (1ull << 16);
+            e.scal[SC_HINT] = pack2(e.nfree, 0);  // a rebuild may have rewritten the free-slot stack
+          }
         }
       } else {
 #pragma unroll
         for (int k = 0; k < ORL_SOON_PER_LANE; k++) {
           if (e.sr_on) {
-            if (soon.dirty) { e.sr_t[k] = soon.t[k]; e.sr_i[k] = soon.i[k]; }
+            if (soon.dirty) { e.sr_t[k] = soon.t[k]; e.sr_i[k] = soon.i[k]; }  // (dirty == 0: returned untouched)
           } else if ((soon.dirty >> k) & 1) {
             e.soon_t[gl + 8 * k] = soon.t[k];
             e.soon_i[gl + 8 * k] = (u32)soon.i[k];
           }
         }
+        if (!DS && gl == 0) {
+          e.scal[SC_NEXTREL] = (u64)__double_as_longlong(e.next_rel);
+          e.scal[SC_TSOON] = (u64)__double_as_longlong(e.t_soon);
+          e.scal[SC_SBR] = (u64)e.s_br;
+          e.scal[SC_SNH] = (u64)e.s_nh;
+          e.scal[SC_EV] = pack2(e.ev_hwm, e.ev_cnt);
+          e.scal[SC_HINT] = pack2(e.nfree, 0);
+        }
       }
-      if (gl == 0) {
+      if (DS && gl == 0) {
         *mrec<MINI>(M, rec, env, SC_NEXTREL) = (u64)__double_as_longlong(e.next_rel);
         *mrec<MINI>(M, rec, env, SC_TSOON) = (u64)__double_as_longlong(e.t_soon);
         *mrec<MINI>(M, rec, env, SC_EV) = pack2(e.ev_hwm, e.ev_cnt);
@@ -1202,25 +1153,30 @@ __device__ __forceinline__ u64 ctrl_d(const DevParams& P, const Wmem& M, const C
         if (e.flags) rec[SC_FLAGS] = rec[SC_FLAGS] | ((u64)(u32)e.flags << 32);
       }
     }
-    if (gl == 2) slog[2 * (size_t)P.log_stride] = slog_w2((int)(-e.s_nh), (int)(-e.s_br));
-    if constexpr (RW) {
-      rw_wait_for(rw_sync + 2, rw_k);
-      ORL_PROFA(15);
-      read_sums();
-      if (gl == 1)
-        slog[(size_t)P.log_stride] = (ENV == ENV_RWA) ? slog_w1_rwa(accepted, n_hops, path0, slot0) : slog_w1(accepted, n_hops, br_new, occ_s, fb_s, core);
+    if constexpr (DS) {
+      if (gl == 2) slog[2 * (size_t)P.log_stride] = slog_w2((int)(-e.s_nh), (int)(-e.s_br));
+      if constexpr (RW) {
+        rw_wait_for(T.rw_sync + 2, C.rw_k);
+        ORL_PROFA(15);
+        read_sums();
+        if (gl == 1) slog[(size_t)P.log_stride] = slog_w1_of<ENV>(accepted, n_hops, path0, slot0, br_new, occ_s, fb_s, core);
+      }
     }
-    if (carried) {
+    if (C.soon) {
 #pragma unroll
-      for (int k = 0; k < ORL_SOON_PER_LANE; k++) { carried->t[k] = e.sr_t[k]; carried->i[k] = e.sr_i[k]; }
+      for (int k = 0; k < ORL_SOON_PER_LANE; k++) { C.soon->t[k] = e.sr_t[k]; C.soon->i[k] = e.sr_i[k]; }
     }
   }
+  if constexpr (!DS) ORL_PROFA(11);
+  if constexpr (!CP) { if (O.emit_queue) emit_items(P, env, sink, true, lane, P.q_a, P.q_cnt_a); }
   if constexpr (CP && !RW && !RD) {  // (RW: the row wavefront makes its list from the table itself)
-    wave_fence();
-    sink_compact(s_tab + P.E * 8 * (int)(threadIdx.x >> 6), P.E, lane, s_list, s_list_n);
+    if (DS || T.list) {
+      wave_fence();
+      sink_compact(T.tab + P.E * 8 * (int)(threadIdx.x >> 6), P.E, lane, T.list, T.list_n);
+    }
   }
-  ORL_PROFA(11);
-  return desc_out;
+  ORL_PROFA(DS ? 11 : 9);
+  C.desc = desc_out;
 }
 
 // persistent kernel: an item of the row phase read from the sink table in place (RMCSA; the single-core families hand the
@@ -1228,67 +1184,6 @@ __device__ __forceinline__ u64 ctrl_d(const DevParams& P, const Wmem& M, const C
 __device__ __forceinline__ Item item_from_sink(i64 env, int link, const SinkEntry& t) {
   const int nm = (int)((t.crn >> 40) & 15);
   return make_item(env, (u32)link, nm, t.mk0, nm > 4 ? t.mk1 : 0ull, t.crn & 0xffffffffffull, 1 | (int)((t.crn >> 44) & 1) << 1);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// what step() does after the provision, except the link rows: network statistics, next service, done / auto reset
-// ---------------------------------------------------------------------------------------------------------------
-template <int ENV, int W>
-__device__ __forceinline__ bool service_part(const DevParams& P, EnvG& e, i64 env, int lane, int auto_reset, bool accepted, int core,
-                                             bool write_io, g8::RngG& rng, Prof& prof, SvcBuf* svc) {
-  const int gl = lane & 7;
-  if (accepted && ENV != ENV_RWA) {  // _update_network_stats (rmsa_env.py:439-462)
-    double last_update = e.g_last, time_diff = e.now - last_update;
-    if (e.now > 0) {
-      double cur_thr = (double)e.s_br;
-      e.g_thr = div_pos((e.g_thr * last_update) + (cur_thr * time_diff), e.now);
-      // the compactness term needs the sums after the provision's row updates: the next step finishes
-      // g_comp = (g_comp * last_update + compactness * time_diff) / now from these two stashed factors
-      if (gl == 0) {
-        e.scal[SC_GC_A] = (u64)__double_as_longlong(e.g_comp * last_update);
-        e.scal[SC_GC_TD] = (u64)__double_as_longlong(time_diff);
-        e.scal[SC_ACC] = 3ull | ((u64)(u32)core << 32) | ((u64)e.s_nh << 37);  // s_nh at provision time (< 2^27)
-      }
-    }
-    e.g_last = e.now;
-  }
-  e.new_service = 0;
-  ORL_PROFA(6);
-  if (svc) {
-    // _next_service with the draws done ahead (svc_generate): the service comes from the lane of the group that holds it
-    if (!e.new_service) {
-      const int k = svc->cnt & 0xff;
-      const double q = gget(svc->q, k, lane), ht = gget(svc->ht, k, lane);
-      const u32 pk = gget(svc->pk, k, lane);
-      svc->cnt += 1;
-      const double at = e.now + q;
-      e.now = at;
-      const int br_idx = (int)(pk >> 20);
-      int bit_rate = 0;
-      if (ENV != ENV_RWA) bit_rate = (P.bit_rate_mode == 0) ? P.br_lo + br_idx : P.bit_rates[br_idx];
-      e.id = (int)e.esp;
-      e.src = (int)(pk & 0x3ffu); e.dst = (int)((pk >> 10) & 0x3ffu); e.at = at; e.ht = ht;
-      e.bit_rate = bit_rate; e.br_idx = (ENV != ENV_RWA) ? br_idx : 0;
-      e.new_service = 1;
-      if (ENV == ENV_RMSA || ENV == ENV_DEEPRMSA) { e.sp += 1; e.esp += 1; }
-      if (ENV != ENV_RWA) {
-        e.brq += bit_rate;
-        e.ebrq += bit_rate;
-        if (P.bit_rate_mode == 1 && gl == 0) P.br_hist[e.env * 2 * P.n_br + br_idx] += 1;
-      }
-    }
-  } else {
-    g8::next_service<ENV, W>(P, e, lane, rng);  // the due releases are release_soon's job
-  }
-  ORL_PROFA(7);
-  bool done = (e.esp == (i64)P.episode_length);
-  if (done && P.ep_log && gl == 0) episode_log(P, env, e.esa);
-  if (done && auto_reset) {
-    e.ebrq = 0; e.ebrp = 0; e.esp = 0; e.esa = 0;
-    if (ENV != ENV_RWA && e.new_service) { e.esp += 1; e.ebrq += e.bit_rate; }
-  }
-  if (gl == 0 && write_io) P.done[env] = done ? 1 : 0;
-  return done;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

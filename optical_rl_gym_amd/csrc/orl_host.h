@@ -13,8 +13,9 @@
 #include "../../include/orl.h"
 #include "orl_device.h"
 
-// Deferred statistics of the persistent kernel (orl_device_split.h ctrl_d, orl_kernels.hip k_stats): the per-env bookkeeping of a launch is
-// logged and replayed lane-per-env afterwards (RMSA, DeepRMSA, RWA, RMCSA).  -DORL_PERSIST_DS=0 keeps it in the loop.
+// Deferred statistics of the persistent kernel (orl_device_split.h ctrl_phase<..., DS>, orl_kernels.hip k_stats): the per-env
+// bookkeeping of a launch is logged and replayed lane-per-env afterwards (RMSA, DeepRMSA, RWA, RMCSA).  -DORL_PERSIST_DS=0 keeps
+// it in the loop.
 #ifndef ORL_PERSIST_DS
 #define ORL_PERSIST_DS 1
 #endif

@@ -176,6 +176,9 @@ __global__ void __launch_bounds__(256) k_step_a2(DevParams P, int pol, int parit
   const sp::Wmem M = sp::wmem_global(P);
   sp::CtrlOpts O;
   O.persistent = false; O.write_io = true; O.trusted = false; O.emit_queue = true; O.prefetch = false; O.auto_reset = true; O.rank_pairs = false;
+  O.parity = parity;
+  const sp::CtrlLds<false> T = {(sp::SinkEntry*)orl_lds_raw, s_tally, 32, nullptr, nullptr, nullptr, nullptr, nullptr};
+  sp::StepCarry C;
   ORL_PROFA_BEGIN();
   if (FUSED_POLICY) {
     const i64 env0 = env - ((lane >> 3));  // first env of this wavefront
@@ -186,9 +189,9 @@ __global__ void __launch_bounds__(256) k_step_a2(DevParams P, int pol, int parit
     const int4 av = make_int4(a[0], a[1], a[2], a[3]);
     ORL_PROFA(1);
     O.trusted = true;
-    sp::ctrl_a<ENV, W>(P, M, O, env, valid, lane, prof, &av, s_tally, (sp::SinkEntry*)orl_lds_raw, parity, nullptr, nullptr);
+    sp::ctrl_phase<ENV, W, false>(P, M, O, T, C, env, valid, lane, prof, &av, nullptr);
   } else {
-    sp::ctrl_a<ENV, W>(P, M, O, env, valid, lane, prof, nullptr, s_tally, (sp::SinkEntry*)orl_lds_raw, parity, nullptr, nullptr);
+    sp::ctrl_phase<ENV, W, false>(P, M, O, T, C, env, valid, lane, prof, nullptr, nullptr);
   }
   ORL_PROFA_END();
 }
@@ -345,8 +348,8 @@ __device__ __forceinline__ void persist_fill_window(const DevParams& P, i64 env0
   }
 }
 
-// Deferred statistics (orl_device_split.h, ctrl_d): the persistent kernel of the single-core families leaves the per-env
-// bookkeeping to k_stats below.  -DORL_PERSIST_DS=0 builds keep it in the loop (ctrl_a; A/B measurements, cross-checks).
+// Deferred statistics (orl_device_split.h, ctrl_phase<..., DS = true>): the persistent kernel leaves the per-env bookkeeping
+// to k_stats below.  -DORL_PERSIST_DS=0 builds keep it in the loop (DS = false; A/B measurements, cross-checks).
 // (the macros and orl_persist_deferred(): orl_host.h)
 template <int ENV, int LDS> struct PersistDeferred {
   static constexpr bool value = ORL_PERSIST_DS != 0 && ORL_PERSIST_SVC != 0 && LDS != 2 &&
@@ -354,7 +357,7 @@ template <int ENV, int LDS> struct PersistDeferred {
 };
 
 // The bookkeeping of the steps a launch of k_persist ran, one LANE per env: counters, bit-rate sums, the running averages of
-// network throughput and compactness, episode ends — what ctrl_a / service_part (orl_device_split.h) do inside the step,
+// network throughput and compactness, episode ends — what ctrl_phase without DS (orl_device_split.h) does inside the step,
 // statement for statement and in the reference's order (rmsa_env.py:163-282 decision and counters, 439-462
 // _update_network_stats, 545-597 _next_service, 284-359 soft reset; rwa_env.py:101-162), from the three log words per step.
 // Leaves the record exactly as that code would: a pending network-compactness update stays pending (SC_ACC bit 1 with its
@@ -435,7 +438,7 @@ __global__ void __launch_bounds__(64) k_stats(DevParams P, int hist_lds) {
       if (t0 + k < n) {
         const u64 a1 = w1[k], a2 = w2[k];
         if (ENV != ENV_RWA && ((u32)acc & 2u)) {
-          // the previous accepted step's network-compactness update, from the sums right after its provision (ctrl_a)
+          // the previous accepted step's network-compactness update, from the sums right after its provision (as ctrl_phase)
           const int c0 = (int)((acc >> 32) & 31);
           (void)c0;
           const i64 s_nh_prov = (i64)(acc >> 37);
@@ -482,7 +485,7 @@ __global__ void __launch_bounds__(64) k_stats(DevParams P, int hist_lds) {
         }
         acc = pack2(accepted ? 1 : 0, core);
         now_a = now;
-        if (accepted && ENV != ENV_RWA) {  // _update_network_stats (rmsa_env.py:439-462), as service_part
+        if (accepted && ENV != ENV_RWA) {  // _update_network_stats (rmsa_env.py:439-462), as ctrl_phase
           const double last_update = g_last, time_diff = now - last_update;
           if (now > 0) {
             const double cur_thr = (double)s_br;
@@ -571,7 +574,7 @@ __global__ void __launch_bounds__(64) k_stats(DevParams P, int hist_lds) {
 
 // ---- rows-deferred form: the replay of the row statistics (round 6) ----------------------------------------------------------
 // In the rows-deferred forms of k_persist the loop is slot scan + control phase only: the control phase changes the slot maps
-// itself and logs one event per provision / release (sp::ctrl_d<..., RD>).  Nothing the row phase computed feeds a decision —
+// itself and logs one event per provision / release (sp::ctrl_phase<..., RD>).  Nothing the row phase computed feeds a decision —
 // the per-link running averages of _update_link_stats (rmsa_env.py:464-543; rwa_env.py:365-383) and the integer sums behind
 // _get_network_compactness (rmsa_env.py:699-744) are state the loop only ever wrote.  This kernel replays them after the launch
 // with one LANE per link ROW: the lane starts from the row as the launch found it (DevParams::bitmap0, written when the wavefront
@@ -1047,7 +1050,7 @@ __device__ __forceinline__ void persist_row_wave(const DevParams& P, const Persi
     sp::rw_acquire_lds();
     ORL_PROFR(8);  // (idle)
     k++;
-    // the step's work items, from the sink table the control wavefront filled (its own ctrl_d skips this in the pair form)
+    // the step's work items, from the sink table the control wavefront filled (its own control phase skips this in the pair form)
     sp::sink_compact(s_tab, P.E, lane, s_list, s_list_n);
     wave_fence();
     const int n_items = __builtin_amdgcn_readfirstlane((int)*s_list_n);
@@ -1069,7 +1072,7 @@ __device__ __forceinline__ void persist_row_wave(const DevParams& P, const Persi
 
 // RW: the two-wavefront form above (128 threads per workgroup)
 // LDS_ 4 / 5: the rows-deferred forms (round 6) — the window of state 3 / 1 without everything the row phase needed; the loop is
-// slot scan + ctrl_d<..., RD> (which changes the slot maps itself and logs events), k_rowstats replays the rest after the launch
+// slot scan + ctrl_phase<..., RD> (which changes the slot maps itself and logs events), k_rowstats replays the rest after the launch
 #ifdef ORL_TIMING
 // (diagnostic builds) per wavefront of the last launch: the constant 100 MHz clock at entry, at the first step, behind the last step and
 // at the end of the write-back, HW_ID, XCC_ID — tools/wave_timeline.py reads them through the profile call (mode 2; mode 3: the
@@ -1103,7 +1106,7 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
 #define ORL_SYNC() do { if constexpr (RW) { wave_fence(); __builtin_amdgcn_wave_barrier(); } else __syncthreads(); } while (0)
 #endif
   constexpr bool SVC = ORL_PERSIST_SVC != 0;
-  constexpr bool DS = PersistDeferred<ENV, LDS>::value;  // bookkeeping logged for k_stats (ctrl_d) instead of done in the loop
+  constexpr bool DS = PersistDeferred<ENV, LDS>::value;  // bookkeeping logged for k_stats instead of done in the loop
 #ifdef ORL_DIAG_NO_MINI  // (A/B: the control phase's record words stay in the global records)
   constexpr bool MINI = false;
 #else
@@ -1120,7 +1123,7 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
   int* s_deferred = (int*)(orl_lds_raw + L.misc);  // [2], alternating by step
   u32* s_list_n = (u32*)(orl_lds_raw + L.misc + 8);
   u32* rw_sync = (u32*)(orl_lds_raw + L.total);  // (RW: the pair's counters behind the window, then the staged batch of services)
-  u32 rw_k = 0u;                                  // (RW: steps of this launch whose items have been listed)
+  sp::CtrlLds<CP> T = {s_tab, s_tally, L.tw, s_mtab, s_list, s_list_n, s_deferred, rw_sync};
   u32 rw_asked0 = 0u, rw_asked1 = 0u;             // (RW: batches of services asked of the row wavefront so far, per channel)
   u32 rw_early = 0u, rw_early_groups = 0u;        // (RW: the number of the batch asked for a step ahead and not yet taken, 0: none; its groups)
   // (area 0: the batch asked for a step ahead; area 1: one asked for on the spot)
@@ -1169,21 +1172,21 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
   // carried from step to step in registers: the pending service's descriptor and (SR) this lane's entries of the env's soon
   // list.  Requested together with the LDS window, before the row caches are built from it (their latency hides behind
   // that); requested again in the rare case that pending releases are done first.
-  u64 desc = 0ull;
   sp::SoonRegs soon_c;
   soon_c.dirty = 0;
   sp::SvcBuf svb;
   svb.q = 0.0; svb.ht = 0.0; svb.pk = 0u; svb.cnt = 0;
-  int esp_c = 0;        // DS: the env's episode step counter (SC_ESP; the replay keeps the record's copy)
-  int prev_core = 0;    // DS, RMCSA: the core of the env's last accepted provision (the high half of SC_ACC)
-  int ecur = 0;         // RD: events this lane's env has logged in this launch
+  sp::StepCarry C;  // + the descriptor; DS: the episode step counter (SC_ESP; the replay keeps the record's copy), RMCSA: the core of
+                    // the last accepted provision (the high half of SC_ACC); RD: events logged in this launch; RW: steps handed over
+  C.soon = SR ? &soon_c : nullptr;
+  C.svc = SVC ? &svb : nullptr;
   u64 now0_w = 0ull;    // DS: the clock the launch starts at (logged for the replay)
 #define ORL_LOAD_CARRIED()                                                                                  \
   do {                                                                                                      \
-    desc = valid ? P.svc_desc[env] : 0ull;                                                                  \
+    C.desc = valid ? P.svc_desc[env] : 0ull;                                                                \
     if (DS && valid && step < target) {                                                                     \
-      esp_c = (int)P.scal[env * ORL_SCAL_WORDS + SC_ESP];                                                   \
-      if (ENV == ENV_RMCSA) prev_core = (int)((P.scal[env * ORL_SCAL_WORDS + SC_ACC] >> 32) & 31ull);       \
+      C.esp = (int)P.scal[env * ORL_SCAL_WORDS + SC_ESP];                                                   \
+      if (ENV == ENV_RMCSA) C.prev_core = (int)((P.scal[env * ORL_SCAL_WORDS + SC_ACC] >> 32) & 31ull);     \
       now0_w = P.scal[env * ORL_SCAL_WORDS + SC_NOW];                                                       \
     }                                                                                                       \
     if (SVC && valid && step < target) {                                                                    \
@@ -1325,7 +1328,7 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
   if (DS && valid && step < target && (lane & 7) < 2) {
     // header row of the log: the clock the first step is decided at, the bit-rate index of the service it serves
     // (words 0 and 2 of that row: its word 1 is where a wavefront that logs log_cap steps leaves its last sums)
-    P.slog[(size_t)(3 * P.log_cap + 2 * (lane & 7)) * (size_t)P.log_stride + (size_t)env] = (lane & 7) == 0 ? now0_w : ((desc >> 32) & 0xffffull);
+    P.slog[(size_t)(3 * P.log_cap + 2 * (lane & 7)) * (size_t)P.log_stride + (size_t)env] = (lane & 7) == 0 ? now0_w : ((C.desc >> 32) & 0xffffull);
   }
   if (MINI) {
     M.mini = (u64*)(orl_lds_raw + L.mini);
@@ -1409,6 +1412,7 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
     O.prefetch = PF;
     O.auto_reset = true;
     O.rank_pairs = SR;
+    O.parity = 0;
     int done_i = 0;
     {
       int a[4];
@@ -1432,28 +1436,24 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
           if (nfree > 0) pop_pre = (int)((const unsigned short*)(rec_i + SC_FREE0))[nfree - 1];
         }
       }
-      policy_g<ENV, W, 8>(P, sp::wm_bm(P, M, valid_i ? env_i : M.env0), valid_i, (int)(u32)desc, (int)((desc >> 32) & 0xffffu),
-                          (int)((desc >> 48) & 0xffu), lane_i, pol, (pol == POL_PATH_FF && valid_i) ? P.path_col[env_i] : 0, a,
+      policy_g<ENV, W, 8>(P, sp::wm_bm(P, M, valid_i ? env_i : M.env0), valid_i, (int)(u32)C.desc, (int)((C.desc >> 32) & 0xffffu),
+                          (int)((C.desc >> 48) & 0xffu), lane_i, pol, (pol == POL_PATH_FF && valid_i) ? P.path_col[env_i] : 0, a,
                           HAND ? &hand : nullptr);
 #endif
       const int4 av = make_int4(a[0], a[1], a[2], a[3]);
       ORL_PROFA(1);
       if (fair) wave_prio_rotate(wslot, fair);
-      if constexpr (DS) {
-        u64* slog_s = P.slog + (size_t)(step - first_step) * ORL_SLOG_WORDS * (size_t)P.log_stride + (size_t)(valid_i ? env_i : 0);
-        desc = sp::ctrl_d<ENV, W, CP, MINI, RW, RD>(P, M, O, env_i, valid_i, lane_i, prof, av, desc, s_tab, s_tally, L.tw, &s_deferred[step & 1], &done_i,
-                                              s_list, s_list_n, SR ? &soon_c : nullptr, s_mtab, svb, esp_c, prev_core, slog_s,
-                                              HAND ? &hand : nullptr, pop_pre, rw_sync, rw_k, &ecur, step - first_step);
-      } else {
-        desc = sp::ctrl_a<ENV, W, CP>(P, M, O, env_i, valid_i, lane_i, prof, &av, s_tally, s_tab, 0, &s_deferred[step & 1], &done_i,
-                                      s_list, s_list_n, L.tw, SR ? &soon_c : nullptr, s_mtab, nullptr, SVC ? &svb : nullptr);
-      }
+      T.deferred = &s_deferred[step & 1];
+      C.t = step - first_step;
+      // (-DORL_PERSIST_DS=0 builds still instantiate the pair and rows-deferred forms; the host never picks them without DS)
+      sp::ctrl_phase<ENV, W, CP, DS, MINI, DS && RW, DS && RD>(P, M, O, T, C, env_i, valid_i, lane_i, prof, &av, &done_i, nullptr,
+                                                               HAND ? &hand : nullptr, pop_pre);
     }
     ORL_SYNC();  // sink table + item list, clocks, env records
     if (fair) wave_prio_rotate(wslot, fair);
-    if constexpr (RW) {  // the row wavefront takes the items (the slot maps are up to date: ctrl_d applied the masks); this one goes on
-      rw_k++;
-      rw_signal(rw_sync + 0, rw_k, lane_i);
+    if constexpr (RW) {  // the row wavefront takes the items (the slot maps are up to date: the control phase applied the masks); this one goes on
+      C.rw_k++;
+      rw_signal(rw_sync + 0, C.rw_k, lane_i);
       if constexpr (SVC) {
         // the next batch of services, asked for when this one holds one more: the next step — certain to run: this one was not cut
         // short and the launch has room — takes it, the one after finds the new batch drawn
@@ -1490,7 +1490,7 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
       if (valid_i) {
         if (MINI) {  // (the pending service's words are the descriptor's)
           u64 sd, br;
-          sp::svc_words<ENV>(P, desc, sd, br);
+          sp::svc_words<ENV>(P, C.desc, sd, br);
           obs8_env_w<W>(P, sp::wm_bm(P, M, env_i), sd, br, env_i, lane_i, done_i);
         } else {
           obs8_env<W>(P, sp::wm_bm(P, M, env_i), sp::wm_scal(P, M, env_i), env_i, lane_i, done_i);
@@ -1501,14 +1501,14 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
     if (deferred) { left_pending = true; break; }
     // (RD: an env whose event log could not take another step's provision and releases: the wavefront stops here and counts as
     // unfinished, like one that has used up the statistics log)
-    if constexpr (RD) { if (__ballot(valid_i && ecur + 1 + P.rel_limit > P.elog_cap) != 0ull) break; }
+    if constexpr (RD) { if (__ballot(valid_i && C.ecur + 1 + P.rel_limit > P.elog_cap) != 0ull) break; }
   }
   ORL_PROF_END();
 #ifdef ORL_TIMING
   wts2 = wall_clock64();
 #endif
   if constexpr (RW) {
-    rw_wait(rw_sync + 2, rw_k);
+    rw_wait(rw_sync + 2, C.rw_k);
     if (SVC && rw_early != 0u) {  // a batch on order: its groups' own are used up (see above); parked below like any other
       rw_wait(rw_sync + 5, rw_early);
       if (valid && ((rw_early_groups >> (lane >> 3)) & 1u) != 0u) ORL_RW_TAKE(0, lane);
@@ -1527,7 +1527,7 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
       if (ENV != ENV_RWA && !RD && env_t < P.B && (tid_t & 7) == 0) {  // (RD: k_rowstats writes them)
         int* cs = sp::wm_cs(P, M, env_t);
         int* rs = cs + 2 * P.C;
-        const int pc = (ENV == ENV_RMCSA) ? prev_core : 0;  // (this lane's group is env_t's)
+        const int pc = (ENV == ENV_RMCSA) ? C.prev_core : 0;  // (this lane's group is env_t's)
         int occ, fb;
         if (!M.cs_lds) { occ = atomicAdd(cs + 2 * pc, 0) - atomicAdd(rs + 2 * pc, 0); fb = atomicAdd(cs + 2 * pc + 1, 0) - atomicAdd(rs + 2 * pc + 1, 0); }
         else { occ = cs[2 * pc] - rs[2 * pc]; fb = cs[2 * pc + 1] - rs[2 * pc + 1]; }
@@ -1539,7 +1539,7 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
       int tid_e = (int)threadIdx.x;
       asm volatile("" : "+v"(tid_e));
       const i64 env_e = env0 + (tid_e >> 3);
-      if (env_e < P.B && (tid_e & 7) == 0) P.elog_n[env_e] = ecur;
+      if (env_e < P.B && (tid_e & 7) == 0) P.elog_n[env_e] = C.ecur;
     }
   } else if (PersistDeferred<ENV, 0>::value && threadIdx.x == 0) {
     P.log_n[blockIdx.x] = 0;  // (a form that keeps the bookkeeping in the loop: nothing for k_stats)
@@ -1647,7 +1647,7 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
       if (k == 0) P.scal[env_w * ORL_SCAL_WORDS + SC_AT] = v;
     } else if (k == ORL_MINI_WORDS) {
       u64 sd, br;
-      sp::svc_words<ENV>(P, desc, sd, br);
+      sp::svc_words<ENV>(P, C.desc, sd, br);
       P.scal[env_w * ORL_SCAL_WORDS + SC_SRC_DST] = sd;
       P.scal[env_w * ORL_SCAL_WORDS + SC_BR_IDX] = br;
     }
@@ -1669,7 +1669,7 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
   if (step > first_step && step < target && valid_w) {
     // leaving early (deferred releases): the descriptor the next launch / the stand-alone scan reads; action, reward and done
     // of an unfinished run are not host-visible
-    if ((lane & 7) == 0) P.svc_desc[env_w] = desc;
+    if ((lane & 7) == 0) P.svc_desc[env_w] = C.desc;
   }
   if (threadIdx.x == 0) {
     wg_step[blockIdx.x] = step;
@@ -1810,7 +1810,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORL_AGE
   wave_fence();
   sp::CtrlOpts O;
   O.persistent = true; O.write_io = true; O.trusted = false; O.emit_queue = false; O.prefetch = true; O.auto_reset = auto_reset != 0;
-  O.rank_pairs = false;
+  O.rank_pairs = false; O.parity = 0;
+  const sp::CtrlLds<CP> T = {s_tab, s_tally, L.tw, s_mtab, s_list, s_list_n, s_deferred, nullptr};
   int done_i = 0;
   sp::InfoCarry ic;
   ic.prev_comp = 1.0; ic.s_nh_prov = 0;
@@ -1823,7 +1824,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORL_AGE
   constexpr bool SOONR = ORL_AGENT_SOONR != 0;
   sp::SoonRegs soon_c;
   soon_c.dirty = 0;
+  sp::StepCarry C;
   if constexpr (SOONR) {
+    C.soon = &soon_c;
 #pragma unroll
     for (int k = 0; k < ORL_SOON_PER_LANE; k++) {
       soon_c.t[k] = valid ? P.soon_t[env * ORL_SOON + gl + 8 * k] : __builtin_inf();
@@ -1839,8 +1842,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORL_AGE
     av = make_int4(a[0], a[1], a[2], a[3]);
     O.trusted = true;
   }
-  sp::ctrl_a<ENV, W, CP>(P, M, O, env, valid, lane, prof, FUSED ? &av : nullptr, s_tally, s_tab, 0, s_deferred, &done_i, s_list, s_list_n, L.tw,
-                         SOONR ? &soon_c : nullptr, s_mtab, &ic);
+  sp::ctrl_phase<ENV, W, CP>(P, M, O, T, C, env, valid, lane, prof, FUSED ? &av : nullptr, &done_i, &ic);
   if constexpr (SOONR) {
     if (valid) {
 #pragma unroll
@@ -2511,7 +2513,7 @@ template <int W> void persist(orl_batch* b, const DevParams& VP0, hipStream_t st
     }
 #undef ROWSTATS
   }
-  // the bookkeeping of the steps this launch ran, one lane per env (deferred statistics: ctrl_d logged it), behind the launch
+  // the bookkeeping of the steps this launch ran, one lane per env (deferred statistics: the control phase logged it), behind the launch
   // on its stream; the forms that keep it in the loop logged nothing
   if (orl_persist_deferred(VP.env_type) && VP.slog) {
     dim3 gs((unsigned)((VP.B + ORL_STATS_LANES - 1) / ORL_STATS_LANES));

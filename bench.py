@@ -18,6 +18,12 @@ What is timed, however the script is invoked:
 --dump-outputs DIR then writes what the timed run() left for its caller to read back (the batch state after its last step)
 as DIR/<name>.npy, float64 / float32, <= 64 MB in all: see dump_outputs().  The inputs (seeds, preparation steps) depend on
 the arguments only, so two builds run with the same arguments can be compared array for array.
+A plain run stops there: the result line carries the headline and what follows from the timed launches themselves (the
+roofline of k_persist, the state checks, and the PMC traffic / VALU figures of profiles/traffic_*.json where they match this
+build).  --full also measures, after the timed run and the dump, everything that takes runs of its own: the HBM streaming
+peak of the library's own kernels (`roofline.peak_measured*`), the stand-alone slot-scan kernel (`slot_scan_standalone`) and,
+on a single rank unless --no-cpu-baseline, the CPU oracle on one and on all host cores (`cpu_baseline`) and the host-driven /
+agent-loop rates (`host_driven`).  In a plain run those fields are null.
 N > 1: one process per GPU, every rank owns its own 65 536 envs (weak scaling, no collective on the data path; the barrier
 and the max-over-ranks time go through a gloo group — the data path needs no RCCL).  Started under torchrun the script is one
 rank; started by hand with --gpus N > 1 it launches the N ranks itself (fresh child processes, before any GPU call) and
@@ -25,6 +31,7 @@ refuses to run when fewer than N GPUs are visible.  `n_gpus` in the output is th
 each one's own rate.
 
     python bench.py --gpus 1 --steps 300 --warmup 0
+    python bench.py --gpus 1 --steps 300 --full       # + streaming peak, stand-alone scan, CPU baselines, host-driven rates
     python bench.py --gpus 8 --steps 300              # starts 8 ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -210,7 +217,10 @@ def main():
                          "strong: --batch envs in total, cut into contiguous blocks of env indices over the ranks "
                          "(optical_rl_gym_amd.sharding.shard_range) — the headline batch of 65 536 at 1/2/4/8 GPUs")
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the HBM streaming peak, the stand-alone "
+                         "slot scan, the CPU baselines and the host-driven rates (null in a plain run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines and host-driven rates")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the batch state they computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--device", type=int, default=None,
@@ -395,17 +405,18 @@ def main():
                                 achieved=round(rate, 1), frac=round(rate / RANDOM_ACCESS_PEAK, 4))
     # SURVEY 8(d) "report both": beside the 8 TB/s spec peak, what this GPU's HBM delivers to the library's own plain streaming
     # kernels, measured now (orl_debug_stream_peak: 1 GiB, 16 bytes per lane, HIP events, best of 10): a read — the kernel the
-    # counter calibration uses — and a copy (read + write bytes).  `peak_measured` is the higher of the two.
+    # counter calibration uses — and a copy (read + write bytes).  `peak_measured` is the higher of the two.  --full only.
     peak_meas = peak_read = peak_copy = None
-    try:
-        import ctypes as C_
+    if args.full:
+        try:
+            import ctypes as C_
 
-        rd, cp = C_.c_double(), C_.c_double()
-        if env.lib.orl_debug_stream_peak(dev_index, 1 << 30, 10, C_.byref(rd), C_.byref(cp)) == 0 and rd.value > 0:
-            peak_read, peak_copy = rd.value, cp.value
-            peak_meas = max(peak_read, peak_copy)
-    except Exception:  # (a GPU too full for the two buffers: the spec peak alone)
-        peak_meas = None
+            rd, cp = C_.c_double(), C_.c_double()
+            if env.lib.orl_debug_stream_peak(dev_index, 1 << 30, 10, C_.byref(rd), C_.byref(cp)) == 0 and rd.value > 0:
+                peak_read, peak_copy = rd.value, cp.value
+                peak_meas = max(peak_read, peak_copy)
+        except Exception:  # (a GPU too full for the two buffers: the spec peak alone)
+            peak_meas = None
     roofline = dict(bound="hbm", achieved=round(ach, 2), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(ach / HBM_PEAK_GBS, 5),
                     peak_measured=None if peak_meas is None else round(peak_meas, 1),
                     peak_measured_read=None if peak_read is None else round(peak_read, 1),
@@ -422,27 +433,29 @@ def main():
 
     # the stand-alone slot-scan kernel (what orl_batch_policy launches for a host-side agent), on the same steady-state
     # slot maps.  The production loop above does NOT launch it: there the scan is the first phase of k_persist.
-    n_t = 50
-    st2 = env.run(policy, n_t, time_kernels=2)
-    scan_ach = alg["scan"] * B / (st2.ms_policy * 1e-3) / 1e9
-    # ... and on the bytes the kernel's lanes really request: the rows of the k paths of the pending pair (links shared by
-    # several paths are requested once per path), the 32-byte path records, the descriptor in and the action out
-    hops_sum = t.path_hops.reshape(t.n_nodes, t.n_nodes, -1).sum(-1)
-    np_pair = t.n_paths.reshape(t.n_nodes, t.n_nodes)
-    off = ~np.eye(t.n_nodes, dtype=bool)
-    W_ = (env.num_spectrum_resources + 63) // 64
-    W_ = 1 if W_ <= 1 else (2 if W_ <= 2 else (5 if W_ <= 5 else 8))
-    req_env = float(hops_sum[off].mean()) * W_ * 8 * env.num_spatial_resources + 32.0 * float(np_pair[off].mean()) + 8 + 16
-    scan_req = req_env * B / (st2.ms_policy * 1e-3) / 1e9
-    slot_scan = dict(kernel="k_policy", bound="hbm", achieved=round(scan_ach, 2), peak=HBM_PEAK_GBS, unit="GB/s",
-                     frac=round(scan_ach / HBM_PEAK_GBS, 5), us_per_launch=round(st2.ms_policy * 1e3, 2),
-                     algorithmic_bytes_per_launch=int(alg["scan"] * B),
-                     requested_bytes_per_env=round(req_env, 1), requested_gbs=round(scan_req, 2),
-                     requested_frac=round(scan_req / HBM_PEAK_GBS, 5),
-                     note="stand-alone launch (host-side agents); not part of the timed loop, whose scan runs inside " + kernel)
+    slot_scan = None
+    if args.full:
+        n_t = 50
+        st2 = env.run(policy, n_t, time_kernels=2)
+        scan_ach = alg["scan"] * B / (st2.ms_policy * 1e-3) / 1e9
+        # ... and on the bytes the kernel's lanes really request: the rows of the k paths of the pending pair (links shared by
+        # several paths are requested once per path), the 32-byte path records, the descriptor in and the action out
+        hops_sum = t.path_hops.reshape(t.n_nodes, t.n_nodes, -1).sum(-1)
+        np_pair = t.n_paths.reshape(t.n_nodes, t.n_nodes)
+        off = ~np.eye(t.n_nodes, dtype=bool)
+        W_ = (env.num_spectrum_resources + 63) // 64
+        W_ = 1 if W_ <= 1 else (2 if W_ <= 2 else (5 if W_ <= 5 else 8))
+        req_env = float(hops_sum[off].mean()) * W_ * 8 * env.num_spatial_resources + 32.0 * float(np_pair[off].mean()) + 8 + 16
+        scan_req = req_env * B / (st2.ms_policy * 1e-3) / 1e9
+        slot_scan = dict(kernel="k_policy", bound="hbm", achieved=round(scan_ach, 2), peak=HBM_PEAK_GBS, unit="GB/s",
+                         frac=round(scan_ach / HBM_PEAK_GBS, 5), us_per_launch=round(st2.ms_policy * 1e3, 2),
+                         algorithmic_bytes_per_launch=int(alg["scan"] * B),
+                         requested_bytes_per_env=round(req_env, 1), requested_gbs=round(scan_req, 2),
+                         requested_frac=round(scan_req / HBM_PEAK_GBS, 5),
+                         note="stand-alone launch (host-side agents); not part of the timed loop, whose scan runs inside " + kernel)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle.oracle import OracleBatch
 
         n_cpu, warm, timed_c = 128, 1500, 3500  # ~14 s of one host core
@@ -474,7 +487,7 @@ def main():
                                                   "timed in the build container; it cannot travel to the GPU box")
 
     host = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and fam in ("RMSA", "RWA"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and fam in ("RMSA", "RWA"):
         # SURVEY 8(d) second variant: host-supplied uniform-random actions, reward/done/info fetched every step — the
         # PCIe-inclusive rate of an agent on the host (never `value`)
         rng = np.random.RandomState(3)
@@ -527,6 +540,7 @@ def main():
             "per_rank": per_rank,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,  # whether the figures that take runs of their own were measured (null otherwise)
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "timed_region_s": round(timed, 4),
             "higher_is_better": True,

@@ -4,11 +4,11 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$1
 mkdir -p $O
-python3 $R/bench.py --gpus 1 --steps 300 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_cfg2_steps20.json 2> $O/bench_cfg2_steps20.err
+python3 $R/bench.py --gpus 1 --steps 300 --full > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_cfg2_steps20.json 2> $O/bench_cfg2_steps20.err
 for cfg in "cfg1 65536" "cfg3 65536" "cfg4 16384" "cfg5 32768" "cfg1 4096" "cfg2 4096" "cfg3 4096"; do
   set -- $cfg
-  python3 $R/bench.py --workload $1 --batch $2 --steps 200 --no-cpu-baseline > $O/bench_$1_$2.json 2> $O/bench_$1_$2.err
+  python3 $R/bench.py --workload $1 --batch $2 --steps 200 --full --no-cpu-baseline > $O/bench_$1_$2.json 2> $O/bench_$1_$2.err
 done
 python3 -c "
 import json, glob

@@ -8,12 +8,12 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # ---- the two headline commands, and the kernel trace of each --------------------------------------------------------------
-python3 $R/bench.py --gpus 1 --steps 300 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_cfg2_steps20.json 2> $O/bench_cfg2_steps20.err
+python3 $R/bench.py --gpus 1 --steps 300 --full > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_cfg2_steps20.json 2> $O/bench_cfg2_steps20.err
 python3 -c "import json; [print(n, d['value'], d['roofline']['frac'], d['roofline']['us_per_launch']) for n, d in ((n, json.load(open('$O/bench_cfg2%s.json' % n))) for n in ('', '_steps20'))]"
 rm -rf $O/stats_cfg2 $O/stats_cfg2_steps20
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_cfg2 -- python3 $R/bench.py --gpus 1 --steps 300 --no-cpu-baseline > $O/stats_cfg2.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_cfg2_steps20 -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/stats_cfg2_steps20.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_cfg2 -- python3 $R/bench.py --gpus 1 --steps 300 --full --no-cpu-baseline > $O/stats_cfg2.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_cfg2_steps20 -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/stats_cfg2_steps20.log 2>&1
 python3 $R/tools/agent_loop_rate.py cfg2 65536 2> /dev/null | grep "^{" > $O/agent_loop_cfg2.json
 python3 $R/tools/agent_loop_rate.py cfg3 65536 2> /dev/null | grep "^{" > $O/agent_loop_cfg3.json
 cat $O/agent_loop_cfg2.json $O/agent_loop_cfg3.json
@@ -38,14 +38,14 @@ counters cfg2 65536 20 _s20
 if [ "$QUICK" != "quick" ]; then
 for cfg in "cfg1 65536" "cfg3 65536" "cfg4 16384" "cfg5 32768"; do
   set -- $cfg
-  python3 $R/bench.py --workload $1 --batch $2 --steps 200 --no-cpu-baseline > $O/bench_$1_$2.json 2> $O/bench_$1_$2.err
+  python3 $R/bench.py --workload $1 --batch $2 --steps 200 --full --no-cpu-baseline > $O/bench_$1_$2.json 2> $O/bench_$1_$2.err
   rm -rf $O/stats_$1
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$1 -- python3 $R/bench.py --workload $1 --batch $2 --steps 200 --no-cpu-baseline > $O/stats_$1.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$1 -- python3 $R/bench.py --workload $1 --batch $2 --steps 200 --full --no-cpu-baseline > $O/stats_$1.log 2>&1
   counters $1 $2 128 ""
 done
 for cfg in "cfg1 4096" "cfg2 4096" "cfg3 4096"; do
   set -- $cfg
-  python3 $R/bench.py --workload $1 --batch $2 --steps 200 --no-cpu-baseline > $O/bench_$1_$2.json 2> $O/bench_$1_$2.err
+  python3 $R/bench.py --workload $1 --batch $2 --steps 200 --full --no-cpu-baseline > $O/bench_$1_$2.json 2> $O/bench_$1_$2.err
   counters $1 $2 128 _b4096   # (BASELINE's literal batch: the lines of tools/bench_lines.sh then carry traffic / valu too)
 done
 python3 -c "

@@ -266,6 +266,8 @@ int orl_host_free(void* p);
 #define ORL_BUF_ACTION_MASK 7 /* u8 [n_envs][pitch]: the rows of the last orl_batch_action_mask, in that call's layout (pitch of
                                * orl_batch_action_mask_shape); each layout has a buffer of its own, allocated by its first call, so a
                                * pointer taken after a JOINT call keeps showing JOINT rows; n_elements = 0 before any call */
+#define ORL_BUF_MATRIX_PATHS_OBS 8 /* u8 [n_envs][pitch]: rows of the last orl_batch_matrix_paths_observation (pitch of
+                                    * orl_batch_matrix_paths_obs_shape); allocated by the first call, n_elements = 0 before it */
 int orl_batch_device_buffer(orl_batch* b, int which, void** device_ptr, int64_t* n_elements);
 /* The HIP stream (hipStream_t) the batch queues its launches on.  An agent on the same GPU that queues ITS kernels on this
  * stream too (torch: `torch.cuda.ExternalStream(ptr)`) needs no synchronisation between its network and orl_batch_step: the
@@ -341,6 +343,21 @@ void orl_multi_destroy(orl_multi* m);
  * the rows are then copied out densely and the call synchronises. */
 int orl_batch_action_mask_shape(const orl_batch* b, int layout, int32_t* dim, int32_t* pitch);
 int orl_batch_action_mask(orl_batch* b, int layout, uint8_t* out);
+
+/* MatrixObservationWithPaths (qos_constrained_ra.py:440-493) of the pending service of every env, built on the device from the
+ * link counters: QoSConstrainedRA only (other families return ORL_E_INVALID).  Per env a row of dim = links * S * (k + 1) + 1
+ * bytes: the reference's float64 [links, (k + 1) S] matrix flattened link-major, then the service class as a byte (it exceeds 1
+ * for classes >= 2, as in the reference).  Block b of S columns of link l is a prefix run of ones of length
+ *   b = 0: S - a_l (a_l = free units of l);  1 <= b <= k: min(S - a_l + 1, S) if l lies on allowed path b - 1, else 1 if b >= 2,
+ *   l lies on allowed path b - 2 and a_l = 0 (the reference's slice runs one column into the next path's block, clipped at the
+ *   end of the row), else 0.  Path p is allowed iff p < n_paths[src, dst] and (class != 0 or p == 0).
+ * orl_batch_matrix_paths_obs_shape: *dim and the device pitch round_up(dim, 16) of ORL_BUF_MATRIX_PATHS_OBS's rows.
+ * orl_batch_matrix_paths_observation: one launch on the batch's stream into ORL_BUF_MATRIX_PATHS_OBS (no synchronisation,
+ * graph-capturable: the buffer is allocated by the first call, which should therefore come before a capture; a failed
+ * allocation returns ORL_E_HIP and leaves the batch usable); with out != NULL ([n_envs][dim] bytes) the rows are then copied
+ * out densely and the call synchronises. */
+int orl_batch_matrix_paths_obs_shape(const orl_batch* b, int32_t* dim, int32_t* pitch);
+int orl_batch_matrix_paths_observation(orl_batch* b, uint8_t* out);
 
 /* Snapshot / restore of the complete simulation state of the batch (slot maps, pending releases, RNG, statistics,
  * counters).  The reference has no equivalent (no checkpointing); used for long PPO runs. */

@@ -126,6 +126,8 @@ __global__ void k_matrix_obs(DevParams P, unsigned char* out) {
   }
 }
 
+#include "orl_qos_obs.h"  // k_qos_matrix_obs: MatrixObservationWithPaths of QoSConstrainedRA (qos_constrained_ra.py:440-493)
+
 // end of a device-resident run: the network-compactness update the last step left pending (one thread per env), so
 // that every host-visible state is final; also the OR of every env's flag word (as k_flags_or) — one launch, and
 // orl_batch_run fetches its result together with the straggler count in a single copy
@@ -1104,6 +1106,10 @@ extern "C" int orl_host_free(void* p) try {
 }
 ORL_ABI_CATCH_INT
 
+// MatrixObservationWithPaths (orl_qos_obs.h): row length and device pitch, in 64 bits
+static int64_t qos_obs_dim(const DevParams& P) { return (int64_t)P.E * P.S * (P.K + 1) + 1; }
+static int64_t qos_obs_pitch(const DevParams& P) { return (qos_obs_dim(P) + 15) / 16 * 16; }
+
 // action masks (orl_mask.h): row length of `layout` for this batch's family, 0 = not supported
 static int mask_dim(const DevParams& P, int layout) {
   if (P.env_type != ENV_RMSA && P.env_type != ENV_DEEPRMSA && P.env_type != ENV_RWA) return 0;
@@ -1127,6 +1133,10 @@ extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_pt
       if (b->mask_last < 0) { *device_ptr = nullptr; *n_elements = 0; break; }
       *device_ptr = b->mask_buf[b->mask_last];
       *n_elements = B * ((mask_dim(b->P, b->mask_last) + 15) / 16 * 16);
+      break;
+    case ORL_BUF_MATRIX_PATHS_OBS:
+      *device_ptr = b->qobs_buf;
+      *n_elements = b->qobs_buf ? B * qos_obs_pitch(b->P) : 0;
       break;
     default: return fail(ORL_E_INVALID, "unknown buffer %d", which);
   }
@@ -1199,6 +1209,51 @@ extern "C" int orl_batch_action_mask(orl_batch* b, int layout, uint8_t* out) try
   b->mask_last = layout;
   if (out) {
     HIPCHK(hipMemcpy2DAsync(out, (size_t)dim, buf, (size_t)pitch, (size_t)dim, (size_t)B, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+  }
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+static int qos_obs_check(const orl_batch* b) {
+  if (b->P.env_type != ENV_QOS) return fail(ORL_E_INVALID, "MatrixObservationWithPaths is defined for QoSConstrainedRA only");
+  if ((size_t)ORL_QOBS_WAVES * qos_obs_wave_lds(b->P.E, b->P.K) > 64 * 1024)
+    return fail(ORL_E_INVALID, "MatrixObservationWithPaths of %d links x %d paths exceeds the kernel's LDS budget", b->P.E, b->P.K);
+  return ORL_OK;
+}
+
+extern "C" int orl_batch_matrix_paths_obs_shape(const orl_batch* b, int32_t* dim, int32_t* pitch) try {
+  if (!b || !dim || !pitch) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = qos_obs_check(b)) return rc;
+  *dim = (int32_t)qos_obs_dim(b->P);
+  *pitch = (int32_t)qos_obs_pitch(b->P);
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+extern "C" int orl_batch_matrix_paths_observation(orl_batch* b, uint8_t* out) try {
+  if (!b) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = qos_obs_check(b)) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  const int64_t B = b->P.B, dim = qos_obs_dim(b->P), pitch = qos_obs_pitch(b->P);
+  if (!b->qobs_buf) {  // (the first call allocates: it comes before a graph capture)
+    const size_t bytes = (size_t)(B * pitch);
+    unsigned char* p = nullptr;
+    const hipError_t e = hipMalloc((void**)&p, bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();  // (a failed allocation leaves the batch as it was)
+      return fail(ORL_E_HIP, "MatrixObservationWithPaths: allocating %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    }
+    b->qobs_buf = p;
+    b->allocs.push_back(p);
+  }
+  const unsigned grid = (unsigned)((B + ORL_QOBS_WAVES - 1) / ORL_QOBS_WAVES);
+  const size_t lds = (size_t)ORL_QOBS_WAVES * qos_obs_wave_lds(b->P.E, b->P.K);
+  hipLaunchKernelGGL(k_qos_matrix_obs, dim3(grid), dim3(256), lds, b->stream, b->P, b->qobs_buf, (int)pitch);
+  ORL_TK(b, "k_qos_matrix_obs");
+  HIPCHK(hipGetLastError());
+  if (out) {
+    HIPCHK(hipMemcpy2DAsync(out, (size_t)dim, b->qobs_buf, (size_t)pitch, (size_t)dim, (size_t)B, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
   }
   return ORL_OK;

@@ -88,6 +88,8 @@ struct orl_batch {
   unsigned char* mask_buf[2] = {nullptr, nullptr};  // action masks per layout (ORL_MASK_JOINT / _PATH): [B][pitch] bytes, allocated by
                                                    // the first orl_batch_action_mask of that layout (a view of one stays that layout's)
   int mask_last = -1;              // layout of the last launch: what ORL_BUF_ACTION_MASK hands out (-1: none yet)
+  unsigned char* qobs_buf = nullptr;  // MatrixObservationWithPaths (QoSConstrainedRA): [B][pitch] bytes, allocated by the first
+                                    // orl_batch_matrix_paths_observation; what ORL_BUF_MATRIX_PATHS_OBS hands out
 };
 
 #define ORL_TK(B_, NAME)                                                                 \

@@ -549,9 +549,34 @@ class BatchedOpticalEnv:
         self._mask_layout = layout
         return out.view(np.bool_)
 
+    # ---- MatrixObservationWithPaths (include/orl.h, orl_batch_matrix_paths_observation): QoSConstrainedRA only ---------------
+    def matrix_paths_obs_shape(self):
+        """(dim, pitch): dim = links * S * (k + 1) + 1 columns per env, rows pitch bytes apart in the device buffer."""
+        d, p = C.c_int32(), C.c_int32()
+        self._ck(self.lib.orl_batch_matrix_paths_obs_shape(self._h, C.byref(d), C.byref(p)))
+        return d.value, p.value
+
+    def matrix_observation_with_paths(self, fetch=True, out=None):
+        """MatrixObservationWithPaths (qos_constrained_ra.py:440-493) of every env's pending service, built on the device:
+        uint8 [num_envs, dim] — per link a run of ones for its used units, then per path block the usage the link would have
+        with the service on that path; the service class in the last column.  `out` (a C-contiguous uint8 [num_envs, dim]
+        array) receives the rows instead of a fresh array.  fetch=False only queues the launch on the batch's stream — read
+        the rows in place with device_array("matrix_paths_obs") / device_tensor("matrix_paths_obs")."""
+        if not fetch:
+            self._ck(self.lib.orl_batch_matrix_paths_observation(self._h, None))
+            return None
+        dim, _pitch = self.matrix_paths_obs_shape()
+        if out is None:
+            out = np.empty((self.num_envs, dim), np.uint8)
+        elif out.shape != (self.num_envs, dim) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous uint8 array of shape %r" % ((self.num_envs, dim),))
+        self._ck(self.lib.orl_batch_matrix_paths_observation(self._h, out.ctypes.data))
+        return out
+
     # ---- zero-copy device views (an agent on the same GPU: no PCIe in the loop) -------------------------
     _BUFFERS = {"actions": (0, "<i4", 4), "reward": (1, "<f8", 0), "done": (2, "|u1", 0), "info": (3, "<f8", -1),
-                "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0), "action_mask": (7, "|b1", -3)}
+                "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0), "action_mask": (7, "|b1", -3),
+                "matrix_paths_obs": (8, "|u1", -4)}
 
     def device_array(self, name):
         """The batch's device-resident I/O array `name` as an object with `__cuda_array_interface__` (what
@@ -567,6 +592,12 @@ class BatchedOpticalEnv:
             if n.value == 0 or not ptr.value:
                 raise _lib.OrlError("no action mask yet: call action_mask() (fetch=False only queues it) first")
             cols, pitch = self.action_mask_shape(getattr(self, "_mask_layout", "joint"))
+            strides = (pitch, 1)
+        elif cols == -4:  # the rows of the last matrix_observation_with_paths(), [num_envs, dim] at the device pitch
+            if n.value == 0 or not ptr.value:
+                raise _lib.OrlError("no MatrixObservationWithPaths yet: call matrix_observation_with_paths() (fetch=False only "
+                                    "queues it) first")
+            cols, pitch = self.matrix_paths_obs_shape()
             strides = (pitch, 1)
         cols = {-1: self.n_info, -2: self.obs_dim}.get(cols, cols)
         if n.value == 0 or not ptr.value:

@@ -240,6 +240,17 @@ class MultiDeviceBatch:
         out = self._map(lambda r: self.shards[r].action_mask(layout, fetch=fetch))
         return self._cat(out) if fetch else None
 
+    def matrix_paths_obs_shape(self):
+        return self.shards[0].matrix_paths_obs_shape()
+
+    def matrix_observation_with_paths(self, fetch=True, out=None):
+        """The shards' rows in env order; with `out` ([num_envs, dim] uint8, C-contiguous) every shard writes its own rows."""
+        if out is None or not fetch:
+            parts = self._map(lambda r: self.shards[r].matrix_observation_with_paths(fetch=fetch))
+            return self._cat(parts) if fetch else None
+        self._map(lambda r: self.shards[r].matrix_observation_with_paths(out=out[self.bounds[r]:self.bounds[r + 1]]))
+        return out
+
     def sync(self):
         self._map(lambda r: self.shards[r].sync())
 

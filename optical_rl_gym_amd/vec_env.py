@@ -282,7 +282,8 @@ class OpticalVecEnv:
                  obs_dtype=np.float64, observation="default", max_logged_episodes=1 << 20, monitor_spill_path=None,
                  rates_only_info=False):
         """observation: "default" (DeepRMSA: its 1-D vector; other families: None, as their Dict observation holds live
-        objects) or "matrix" (SimpleMatrixObservation built on the device: uint8 [2N + C*E*S]).
+        objects), "matrix" (SimpleMatrixObservation built on the device: uint8 [2N + C*E*S]) or "matrix_paths"
+        (QoSConstrainedRA only: MatrixObservationWithPaths built on the device, uint8 [E*S*(k+1) + 1]).
         max_logged_episodes / monitor_spill_path: the bound of `episode_log` and where rows beyond it go (EpisodeLog).
         rates_only_info (opt-in; the reference's step() always fills every info entry, rmsa_env.py:228-264): when the info
         keywords are blocking rates only, the step kernel may skip the compactness entries and the two link means — then
@@ -296,6 +297,12 @@ class OpticalVecEnv:
         if observation == "matrix":
             t = batch.topology
             dim = 2 * t.n_nodes + batch.num_spatial_resources * t.n_links * batch.num_spectrum_resources
+            self.observation_space = _space_module().Box(low=0, high=1, shape=(dim,), dtype=np.uint8)
+        elif observation == "matrix_paths":
+            if getattr(batch, "ENV_TYPE", None) != 4:
+                raise ValueError("observation='matrix_paths' (MatrixObservationWithPaths) is defined for QoSConstrainedRA only")
+            # (as qos_constrained_ra.py:443-451 declares it: the last entry, the service class, exceeds 1 for classes >= 2)
+            dim, _pitch = batch.matrix_paths_obs_shape()
             self.observation_space = _space_module().Box(low=0, high=1, shape=(dim,), dtype=np.uint8)
         self.info_keywords = tuple(k for k in info_keywords if k in batch.info_keys)
         self._kw_idx = [batch.info_keys.index(k) for k in self.info_keywords]
@@ -347,8 +354,10 @@ class OpticalVecEnv:
         28-MB copy / dtype pass runs on the host per step (float32 is cast on the device)."""
         if self._obs_ring is None:
             make = getattr(self.batch, "host_array", None)
-            shape = (self.num_envs, self.batch.obs_dim)
-            self._obs_ring = [make(shape, self.obs_dtype) if make else np.zeros(shape, self.obs_dtype) for _ in range(3)]
+            shape, dtype = (self.num_envs, self.batch.obs_dim), self.obs_dtype
+            if self.observation_mode == "matrix_paths":  # (the rows of MatrixObservationWithPaths: 0.5 GB at 65 536 envs, S = 64)
+                shape, dtype = (self.num_envs, self.batch.matrix_paths_obs_shape()[0]), np.dtype(np.uint8)
+            self._obs_ring = [make(shape, dtype) if make else np.zeros(shape, dtype) for _ in range(3)]
         self._obs_turn = (self._obs_turn + 1) % 3
         return self._obs_ring[self._obs_turn]
 
@@ -558,14 +567,19 @@ class OpticalVecEnv:
 
     # ---- zero-copy views for an agent on the same GPU ----
     def device_tensors(self):
-        """{"actions", "reward", "done", "info"[, "obs", "terminal_obs"]}: torch views of the batch's device arrays (DLPack /
+        """{"actions", "reward", "done", "info"[, "obs", "terminal_obs"][, "matrix_paths_obs"]}: torch views of the batch's device arrays (DLPack /
         __cuda_array_interface__, no copy).  Write actions, `batch.step(None, auto_reset=True, fetch=False)`, `batch.sync()`."""
         names = ["actions", "reward", "done", "info"] + (["obs", "terminal_obs"] if self.batch.obs_dim else [])
+        if self.observation_mode == "matrix_paths":  # (queued once so that the device buffer exists; rows as the batch stands)
+            self.batch.matrix_observation_with_paths(fetch=False)
+            names.append("matrix_paths_obs")
         return {n: self.batch.device_tensor(n) for n in names}
 
     def _obs(self, obs):
         if self.observation_mode == "matrix":
             return self.batch.matrix_observation()
+        if self.observation_mode == "matrix_paths":
+            return self.batch.matrix_observation_with_paths(out=self._next_obs_buffer())
         if obs is None:
             return None
         return np.array(obs, dtype=self.obs_dtype)

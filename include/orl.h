@@ -142,6 +142,32 @@ int orl_batch_create(const orl_env_config* cfg, const orl_topology* topo, int64_
 int orl_batch_create_seeded(const orl_env_config* cfg, const orl_topology* topo, int64_t n_envs, const int64_t* seeds,
                             orl_batch** out);
 void orl_batch_destroy(orl_batch* b);
+/* Per-env traffic load.  Env i has its own pair (lambda_arrival_i, lambda_holding_i) = (1 / mean_service_inter_arrival_time,
+ * 1 / mean_service_holding_time), computed by the caller with the reference's expressions (optical_network_env.py:92-94,
+ * rmsa_env.py:548-553); the two constructors above give every env the configuration's pair.  Rates are CONFIGURATION, not
+ * simulation state: orl_batch_reset (soft or full), orl_batch_reseed and orl_batch_set_state leave them alone, and they are not
+ * part of orl_batch_state_bytes / the snapshot format — a restored batch keeps the rates it has.
+ * orl_batch_create_with_rates: orl_batch_create / orl_batch_create_seeded (exactly one of mt_state / seeds non-NULL) with
+ * lambda_arrival / lambda_holding [n_envs] each, or NULL = the configuration's scalar for every env.  The rates are on the device
+ * before the constructor's reset draws the first service.  With event_capacity == 0 the capacity is derived from the largest
+ * lambda_arrival / lambda_holding of the batch. */
+int orl_batch_create_with_rates(const orl_env_config* cfg, const orl_topology* topo, int64_t n_envs, const uint32_t* mt_state,
+                                const int64_t* seeds, const double* lambda_arrival, const double* lambda_holding, orl_batch** out);
+/* set_load(load, mean_service_holding_time) (optical_network_env.py:76-94) for the envs selected by env_mask (NULL = all, else
+ * [n_envs] bytes): services drawn after the call use the new rates; the pending service, the clock, the pending releases, the
+ * random stream, counters and statistics do not change.  Arrays [n_envs] (entries of unselected envs are ignored); either may be
+ * NULL = keep.  Ordered on the batch's stream behind whatever is queued; returns synchronised.  Returns ORL_E_INVALID, with
+ * nothing modified, for: a non-finite or non-positive rate of a selected env; a selected env whose load lambda_arrival /
+ * lambda_holding needs more pending releases than the batch's event_capacity (by the formula that derives it at creation);
+ * a batch whose last device-resident run did not complete (services it parked were drawn with the old rates: reset or restore
+ * the batch first, as for orl_batch_get_state). */
+int orl_batch_set_rates(orl_batch* b, const double* lambda_arrival, const double* lambda_holding, const uint8_t* env_mask);
+/* The rates in force, read back from the device: [n_envs] each, either may be NULL. */
+int orl_batch_get_rates(orl_batch* b, double* lambda_arrival_out, double* lambda_holding_out);
+/* Pending releases per env the batch has room for: the configuration's event_capacity, or with 0 the value derived from the
+ * (largest) load, (int)(load + 10 sqrt(load) + 64), either rounded up to a multiple of 64.  What orl_batch_set_rates compares
+ * the same expression of a new load with. */
+int orl_batch_event_capacity(const orl_batch* b);
 
 int orl_batch_info_dim(const orl_batch* b); /* floats per env in the info row */
 int orl_batch_obs_dim(const orl_batch* b);  /* DeepRMSA observation length, else 0 */
@@ -360,7 +386,8 @@ int orl_batch_matrix_paths_obs_shape(const orl_batch* b, int32_t* dim, int32_t* 
 int orl_batch_matrix_paths_observation(orl_batch* b, uint8_t* out);
 
 /* Snapshot / restore of the complete simulation state of the batch (slot maps, pending releases, RNG, statistics,
- * counters).  The reference has no equivalent (no checkpointing); used for long PPO runs. */
+ * counters).  The reference has no equivalent (no checkpointing); used for long PPO runs.  The per-env
+ * rates (orl_batch_set_rates) are configuration and not part of it. */
 int64_t orl_batch_state_bytes(orl_batch* b);
 int orl_batch_get_state(orl_batch* b, void* out);
 int orl_batch_set_state(orl_batch* b, const void* in);

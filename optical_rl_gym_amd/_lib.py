@@ -43,6 +43,11 @@ EXPORTS = {
     "orl_batch_create": (C.c_int, [C.POINTER(EnvConfig), C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)]),
     "orl_batch_create_seeded": (C.c_int, [C.POINTER(EnvConfig), C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)]),
     "orl_batch_destroy": (None, [C.c_void_p]),
+    "orl_batch_create_with_rates": (C.c_int, [C.POINTER(EnvConfig), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_void_p)]),
+    "orl_batch_set_rates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "orl_batch_get_rates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "orl_batch_event_capacity": (C.c_int, [C.c_void_p]),
     "orl_batch_matrix_obs_dim": (C.c_int, [C.c_void_p]),
     "orl_batch_matrix_observation": (C.c_int, [C.c_void_p, C.c_void_p]),
     "orl_batch_state_bytes": (C.c_int64, [C.c_void_p]),

@@ -3,6 +3,7 @@
 // Host side: plain HIP runtime, one stream per batch, no torch types.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <dlfcn.h>
 #include <limits.h>
 #include <math.h>
@@ -386,6 +387,7 @@ static DevParams env_view(const DevParams& P, i64 lo, i64 cnt, int part) {
   q.B = cnt;
   q.bitmap += lo * P.bm_words; q.ev_time += lo * P.ev_cap; q.ev_info += lo * P.ev_cap; q.mt += lo * 624;
   if (q.mt2) q.mt2 += lo * 624;
+  if (q.rates) q.rates += lo;
   q.lstat += lo * 4 * P.E; q.scal += lo * ORL_SCAL_WORDS; q.svc_desc += lo; q.core_sums += lo * P.cs_words;
   q.soon_t += lo * ORL_SOON; q.soon_i += lo * ORL_SOON;
   q.svc_q += lo * 8; q.svc_ht += lo * 8; q.svc_pk += lo * 8; q.svc_cnt += lo * 8;  // (64 lanes per 8 envs; lo is a multiple of 8)
@@ -430,8 +432,12 @@ static int policy_ok(const orl_batch* b, int policy_id) {
   return 1;
 }
 
-// the scalar sizes of DevParams that follow from the configuration alone (no device needed: also what keys a specialisation)
-static void derive_sizes(const orl_env_config* c, int N, int E, int K, int H, int M, int64_t n_envs, DevParams& P, int* wt_out) {
+// pending releases an env at `load` = lambda_arrival / lambda_holding Erlang is given room for when event_capacity is 0
+static int event_capacity_for(double load) { return (int)(load + 10.0 * sqrt(load) + 64.0); }
+// the scalar sizes of DevParams that follow from the configuration alone (no device needed: also what keys a specialisation).
+// `max_load`: the largest lambda_arrival / lambda_holding of a batch with per-env rates (< 0: the configuration's own pair)
+static void derive_sizes(const orl_env_config* c, int N, int E, int K, int H, int M, int64_t n_envs, DevParams& P, int* wt_out,
+                         double max_load = -1.0) {
   const bool qos = c->env_type == ORL_ENV_QOS;
   const int S = c->num_spectrum_resources, C = c->num_spatial_resources;
   P.env_type = c->env_type;
@@ -452,14 +458,11 @@ static void derive_sizes(const orl_env_config* c, int N, int E, int K, int H, in
   P.rand_bits = 0;
   for (int v = P.rand_n; v > 0; v >>= 1) P.rand_bits++;
   P.lambda_a = c->lambda_arrival;
-  P.pf_window = 4.0 / c->lambda_arrival;
   P.lambda_h = c->lambda_holding;
+  P.pf_window = 4.0 / c->lambda_arrival;
   P.B = n_envs;
   int cap = c->event_capacity;
-  if (cap <= 0) {
-    double load = P.lambda_a / P.lambda_h;
-    cap = (int)(load + 10.0 * sqrt(load) + 64.0);
-  }
+  if (cap <= 0) cap = event_capacity_for(max_load >= 0.0 ? max_load : c->lambda_arrival / c->lambda_holding);
   P.ev_cap = (cap + 63) / 64 * 64;
   int words = C * P.E * wt;
   P.bm_words = (words + 1) & ~1;
@@ -482,8 +485,15 @@ static bool pipeline_applies(const orl_env_config* c, const DevParams& P) {
   return P.K <= 8 && P.ev_cap <= 2048 && c->env_type != ORL_ENV_QOS && max_n <= 63 && P.S <= 512;
 }
 
+// the prefetch window of a batch (DevParams::pf_window) from its rates: 4 mean inter-arrival times at the batch's mean arrival rate
+static double pf_window_of(const std::vector<double>& rates) {
+  double sum = 0.0;
+  for (size_t i = 0; i < rates.size(); i += 2) sum += rates[i];
+  return 4.0 / (sum / (double)(rates.size() / 2));
+}
+
 static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int64_t n_envs, const uint32_t* mt_state,
-                             const int64_t* seeds, orl_batch** out) {
+                             const int64_t* seeds, const double* lambda_arrival, const double* lambda_holding, orl_batch** out) {
   if (!c || !t || !out || (!mt_state && !seeds) || n_envs < 1) return fail(ORL_E_INVALID, "null/invalid argument");
   if (c->struct_size != sizeof(orl_env_config))
     return fail(ORL_E_INVALID, "orl_env_config.struct_size is %u, this library (ABI %d) expects %zu: client built against another header",
@@ -515,6 +525,18 @@ static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int
     return fail(ORL_E_INVALID, "continuous mode needs n_bit_rates == hi - lo + 1");
   if (!(c->lambda_arrival > 0) || !(c->lambda_holding > 0)) return fail(ORL_E_INVALID, "rates must be positive");
   if (c->action_histograms && qos) return fail(ORL_E_INVALID, "action histograms are not kept for this env family");
+  // the per-env rates {lambda_arrival, lambda_holding}: the caller's arrays, else the configuration's pair for every env
+  std::vector<double> h_rates((size_t)n_envs * 2);
+  double max_load = -1.0;
+  for (int64_t i = 0; i < n_envs; i++) {
+    const double la = lambda_arrival ? lambda_arrival[i] : c->lambda_arrival, lh = lambda_holding ? lambda_holding[i] : c->lambda_holding;
+    if (!(la > 0) || !(lh > 0) || !std::isfinite(la) || !std::isfinite(lh))
+      return fail(ORL_E_INVALID, "rates must be positive and finite (env %lld)", (long long)i);
+    h_rates[2 * (size_t)i] = la;
+    h_rates[2 * (size_t)i + 1] = lh;
+    if (la / lh > max_load) max_load = la / lh;
+  }
+  const bool per_env = lambda_arrival || lambda_holding;
   HIPCHK(hipSetDevice(t->device));
   // (owned until the last statement: an early return or an exception on the way frees everything allocated so far)
   struct Destroy { void operator()(orl_batch* p) const { orl_batch_destroy(p); } };
@@ -525,7 +547,8 @@ static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int
 #define FAIL_B(...) do { return fail(__VA_ARGS__); } while (0)
 #define HIPCHK_B(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) FAIL_B(ORL_E_HIP, "%s failed: %s", #x, hipGetErrorString(e_)); } while (0)
   DevParams& P = b->P;
-  derive_sizes(c, t->N, t->E, t->K, t->H, t->M, n_envs, P, &b->wt);
+  derive_sizes(c, t->N, t->E, t->K, t->H, t->M, n_envs, P, &b->wt, per_env ? max_load : -1.0);
+  if (per_env) P.pf_window = pf_window_of(h_rates);
   if (P.lds_bytes > 64 * 1024) FAIL_B(ORL_E_INVALID, "per-env LDS window too large (%d B)", P.lds_bytes);
   {
     // The persistent kernel (k_persist) serves the device-resident loop wherever its 8-lanes-per-env slot scan applies
@@ -593,6 +616,11 @@ static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int
   }
   size_t B = (size_t)n_envs;
   rc |= dalloc(b, &P.svc_desc, B);
+  if (per_env) {  // (a uniform batch keeps the two scalars of DevParams: nothing to allocate, nothing for the kernels to load)
+    double2* r = nullptr;
+    rc |= dalloc(b, &r, B);
+    P.rates = r;
+  }
   {
     // one queue region per control wavefront (8 envs), sized for the most items its envs can produce in a step:
     // a provision touches <= H links, the releases of a step <= E links (one item per link)
@@ -670,6 +698,8 @@ static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int
   HIPCHK_B(hipMemsetAsync(P.path_col, 0, B * sizeof(int), b->stream));
   if (P.act2d) HIPCHK_B(hipMemsetAsync(P.act2d, 0, B * (size_t)P.act2d_words * sizeof(int), b->stream));  // (RMSAEnv.reset never clears them)
   HIPCHK_B(hipMemsetAsync(P.actions, 0, B * 4 * sizeof(int), b->stream));
+  // the rates are on the device before the constructor's reset draws the first service with them
+  if (P.rates) HIPCHK_B(hipMemcpyAsync((void*)P.rates, h_rates.data(), B * sizeof(double2), hipMemcpyHostToDevice, b->stream));
   // MT state upload + conversion, then the constructor's full reset
   u32* raw = nullptr;
   HIPCHK_B(hipMalloc((void**)&raw, B * 625 * sizeof(u32)));
@@ -700,13 +730,20 @@ static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int
 extern "C" int orl_batch_create(const orl_env_config* c, const orl_topology* t, int64_t n_envs, const uint32_t* mt_state,
                                 orl_batch** out) try {
   if (!mt_state) return fail(ORL_E_INVALID, "mt_state is null");
-  return batch_create_impl(c, t, n_envs, mt_state, nullptr, out);
+  return batch_create_impl(c, t, n_envs, mt_state, nullptr, nullptr, nullptr, out);
 }
 ORL_ABI_CATCH_INT
 extern "C" int orl_batch_create_seeded(const orl_env_config* c, const orl_topology* t, int64_t n_envs, const int64_t* seeds,
                                        orl_batch** out) try {
   if (!seeds) return fail(ORL_E_INVALID, "seeds is null");
-  return batch_create_impl(c, t, n_envs, nullptr, seeds, out);
+  return batch_create_impl(c, t, n_envs, nullptr, seeds, nullptr, nullptr, out);
+}
+ORL_ABI_CATCH_INT
+extern "C" int orl_batch_create_with_rates(const orl_env_config* c, const orl_topology* t, int64_t n_envs, const uint32_t* mt_state,
+                                           const int64_t* seeds, const double* lambda_arrival, const double* lambda_holding,
+                                           orl_batch** out) try {
+  if ((mt_state != nullptr) == (seeds != nullptr)) return fail(ORL_E_INVALID, "exactly one of mt_state and seeds must be given");
+  return batch_create_impl(c, t, n_envs, mt_state, seeds, lambda_arrival, lambda_holding, out);
 }
 ORL_ABI_CATCH_INT
 
@@ -800,6 +837,77 @@ extern "C" int orl_batch_reseed(orl_batch* b, const int64_t* seeds, const uint8_
   hipFree(dseeds);
   if (e != hipSuccess) return fail(ORL_E_HIP, "reseed failed: %s", hipGetErrorString(e));
   HIPCHK(hipGetLastError());
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+// the rates in force as [B][2] on the host (a uniform batch: its two scalars), behind whatever is queued on the batch's stream
+static int rates_to_host(orl_batch* b, std::vector<double>& h) {
+  const size_t B = (size_t)b->P.B;
+  if (b->P.rates) HIPCHK(hipMemcpyAsync(h.data(), b->P.rates, B * sizeof(double2), hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (!b->P.rates)
+    for (size_t i = 0; i < B; i++) { h[2 * i] = b->P.lambda_a; h[2 * i + 1] = b->P.lambda_h; }
+  return 0;
+}
+extern "C" int orl_batch_event_capacity(const orl_batch* b) { return b ? b->P.ev_cap : 0; }
+extern "C" int orl_batch_get_rates(orl_batch* b, double* lambda_arrival_out, double* lambda_holding_out) try {
+  if (!b) return fail(ORL_E_INVALID, "null batch");
+  HIPCHK(hipSetDevice(b->device));
+  const size_t B = (size_t)b->P.B;
+  std::vector<double> h(B * 2);
+  if (rates_to_host(b, h)) return ORL_E_HIP;
+  for (size_t i = 0; i < B; i++) {
+    if (lambda_arrival_out) lambda_arrival_out[i] = h[2 * i];
+    if (lambda_holding_out) lambda_holding_out[i] = h[2 * i + 1];
+  }
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+// set_load (optical_network_env.py:76-94) of the selected envs: services drawn from here on use the new rates.  Between completed
+// RUNS no service is drawn ahead: svc_generate never draws more services than the launch has steps left and commits words for
+// exactly those, and a launch that ends early (its statistics log full, releases to be done in place) parks what it holds in
+// DevParams::svc_* for the next launch of the SAME run, which orl_batch_run issues before it returns.  This entry point is only
+// reachable between runs, so nothing buffered needs a repair; what an abandoned run left parked is refused.
+extern "C" int orl_batch_set_rates(orl_batch* b, const double* lambda_arrival, const double* lambda_holding, const uint8_t* env_mask) try {
+  if (!b) return fail(ORL_E_INVALID, "null batch");
+  HIPCHK(hipSetDevice(b->device));
+  const size_t B = (size_t)b->P.B;
+  std::vector<double> h(B * 2);
+  if (rates_to_host(b, h)) return ORL_E_HIP;  // (synchronises: behind whatever was queued)
+  if (b->run_abandoned)
+    return fail(ORL_E_INVALID, "the last device-resident run did not complete: reset or restore the batch before changing its rates");
+  for (size_t i = 0; i < B; i++) {
+    if (env_mask && !env_mask[i]) continue;
+    const double la = lambda_arrival ? lambda_arrival[i] : h[2 * i], lh = lambda_holding ? lambda_holding[i] : h[2 * i + 1];
+    if (!(la > 0) || !(lh > 0) || !std::isfinite(la) || !std::isfinite(lh))
+      return fail(ORL_E_INVALID, "rates must be positive and finite (env %zu)", i);
+    if (!std::isfinite(la / lh) || event_capacity_for(la / lh) > b->P.ev_cap)
+      return fail(ORL_E_INVALID, "env %zu: a load of %g Erlang needs an event_capacity of %d, this batch was created with %d", i, la / lh,
+                  std::isfinite(la / lh) ? event_capacity_for(la / lh) : -1, b->P.ev_cap);
+    h[2 * i] = la;
+    h[2 * i + 1] = lh;
+  }
+  bool uniform = true;
+  for (size_t i = 1; i < B && uniform; i++) uniform = h[2 * i] == h[0] && h[2 * i + 1] == h[1];
+  if (!b->P.rates && uniform) {  // one pair for every env again: the batch stays on the scalars
+    b->P.lambda_a = h[0];
+    b->P.lambda_h = h[1];
+  } else {
+    if (!b->P.rates) {  // the first change that gives envs different rates: from here on the batch carries the array
+      double2* r = nullptr;
+      HIPCHK(hipMalloc((void**)&r, B * sizeof(double2) + 64));
+      b->allocs.push_back(r);
+      HIPCHK(hipMemcpyAsync((void*)r, h.data(), B * sizeof(double2), hipMemcpyHostToDevice, b->stream));
+      HIPCHK(hipStreamSynchronize(b->stream));
+      b->P.rates = r;
+    } else {
+      HIPCHK(hipMemcpyAsync((void*)b->P.rates, h.data(), B * sizeof(double2), hipMemcpyHostToDevice, b->stream));
+      HIPCHK(hipStreamSynchronize(b->stream));
+    }
+  }
+  b->P.pf_window = pf_window_of(h);
   return ORL_OK;
 }
 ORL_ABI_CATCH_INT

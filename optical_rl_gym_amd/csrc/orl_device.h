@@ -81,8 +81,14 @@ struct DevParams {
   int env_type, N, E, K, H, M, S, W, C, episode_length, allow_rejection, J;
   int bit_rate_mode, br_lo, n_br, rand_n, rand_bits;
   int ev_cap, bm_words, n_info, obs_dim, lds_bytes, cs_words;
+  // per-env traffic rates {1 / mean_service_inter_arrival_time, 1 / mean_service_holding_time} (rmsa_env.py:548-553), computed on
+  // the host: configuration, not simulation state (orl_batch_set_rates changes them, no reset / seed / set_state does)
+  // `rates` is null for a batch whose envs all share one pair — every batch built without per-env rates, until a set_rates
+  // gives envs different ones: the kernels then divide by the two scalars below (kernel arguments: no load at all)
+  const double2* rates;  // [B] or null
   double lambda_a, lambda_h;
-  double pf_window;  // releases due within this time of the clock are worth an early request of their info word (4 mean inter-arrival times)
+  double pf_window;  // releases due within this time of the clock are worth an early request of their info word (4 mean inter-arrival
+                     // times of the batch: a hint, results do not depend on it)
   i64 B;
   // shared, read-only (L2-resident) topology / traffic tables
   const int* n_paths;               // [N*N]
@@ -964,12 +970,14 @@ __device__ __forceinline__ void release_due(const DevParams& P, Env& e, int lane
 template <int ENV, int W, bool EVL>
 __device__ __forceinline__ void next_service(const DevParams& P, Env& e, int lane, const Rng* prefilled, const Prefetch* pf = nullptr) {
   if (e.new_service) return;
+  // the env's pair: one 16-byte load, requested with the window, needed behind the first logarithm (uniform batch: the scalars)
+  const double2 rate = P.rates ? P.rates[e.env] : make_double2(P.lambda_a, P.lambda_h);
   Rng r;
   if (prefilled) r = *prefilled;  // window loaded at kernel entry so its latency hides behind the step logic
   else rng_fill(e, r, lane);
-  double at = e.now + rng_expovariate(e, r, lane, P.lambda_a);
+  double at = e.now + rng_expovariate(e, r, lane, rate.x);
   e.now = at;
-  double ht = rng_expovariate(e, r, lane, P.lambda_h);
+  double ht = rng_expovariate(e, r, lane, rate.y);
   int src = (pf && pf->have_cum) ? rng_choice_pre(e, r, lane, pf->cum_my, P.N) : rng_choice(e, r, lane, P.cum_src, P.N);
   int dst = rng_choice(e, r, lane, P.cum_dst + src * P.N, P.N);
   int bit_rate = 0, br_idx = 0;

@@ -472,9 +472,12 @@ __device__ __forceinline__ void next_service(const DevParams& P, EnvG& e, int la
   // at = now + expovariate(1/miat); ht = expovariate(1/mht) (rmsa_env.py:548-553): the two random() draws come first, in
   // the reference's order, then lanes 0-3 of the group evaluate -log(1 - u1) / lambda_a and lanes 4-7 -log(1 - u2) / lambda_h
   // in one pass (same operations on the same operands as two calls one after the other)
-  const double u1 = rng_random(e, r, lane), u2 = rng_random(e, r, lane);
+  // (the env's rate — one 8-byte vector load per lane, the env index differs between the groups of a wavefront — is requested
+  // before the draws and needed behind the logarithm)
   const bool second = gl >= 4;
-  const double q = -orl_log(1.0 - (second ? u2 : u1)) / (second ? P.lambda_h : P.lambda_a);
+  const double rate = P.rates ? (second ? P.rates[e.env].y : P.rates[e.env].x) : (second ? P.lambda_h : P.lambda_a);
+  const double u1 = rng_random(e, r, lane), u2 = rng_random(e, r, lane);
+  const double q = -orl_log(1.0 - (second ? u2 : u1)) / rate;
   double at = e.now + gget(q, 0, lane);
   e.now = at;
   double ht = gget(q, 4, lane);

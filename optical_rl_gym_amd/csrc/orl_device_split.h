@@ -348,9 +348,12 @@ __device__ __forceinline__ int svc_choice(const double* cum, int n, double u) {
   return cnt;
 }
 // `rec`: the env's record (LDS window or global), `mt`: its Mersenne-Twister state, `active`: this group draws (its buffer
-// is used up), `n_want`: services wanted (<= 8: the steps the launch has left).  All 64 lanes call.
+// is used up), `n_want`: services wanted (<= 8: the steps the launch has left), `rates_wave`: DevParams::rates of the wavefront's
+// first env, null for a uniform batch (DevParams::lambda_a / lambda_h) (wavefront-uniform: the group's own entry is addressed from the lane index, no per-lane pointer is carried through the
+// window).  All 64 lanes call.
 template <int ENV>
-__device__ __forceinline__ void svc_generate(const DevParams& P, u64* rec, u32* mt, int lane, int n_want, SvcBuf& sb, bool active) {
+__device__ __forceinline__ void svc_generate(const DevParams& P, u64* rec, u32* mt, const double2* rates_wave, int lane, int n_want,
+                                             SvcBuf& sb, bool active) {
   const int gl = lane & 7;
   const bool seek = (ENV != ENV_RWA) && P.bit_rate_mode == 0;  // random.randint: words are drawn until one is below rand_n
   const int FIXED = (ENV == ENV_RWA) ? 8 : (P.bit_rate_mode == 0 ? 8 : 10);
@@ -426,6 +429,9 @@ __device__ __forceinline__ void svc_generate(const DevParams& P, u64* rec, u32* 
     if (active && gl + 8 * k < o) mt[svc_wrap(pos + gl + 8 * k)] = nx[k];
   if (active && gl == 0) rec[SC_ID_MTPOS] = (idw & 0xffffffffull) | ((u64)(u32)svc_wrap(pos + o) << 32);
   if (mine) {
+    // the env's rates: one 16-byte vector load per lane (the env index differs between the groups of a wavefront), requested here,
+    // behind the window's loads and stores, and needed behind the tempering and the two logarithms (only lanes of valid envs get here)
+    const double2 rate = rates_wave ? rates_wave[lane >> 3] : make_double2(P.lambda_a, P.lambda_h);  // (null: a uniform batch)
 #pragma unroll
     for (int t = 0; t < 10; t++) {
       u32 v = w[t];
@@ -439,8 +445,8 @@ __device__ __forceinline__ void svc_generate(const DevParams& P, u64* rec, u32* 
     const double u1 = ORL_SVC_RND(w[0], w[1]), u2 = ORL_SVC_RND(w[2], w[3]);
     const double us = ORL_SVC_RND(w[4], w[5]), ud = ORL_SVC_RND(w[6], w[7]);
     // at = now + expovariate(1 / mean_iat), ht = expovariate(1 / mean_ht) (rmsa_env.py:548-553; random.expovariate)
-    sb.q = -orl_log(1.0 - u1) / P.lambda_a;
-    sb.ht = -orl_log(1.0 - u2) / P.lambda_h;
+    sb.q = -orl_log(1.0 - u1) / rate.x;
+    sb.ht = -orl_log(1.0 - u2) / rate.y;
     const int src = svc_choice(P.cum_src, P.N, us);
     const int dst = svc_choice(P.cum_dst + src * P.N, P.N, ud);
     int br_idx = 0;

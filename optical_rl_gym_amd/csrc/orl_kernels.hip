@@ -1034,7 +1034,7 @@ __device__ __forceinline__ void persist_row_wave(const DevParams& P, const Persi
         const bool active = env < P.B && ((groups >> (lane >> 3)) & 1u) != 0u;
         sp::SvcBuf sb;
         sb.q = 0.0; sb.ht = 0.0; sb.pk = 0u; sb.cnt = 0;
-        sp::svc_generate<ENV>(P, sp::wm_scal(P, M, active ? env : M.scenv0), P.mt + (active ? env : 0) * 624, lane, n_want, sb, active);
+        sp::svc_generate<ENV>(P, sp::wm_scal(P, M, active ? env : M.scenv0), P.mt + (active ? env : 0) * 624, (P.rates ? P.rates + env0 : nullptr), lane, n_want, sb, active);
         stg_q[lane] = sb.q; stg_ht[lane] = sb.ht; stg_pk[lane] = sb.pk; stg_cnt[lane] = sb.cnt;
         if (ch) drawn1++; else drawn0++;
         rw_signal(chan + 1, ch ? drawn1 : drawn0, lane);
@@ -1398,7 +1398,7 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
           }
           wave_fence();  // (the slots are read before a later request can overwrite them)
         } else {
-          sp::svc_generate<ENV>(P, sp::wm_scal(P, M, valid_i ? env_i : M.scenv0), P.mt + (valid_i ? env_i : 0) * 624, lane_i, left < 8 ? left : 8, svb, need);
+          sp::svc_generate<ENV>(P, sp::wm_scal(P, M, valid_i ? env_i : M.scenv0), P.mt + (valid_i ? env_i : 0) * 624, (P.rates ? P.rates + env0 : nullptr), lane_i, left < 8 ? left : 8, svb, need);
         }
       }
 #endif

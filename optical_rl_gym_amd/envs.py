@@ -41,6 +41,41 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
+def per_env_values(value, num_envs, name):
+    """A per-env argument (load, mean_service_holding_time, ...): None for a scalar — one value for the whole batch — else
+    the values as a float64 array of length num_envs.  ValueError for any other shape and for values that are not positive
+    and finite."""
+    if value is None or np.isscalar(value) or (isinstance(value, np.ndarray) and value.ndim == 0):
+        return None
+    a = np.array(value, dtype=np.float64)
+    if a.ndim != 1 or a.shape[0] != int(num_envs):
+        raise ValueError("%s must be a scalar or one value per env (length %d), got shape %r" % (name, num_envs, a.shape))
+    if not (np.isfinite(a).all() and (a > 0).all()):
+        raise ValueError("%s must be positive and finite for every env" % name)
+    return a
+
+
+def _check_scalar(value, name):
+    v = float(value)
+    if not (math.isfinite(v) and v > 0):
+        raise ValueError("%s must be positive and finite" % name)
+    return value
+
+
+def derive_rates(load, mean_service_holding_time):
+    """set_load (optical_network_env.py:92-94) and the two rates _next_service divides by (rmsa_env.py:548-553), per env, in
+    Python floats with the reference's own expressions: (mean_service_inter_arrival_time, lambda_arrival, lambda_holding) as
+    float64 arrays for the arrays `load` and `mean_service_holding_time`."""
+    n = len(load)
+    miat, lam_a, lam_h = np.empty(n, np.float64), np.empty(n, np.float64), np.empty(n, np.float64)
+    for i in range(n):
+        ld, mht = float(load[i]), float(mean_service_holding_time[i])
+        miat[i] = 1 / float(ld / float(mht))
+        lam_a[i] = 1 / miat[i]
+        lam_h[i] = 1 / mht
+    return miat, lam_a, lam_h
+
+
 
 class _PinnedBlock:
     """Owner of one page-locked host allocation (orl_host_alloc); numpy views keep it alive through their base chain."""
@@ -89,11 +124,28 @@ class BatchedOpticalEnv:
         self.channel_width = channel_width
         self.j = j
         # set_load (optical_network_env.py:76-94)
-        self.load = load
-        self.mean_service_holding_time = mean_service_holding_time
-        self.mean_service_inter_arrival_time = 1 / float(load / float(mean_service_holding_time))
-        lambda_a = 1 / self.mean_service_inter_arrival_time  # rmsa_env.py:548-550
-        lambda_h = 1 / self.mean_service_holding_time        # rmsa_env.py:553
+        load_v = per_env_values(load, self.num_envs, "load")
+        mht_v = per_env_values(mean_service_holding_time, self.num_envs, "mean_service_holding_time")
+        if load_v is None and mht_v is None:
+            self.load = load
+            self.mean_service_holding_time = mean_service_holding_time
+            self.mean_service_inter_arrival_time = 1 / float(load / float(mean_service_holding_time))
+            lambda_a = 1 / self.mean_service_inter_arrival_time  # rmsa_env.py:548-550
+            lambda_h = 1 / self.mean_service_holding_time        # rmsa_env.py:553
+            self._rate_arrays = (None, None)
+        else:
+            # one pair per env: env i as a reference env constructed with load[i], mean_service_holding_time[i]
+            if load_v is None:
+                load_v = np.full(self.num_envs, float(_check_scalar(load, "load")), np.float64)
+            if mht_v is None:
+                mht_v = np.full(self.num_envs, float(_check_scalar(mean_service_holding_time, "mean_service_holding_time")), np.float64)
+            self.load, self.mean_service_holding_time = load_v, mht_v
+            self.mean_service_inter_arrival_time, lam_a, lam_h = derive_rates(load_v, mht_v)
+            self._rate_arrays = (lam_a, lam_h)
+            # the configuration's scalar pair is that of the env with the largest load: what sizes the pending-release arrays
+            # (event_capacity=0), and with them the specialisation flags, for the whole batch
+            top = int(np.argmax(lam_a / lam_h))
+            lambda_a, lambda_h = float(lam_a[top]), float(lam_h[top])
         # node pair tables (optical_network_env.py:68-74, 156-173)
         N = t.n_nodes
         if node_request_probabilities is None:
@@ -197,15 +249,24 @@ class BatchedOpticalEnv:
         self._cfg, self._desc = cfg, desc  # (kept: what orl_multi_create takes to build the same envs over several devices)
         self._h = C.c_void_p()
         int_seeds = [41 if s_ is None else int(s_) for s_ in self.seeds]
+        lam_a, lam_h = self._rate_arrays
         if all(-2**63 < s_ < 2**63 for s_ in int_seeds):
             # device-side random.Random(seed): no 2.5 KB/env upload, no Python loop over envs
             sd = np.array(int_seeds, np.int64)
-            self._ck(self.lib.orl_batch_create_seeded(C.byref(cfg), self._topo_h, self.num_envs, sd.ctypes.data,
-                                                        C.byref(self._h)))
+            if lam_a is None:
+                self._ck(self.lib.orl_batch_create_seeded(C.byref(cfg), self._topo_h, self.num_envs, sd.ctypes.data,
+                                                            C.byref(self._h)))
+            else:
+                self._ck(self.lib.orl_batch_create_with_rates(C.byref(cfg), self._topo_h, self.num_envs, None, sd.ctypes.data,
+                                                                lam_a.ctypes.data, lam_h.ctypes.data, C.byref(self._h)))
         else:  # seeds beyond 64 bits: let CPython expand them
             st = mt_states(self.seeds)
-            self._ck(self.lib.orl_batch_create(C.byref(cfg), self._topo_h, self.num_envs, st.ctypes.data,
-                                                 C.byref(self._h)))
+            if lam_a is None:
+                self._ck(self.lib.orl_batch_create(C.byref(cfg), self._topo_h, self.num_envs, st.ctypes.data,
+                                                     C.byref(self._h)))
+            else:
+                self._ck(self.lib.orl_batch_create_with_rates(C.byref(cfg), self._topo_h, self.num_envs, st.ctypes.data, None,
+                                                                lam_a.ctypes.data, lam_h.ctypes.data, C.byref(self._h)))
         self.n_info = self.lib.orl_batch_info_dim(self._h)
         self.obs_dim = self.lib.orl_batch_obs_dim(self._h)
         self.specialised = self._attach_specialisation()
@@ -523,6 +584,63 @@ class BatchedOpticalEnv:
             if m is None or m[i]:
                 self.seeds[i] = int(sd[i])
 
+    # ---- traffic load (include/orl.h, orl_batch_set_rates) ---------------------------------------------
+    def _derive_set_load(self, load=None, mean_service_holding_time=None, mask=None):
+        """What set_load hands to the library and keeps: (load, mean_service_holding_time, mean_service_inter_arrival_time,
+        lambda_arrival[num_envs], lambda_holding[num_envs], mask or None).  Host only; ValueError for a bad argument."""
+        n = self.num_envs
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, np.uint8)
+            if m.shape != (n,):
+                raise ValueError("mask must have one entry per env (length %d), got shape %r" % (n, m.shape))
+        load_v = per_env_values(load, n, "load")
+        mht_v = per_env_values(mean_service_holding_time, n, "mean_service_holding_time")
+        if load is not None and load_v is None:
+            _check_scalar(load, "load")
+        if mean_service_holding_time is not None and mht_v is None:
+            _check_scalar(mean_service_holding_time, "mean_service_holding_time")
+        uniform = m is None and load_v is None and mht_v is None and np.isscalar(self.load) and np.isscalar(self.mean_service_holding_time)
+        if uniform:  # one pair for the whole batch, as the reference env's set_load (optical_network_env.py:86-94)
+            new_load = self.load if load is None else load
+            new_mht = self.mean_service_holding_time if mean_service_holding_time is None else mean_service_holding_time
+            miat = 1 / float(new_load / float(new_mht))
+            return new_load, new_mht, miat, np.full(n, 1 / miat, np.float64), np.full(n, 1 / new_mht, np.float64), None
+        sel = np.ones(n, bool) if m is None else m != 0
+        new_load = np.array(np.broadcast_to(np.asarray(self.load, np.float64), (n,)))
+        new_mht = np.array(np.broadcast_to(np.asarray(self.mean_service_holding_time, np.float64), (n,)))
+        if load is not None:
+            new_load[sel] = load_v[sel] if load_v is not None else float(load)
+        if mean_service_holding_time is not None:
+            new_mht[sel] = mht_v[sel] if mht_v is not None else float(mean_service_holding_time)
+        miat, lam_a, lam_h = derive_rates(new_load, new_mht)
+        return new_load, new_mht, miat, lam_a, lam_h, m
+
+    def set_load(self, load=None, mean_service_holding_time=None, mask=None):
+        """set_load (optical_network_env.py:76-94) of the envs selected by `mask` (default: all): scalars or one value per env.
+        Per env a given load replaces the env's load, a given holding time its holding time, and the mean inter-arrival time
+        follows from the two; services drawn from now on use them, the pending service and everything else stay.  ValueError
+        for a bad value; the library refuses (nothing changed) a load the batch's event_capacity is too small for."""
+        new_load, new_mht, miat, lam_a, lam_h, m = self._derive_set_load(load, mean_service_holding_time, mask)
+        self._ck(self.lib.orl_batch_set_rates(self._h, lam_a.ctypes.data, lam_h.ctypes.data, _ptr(m)))
+        self.load, self.mean_service_holding_time, self.mean_service_inter_arrival_time = new_load, new_mht, miat
+
+    def event_capacity_in_force(self):
+        """Pending releases per env this batch has room for (include/orl.h, orl_batch_event_capacity)."""
+        return int(self.lib.orl_batch_event_capacity(self._h))
+
+    @staticmethod
+    def capacity_needed(load):
+        """The pending releases the library gives an env at `load` Erlang room for — what set_load's load must fit into."""
+        return int(load + 10.0 * math.sqrt(load) + 64.0)
+
+    def rates(self):
+        """(lambda_arrival, lambda_holding) = (1 / mean_service_inter_arrival_time, 1 / mean_service_holding_time) of every
+        env as the device holds them: two float64 arrays of length num_envs."""
+        la, lh = np.zeros(self.num_envs, np.float64), np.zeros(self.num_envs, np.float64)
+        self._ck(self.lib.orl_batch_get_rates(self._h, la.ctypes.data, lh.ctypes.data))
+        return la, lh
+
     # ---- action masks (include/orl.h, orl_batch_action_mask) -------------------------------------------
     MASK_LAYOUTS = {"joint": 0, "path": 1}
 
@@ -803,8 +921,16 @@ class BatchedDeepRMSAEnv(BatchedOpticalEnv):
                  action_histograms=False):
         if seeds is None and seed is not None:
             seeds = seed
+        mht_v = per_env_values(mean_service_holding_time, num_envs, "mean_service_holding_time")
+        miat_v = per_env_values(mean_service_inter_arrival_time, num_envs, "mean_service_inter_arrival_time")
+        if mht_v is None and miat_v is None:
+            load = mean_service_holding_time / mean_service_inter_arrival_time  # deeprmsa_env.py:25
+        else:  # the same division per env, in Python floats
+            h = mht_v if mht_v is not None else [_check_scalar(mean_service_holding_time, "mean_service_holding_time")] * int(num_envs)
+            a = miat_v if miat_v is not None else [_check_scalar(mean_service_inter_arrival_time, "mean_service_inter_arrival_time")] * int(num_envs)
+            load = [float(h[i]) / float(a[i]) for i in range(int(num_envs))]
         self._setup(topology, num_envs, seeds, device_id, episode_length=episode_length,
-                    load=mean_service_holding_time / mean_service_inter_arrival_time,  # deeprmsa_env.py:25
+                    load=load,
                     mean_service_holding_time=mean_service_holding_time,
                     num_spectrum_resources=num_spectrum_resources, allow_rejection=allow_rejection,
                     node_request_probabilities=node_request_probabilities, channel_width=12.5, j=j,

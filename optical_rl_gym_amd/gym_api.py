@@ -251,6 +251,24 @@ class _SingleEnv:
         self.batch.seed([self.rand_seed])
         return [self.rand_seed]
 
+    # ---- traffic load (optical_network_env.py:76-94) ----
+    @property
+    def load(self):
+        return self.batch.load
+
+    @property
+    def mean_service_holding_time(self):
+        return self.batch.mean_service_holding_time
+
+    @property
+    def mean_service_inter_arrival_time(self):
+        return self.batch.mean_service_inter_arrival_time
+
+    def set_load(self, load=None, mean_service_holding_time=None):
+        """optical_network_env.py:76-94: services drawn from now on arrive at `load` Erlang with the given mean holding time
+        (either may be omitted: the env keeps its value); the pending service does not change."""
+        self.batch.set_load(load=load, mean_service_holding_time=mean_service_holding_time)
+
     def close(self):
         if hasattr(self.batch, "close"):
             self.batch.close()

@@ -29,6 +29,23 @@ def shard_seeds(base_seed, n_envs_total, rank, world):
     return [base_seed + i for i in range(lo, hi)]
 
 
+def cut_per_env_kwargs(kwargs, names, num_envs, lo, hi):
+    """`kwargs` for the shard that holds envs [lo, hi) of num_envs: the arguments `names` that carry one value per env (anything
+    but a scalar) are cut to the shard's envs, everything else is passed on as it is.  ValueError for a wrong length."""
+    out = dict(kwargs)
+    for name in names:
+        v = kwargs.get(name)
+        if v is None or np.isscalar(v):
+            continue
+        a = np.asarray(v, np.float64)
+        if a.ndim == 0:
+            continue
+        if a.ndim != 1 or a.shape[0] != num_envs:
+            raise ValueError("%s must be a scalar or one value per env (length %d), got shape %r" % (name, num_envs, a.shape))
+        out[name] = a[lo:hi]
+    return out
+
+
 class MultiRunStats:
     """RunStats of a run over several shards (see MultiDeviceBatch.run)."""
 
@@ -51,6 +68,8 @@ class MultiRunStats:
 class MultiDeviceBatch:
     """`num_envs` envs spread over `device_ids` (contiguous shards), with the methods of `BatchedOpticalEnv`."""
 
+    PER_ENV_KWARGS = ("load", "mean_service_holding_time", "mean_service_inter_arrival_time")
+
     def __init__(self, env_id, num_envs, seeds=None, device_ids=(0,), **kwargs):
         from .envs import ENV_CLASSES
 
@@ -61,7 +80,8 @@ class MultiDeviceBatch:
         shards = []
         for r, dev in enumerate(device_ids):
             lo, hi = shard_range(num_envs, r, len(device_ids))
-            shards.append(ENV_CLASSES[env_id](num_envs=hi - lo, seeds=list(seeds[lo:hi]), device_id=int(dev), **kwargs))
+            kw = cut_per_env_kwargs(kwargs, self.PER_ENV_KWARGS, num_envs, lo, hi)
+            shards.append(ENV_CLASSES[env_id](num_envs=hi - lo, seeds=list(seeds[lo:hi]), device_id=int(dev), **kw))
         self._init_from(shards)
 
     @classmethod
@@ -105,6 +125,69 @@ class MultiDeviceBatch:
         if np.isscalar(seeds):
             seeds = [int(seeds) + i for i in range(self.num_envs)]
         self._map(lambda r: self.shards[r].seed(list(seeds[self.bounds[r]:self.bounds[r + 1]]), mask=self._cut(mask, r)))
+
+    def set_load(self, load=None, mean_service_holding_time=None, mask=None):
+        """set_load of every shard's envs (BatchedOpticalEnv.set_load): per-env arguments and the mask are cut per shard.  Every
+        shard's slice is checked before any shard is changed: the arguments on the host (ValueError), and the resulting rates
+        against each shard's pending-release capacity through a call that selects no env (the library validates nothing for
+        unselected envs, so the loads are checked here with its formula).  What remains is a refusal only the library can give
+        — a shard whose last device-resident run did not complete — which leaves the shards before it changed; the error says
+        which shard."""
+        n = self.num_envs
+
+        def part(v, r, name):
+            if v is None or np.isscalar(v):
+                return v
+            a = np.asarray(v, np.float64)
+            if a.ndim != 1 or a.shape[0] != n:
+                raise ValueError("%s must be a scalar or one value per env (length %d), got shape %r" % (name, n, a.shape))
+            return a[self.bounds[r]:self.bounds[r + 1]]
+
+        if mask is not None and np.asarray(mask).shape != (n,):
+            raise ValueError("mask must have one entry per env (length %d)" % n)
+        args = [(part(load, r, "load"), part(mean_service_holding_time, r, "mean_service_holding_time"), self._cut(mask, r))
+                for r in range(len(self.shards))]
+        for r, (sh, (ld, mht, m)) in enumerate(zip(self.shards, args)):
+            if hasattr(sh, "_derive_set_load"):
+                _l, _h, _i, lam_a, lam_h, mm = sh._derive_set_load(ld, mht, m)
+                if hasattr(sh, "event_capacity_in_force"):
+                    sel = np.ones(sh.num_envs, bool) if mm is None else mm != 0
+                    need = [sh.capacity_needed(a / h) for a, h in zip(lam_a[sel], lam_h[sel])]
+                    if need and max(need) > sh.event_capacity_in_force():
+                        raise ValueError("shard %d: a load of its envs needs an event_capacity of %d, the shard was created with %d"
+                                         % (r, max(need), sh.event_capacity_in_force()))
+
+        def one(r):
+            try:
+                self.shards[r].set_load(load=args[r][0], mean_service_holding_time=args[r][1], mask=args[r][2])
+            except Exception as exc:
+                raise type(exc)("shard %d (envs %d..%d): %s" % (r, self.bounds[r], self.bounds[r + 1] - 1, exc)) from None
+
+        for r in range(len(self.shards)):  # in order: a refusal of shard r leaves shards r.. untouched
+            one(r)
+
+    def rates(self):
+        out = self._map(lambda r: self.shards[r].rates())
+        return self._cat([o[0] for o in out]), self._cat([o[1] for o in out])
+
+    def _per_env_attr(self, name):
+        vals = [getattr(s, name) for s in self.shards]
+        if all(np.isscalar(v) for v in vals) and all(v == vals[0] for v in vals):
+            return vals[0]
+        return np.concatenate([np.full(s.num_envs, v, np.float64) if np.isscalar(v) else np.asarray(v, np.float64)
+                               for s, v in zip(self.shards, vals)])
+
+    @property
+    def load(self):
+        return self._per_env_attr("load")
+
+    @property
+    def mean_service_holding_time(self):
+        return self._per_env_attr("mean_service_holding_time")
+
+    @property
+    def mean_service_inter_arrival_time(self):
+        return self._per_env_attr("mean_service_inter_arrival_time")
 
     def set_info_mode(self, rates_only):
         # (shards without the switch — the oracle stand-in of the CPU tests — always write every entry)

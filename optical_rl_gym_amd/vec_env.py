@@ -478,13 +478,18 @@ class OpticalVecEnv:
             # (sb3-contrib only probes for the method with get_attr; each of these computes and fetches the whole batch's masks —
             # call action_masks() or env_method("action_masks") once for all envs instead)
             return [functools.partial(self._env_action_masks, i) for i in idx]
+        if attr_name in ("load", "mean_service_holding_time", "mean_service_inter_arrival_time"):
+            v = getattr(self.batch, attr_name)  # a scalar for a uniform batch, else one value per env
+            return [v if np.isscalar(v) else float(v[i]) for i in idx]
         if hasattr(self, "_extra_attrs") and attr_name in self._extra_attrs:
             return [self._extra_attrs[attr_name][i] for i in idx]
         return [getattr(self.batch, attr_name) for _ in idx]
 
     def set_attr(self, attr_name, value, indices=None):
         """Attributes set through the VecEnv live beside the batch (one value per env): the simulation parameters of a batch
-        are fixed at construction, like a reference env's after __init__."""
+        are fixed at construction, like a reference env's after __init__ — but for the traffic load, which
+        `env_method("set_load", load=..., mean_service_holding_time=..., indices=...)` changes per env as the reference's
+        set_load does."""
         if not hasattr(self, "_extra_attrs"):
             self._extra_attrs = {}
         col = self._extra_attrs.setdefault(attr_name, [None] * self.num_envs)
@@ -508,6 +513,12 @@ class OpticalVecEnv:
             obs = self._obs(self.batch.observation() if self.batch.obs_dim else None)
             return [None if obs is None else np.array(obs[i]) for i in idx]
         if method_name == "render":
+            return [None for _ in idx]
+        if method_name == "set_load":  # optical_network_env.py:76-94 on the selected envs
+            load = method_args[0] if method_args else method_kwargs.get("load")
+            mht = method_args[1] if len(method_args) > 1 else method_kwargs.get("mean_service_holding_time")
+            # (indices=None is a change of the whole batch: no mask, so that scalar arguments keep the batch's attributes scalars)
+            self.batch.set_load(load=load, mean_service_holding_time=mht, mask=None if indices is None else mask)
             return [None for _ in idx]
         if method_name == "action_masks":  # one row per env (np.stack of the list is MaskablePPO's mask array)
             m = self.action_masks()

@@ -420,6 +420,12 @@ int orl_batch_debug_persist_spec(orl_batch* b);
  * done): 0-6 the forms with the row phase in the loop, 7 / 8 the rows-deferred forms (round 6: the loop logs events,
  * k_rowstats replays the link statistics after the launch); -1 = no device-resident run through the persistent kernel yet. */
 int orl_batch_debug_persist_form(orl_batch* b);
+/* The whole choice the launcher of the persistent kernel makes for a batch of n_envs envs of this configuration, without a
+ * device (tests/test_persist_choice.py): out[0..8] = form number, the kernel's LDS template argument, waves per SIMD, the
+ * two-wavefront form, row-cache level, release times in LDS, bytes of the LDS window, bytes of LDS the launch asks for, workgroups
+ * per CU.  `tuned`: the choice made when a specialisation library is attached.  The ORL_PERSIST_* overrides are read from the
+ * environment as at a launch.  Returns 9, or 0 when the configuration does not run the persistent kernel. */
+int orl_debug_persist_choice(const orl_env_config* cfg, const orl_topology_desc* topo, int64_t n_envs, int tuned, int32_t* out);
 /* Which kernel orl_batch_step launches for this batch: 2 = k_agent (8 lanes per env, the persistent kernel's phases for one
  * step; QoSConstrainedRA: k_agent_qos, from 20 480 envs), 0 = k_step (one wavefront per env). */
 int orl_batch_debug_step_kernel(orl_batch* b);

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "orl_host.h"
+#include "orl_persist_form.h"
 
 using namespace orl;
 
@@ -325,16 +326,8 @@ extern "C" void orl_topology_destroy(orl_topology* t) try {
 ORL_ABI_CATCH_VOID
 
 // ---- launch dispatch over the row width ---------------------------------------------------------------
-// Anything but the persistent kernel is about to write slot maps: the row caches the persistent kernel left with the state
-// (DevParams::row_cache) no longer describe them.  The key of the next persistent launch differs from every stored stamp.
-static void slot_maps_change(orl_batch* b) {
-  if (++b->cache_epoch >= (1 << 22)) {  // (the key keeps 22 bits of it: start over with no stamp left standing)
-    if (b->P.row_cache_stamp) hipMemsetAsync(b->P.row_cache_stamp, 0, (size_t)((b->P.B + 7) / 8) * sizeof(int), b->stream);
-    b->cache_epoch = 1;
-  }
-}
 static void launch_reset(orl_batch* b, int full, const unsigned char* dmask) {
-  slot_maps_change(b);
+  slot_maps_change(b, b->stream);
 #define CALL(WW) orl_launch::reset<WW>(b, full, dmask)
   ORL_DISPATCH_W(b, CALL)
 #undef CALL
@@ -345,13 +338,13 @@ static void launch_policy(orl_batch* b, int pol) {
 #undef CALL
 }
 static void launch_step64(orl_batch* b, int auto_reset, int want_info, int fused_policy) {
-  slot_maps_change(b);
+  slot_maps_change(b, b->stream);
 #define CALL(WW) orl_launch::step64<WW>(b, auto_reset, want_info, fused_policy)
   ORL_DISPATCH_W(b, CALL)
 #undef CALL
 }
 static void launch_agent_step(orl_batch* b, int auto_reset, int pol = -1) {
-  slot_maps_change(b);
+  slot_maps_change(b, b->stream);
 #define CALL(WW) orl_launch::agent_step<WW>(b, auto_reset, pol)
   ORL_DISPATCH_W(b, CALL)
 #undef CALL
@@ -374,12 +367,10 @@ static void launch_persist(orl_batch* b, const DevParams& VP, hipStream_t st, in
   ORL_DISPATCH_W(b, CALL)
 #undef CALL
 }
+// wavefronts of the persistent kernel the GPU holds at once for this batch (LDS window and register budget).  (An attached
+// specialisation library counts here whatever ORL_PERSIST_SPEC says.)
 static int persist_resident(orl_batch* b) {
-  int r = 0;
-#define CALL(WW) r = orl_launch::persist_resident<WW>(b, b->n_cu)
-  ORL_DISPATCH_W(b, CALL)
-#undef CALL
-  return r;
+  return persist_choose(b->P, b->spec_launch != nullptr, persist_overrides_from_env()).wgs_per_cu * b->n_cu;
 }
 // the per-env arrays of envs [lo, lo + cnt) as a batch of their own (lo a multiple of 8: wavefronts own 8 consecutive envs)
 static DevParams env_view(const DevParams& P, i64 lo, i64 cnt, int part) {
@@ -408,7 +399,7 @@ static DevParams env_view(const DevParams& P, i64 lo, i64 cnt, int part) {
   return q;
 }
 static void launch_step2(orl_batch* b, int pol) {
-  slot_maps_change(b);
+  slot_maps_change(b, b->stream);
 #define CALL(WW) orl_launch::step2<WW>(b, pol)
   ORL_DISPATCH_W(b, CALL)
 #undef CALL
@@ -1915,23 +1906,16 @@ extern "C" int orl_batch_matrix_observation(orl_batch* b, uint8_t* out) try {
 ORL_ABI_CATCH_INT
 
 // ---- specialisation libraries: k_persist with one configuration's sizes as compile-time constants --------------------------
-static void persist_form_of(const DevParams& P, int wt, int* lds, int* waves) {
-  switch (wt) {
-    case 1: orl_launch::persist_form<1>(P, lds, waves); break;
-    case 2: orl_launch::persist_form<2>(P, lds, waves); break;
-    case 5: orl_launch::persist_form<5>(P, lds, waves); break;
-    default: orl_launch::persist_form<8>(P, lds, waves); break;
-  }
-}
+// the flags of the library a batch of these sizes attaches: the form is the tuned choice
 static int spec_flags(const DevParams& P, int wt, char* buf, int capacity) {
-  int lds = 0, waves = 0;
-  persist_form_of(P, wt, &lds, &waves);
+  const PersistChoice ch = persist_choose(P, true, persist_overrides_from_env());
+  const PersistForm& F = kPersistForms[ch.form];
   const int n = snprintf(buf, (size_t)capacity,
                          "-DORL_SPEC_ONLY -DORL_W=%d -DORL_SPEC_ENV=%d -DORL_SPEC_LDS=%d -DORL_SPEC_WAVES=%d -DORL_SPEC_RW=%d -DORL_SPEC_N=%d -DORL_SPEC_E=%d "
                          "-DORL_SPEC_K=%d -DORL_SPEC_H=%d -DORL_SPEC_M=%d -DORL_SPEC_S=%d -DORL_SPEC_C=%d -DORL_SPEC_J=%d -DORL_SPEC_BRMODE=%d "
                          "-DORL_SPEC_BRLO=%d -DORL_SPEC_NBR=%d -DORL_SPEC_RANDN=%d -DORL_SPEC_RANDBITS=%d -DORL_SPEC_EVCAP=%d "
                          "-DORL_SPEC_BMWORDS=%d -DORL_SPEC_CSWORDS=%d -DORL_SPEC_OBSDIM=%d -DORL_SPEC_NINFO=%d",
-                         wt, P.env_type, lds, waves & 15, waves >> 4, P.N, P.E, P.K, P.H, P.M, P.S, P.C, P.J, P.bit_rate_mode, P.br_lo, P.n_br, P.rand_n,
+                         wt, P.env_type, F.lds_arg, F.waves, ch.rw, P.N, P.E, P.K, P.H, P.M, P.S, P.C, P.J, P.bit_rate_mode, P.br_lo, P.n_br, P.rand_n,
                          P.rand_bits, P.ev_cap, P.bm_words, P.cs_words, P.obs_dim, P.n_info);
   return (n > 0 && n < capacity) ? n : 0;
 }
@@ -1942,19 +1926,35 @@ extern "C" int orl_batch_spec_flags(orl_batch* b, char* buf, int capacity) try {
   return spec_flags(b->P, b->wt, buf, capacity);
 }
 catch (...) { return 0; }
+// the sizes of a batch of n_envs envs of this configuration, without a device; false: not one the persistent kernel serves
+static bool persist_sizes_for(const orl_env_config* cfg, const orl_topology_desc* topo, int64_t n_envs, DevParams& P, int* wt) {
+  if (!cfg || !topo || n_envs < 1) return false;
+  if (cfg->struct_size != sizeof(orl_env_config) || cfg->env_type < 0 || cfg->env_type > ORL_ENV_QOS || !(cfg->lambda_arrival > 0) || !(cfg->lambda_holding > 0)) return false;
+  memset(&P, 0, sizeof P);
+  derive_sizes(cfg, topo->n_nodes, topo->n_links, topo->k_paths, topo->max_hops, topo->n_modulations, n_envs, P, wt);
+  return pipeline_applies(cfg, P);
+}
 extern "C" int orl_spec_flags_for(const orl_env_config* cfg, const orl_topology_desc* topo, char* buf, int capacity) {
   return orl_spec_flags_for_batch(cfg, topo, (int64_t)1 << 20, buf, capacity);
 }
 extern "C" int orl_spec_flags_for_batch(const orl_env_config* cfg, const orl_topology_desc* topo, int64_t n_envs, char* buf, int capacity) try {
-  if (!cfg || !topo || !buf || capacity < 1 || n_envs < 1) return 0;
+  if (!buf || capacity < 1) return 0;
   buf[0] = 0;
-  if (cfg->struct_size != sizeof(orl_env_config) || cfg->env_type < 0 || cfg->env_type > ORL_ENV_QOS || !(cfg->lambda_arrival > 0) || !(cfg->lambda_holding > 0)) return 0;
   DevParams P;
-  memset(&P, 0, sizeof P);
   int wt = 1;
-  derive_sizes(cfg, topo->n_nodes, topo->n_links, topo->k_paths, topo->max_hops, topo->n_modulations, n_envs, P, &wt);
-  if (!pipeline_applies(cfg, P)) return 0;
+  if (!persist_sizes_for(cfg, topo, n_envs, P, &wt)) return 0;
   return spec_flags(P, wt, buf, capacity);
+}
+catch (...) { return 0; }
+extern "C" int orl_debug_persist_choice(const orl_env_config* cfg, const orl_topology_desc* topo, int64_t n_envs, int tuned, int32_t* out) try {
+  DevParams P;
+  int wt = 1;
+  if (!out || !persist_sizes_for(cfg, topo, n_envs, P, &wt)) return 0;
+  const PersistChoice ch = persist_choose(P, tuned != 0, persist_overrides_from_env());
+  const PersistForm& F = kPersistForms[ch.form];
+  const int32_t v[9] = {ch.form, F.lds_arg, F.waves, ch.rw, ch.inner, ch.evl, (int32_t)ch.lds, (int32_t)ch.launch_lds, ch.wgs_per_cu};
+  memcpy(out, v, sizeof v);
+  return 9;
 }
 catch (...) { return 0; }
 extern "C" int orl_batch_load_spec(orl_batch* b, const char* so_path) try {
@@ -1969,12 +1969,12 @@ extern "C" int orl_batch_load_spec(orl_batch* b, const char* so_path) try {
   void* launch = dlsym(h, "orl_spec_launch");
   if (!bytes || !describe || !launch) { dlclose(h); return fail(ORL_E_INVALID, "%s is not a specialisation library", so_path); }
   if (bytes() != (int)sizeof(DevParams)) { dlclose(h); return fail(ORL_E_INVALID, "%s was built from other sources (parameter block %d B, here %zu B)", so_path, bytes(), sizeof(DevParams)); }
-  int d[22];
+  int d[23];
   describe(d);
   const DevParams& P = b->P;
-  const int want[22] = {P.env_type, b->wt, d[2], d[3], P.N, P.E, P.K, P.H, P.M, P.S, P.C, P.J, P.bit_rate_mode, P.br_lo, P.n_br, P.rand_n, P.rand_bits,
+  const int want[23] = {P.env_type, b->wt, d[2], d[3], d[4], P.N, P.E, P.K, P.H, P.M, P.S, P.C, P.J, P.bit_rate_mode, P.br_lo, P.n_br, P.rand_n, P.rand_bits,
                         P.ev_cap, P.bm_words, P.cs_words, P.obs_dim, P.n_info};
-  for (int i = 0; i < 22; i++)
+  for (int i = 0; i < 23; i++)
     if (d[i] != want[i]) { dlclose(h); return fail(ORL_E_INVALID, "%s was built for another configuration (field %d: %d, this batch %d)", so_path, i, d[i], want[i]); }
   if (b->spec_handle) {  // kernels of the library being replaced may still be queued
     HIPCHK(hipSetDevice(b->device));
@@ -1987,6 +1987,7 @@ extern "C" int orl_batch_load_spec(orl_batch* b, const char* so_path) try {
   b->spec_agent_launch = (decltype(b->spec_agent_launch))dlsym(h, "orl_spec_agent_launch");  // (k_agent with the same constants)
   b->spec_lds = d[2];
   b->spec_waves = d[3];
+  b->spec_rw = d[4];
   return ORL_OK;
 }
 ORL_ABI_CATCH_INT
@@ -2108,7 +2109,7 @@ extern "C" int orl_batch_set_state(orl_batch* b, const void* in) try {
   // generator state that has just been replaced: a snapshot is always taken between runs, where nothing is parked
   if (b->P.svc_cnt) HIPCHK(hipMemsetAsync(b->P.svc_cnt, 0, (size_t)((b->P.B + 7) / 8) * 64 * sizeof(int), b->stream));
   b->run_abandoned = false;  // (the step counters of an abandoned run are cleared by the next run: wg_dirty stays set)
-  slot_maps_change(b);
+  slot_maps_change(b, b->stream);
   if (b->P.obs_dim) launch_obs(b, 0);
   HIPCHK(hipStreamSynchronize(b->stream));
   return ORL_OK;

@@ -63,6 +63,30 @@ enum {
 // 8 lanes per env on the same word — was an 8-way bank conflict
 #define ORL_SCAL_LDS_WORDS 34
 #define ORL_FREE_SLOTS 16
+// the record words the deferred-statistics control phase keeps in the LDS window (orl_device_split.h, Wmem::mini): words used, words per env
+#define ORL_MINI_WORDS 6
+#define ORL_MINI_STRIDE 7
+// the release sink's entries (orl_device_split.h, "release sink"): their sizes lay out the LDS window (orl_persist_form.h)
+namespace sp {
+struct SinkEntry {
+  u64 mk0;  // masks 0..3: (s0 | n << 9), 16 bits each, in release order
+  u64 mk1;  // masks 4..7
+  u64 crn;  // the core of each mask, 5 bits each (40 bits) | number of masks << 40 | mask 0 is a provision << 44
+};
+// compact form (single-core families in the persistent kernel's LDS window).  A release frees the SAME slots on every link of
+// its path, so the masks need not be copied into per-link entries: per env one table of masks — entry 0 the step's provision,
+// entry k (1..ORL_REL_MAX) its k-th release in heap-pop order, 16 bits each (first slot: 9 | slots: 6 — the split pipeline
+// serves services of at most 63 slots, orl_api.hip) — and per (env, link) ONE 32-bit word of which of them touch the link.
+// Appending is one LDS atomic OR (its return value says whether the entry was empty, i.e. whether a new work item opens);
+// there is no per-link capacity any more (8 masks per 16-byte entry before: a tally pass guarded it), only the 31 releases
+// per env-step of the table; and the table is 4 bytes per link and env instead of 16 (cfg2: 1 216 B with the masks instead
+// of 2 816 B + 192 B of tallies), which is what lets the LDS window of the 4-wave form fit 16 times into a CU.
+struct SinkEntryC {
+  u32 bits;  // bit 0: the provision; bit k: the k-th release of this step
+};
+#define ORL_REL_MAX 31
+#define ORL_MTAB 32  // masks per env in the table
+}  // namespace sp
 #define ORL_IMASKS 8  // masks one work item can carry = releases of one step that may meet on one link (orl_device_split.h)
 #define ORL_FLAG_EV_OVERFLOW 1
 #define ORL_FLAG_BAD_ACTION 2

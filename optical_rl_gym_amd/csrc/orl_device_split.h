@@ -136,24 +136,7 @@ __device__ __forceinline__ size_t wave_reserve(const DevParams& P, int cnt, u32*
 // [s0, s0+n) masks in release order, each with its core.  While collecting, the items live in an LDS table indexed
 // by the link (24 bytes per link and env): appending a mask is one LDS read-modify-write by the lane that owns the
 // hop, with no search and no per-lane registers.
-struct SinkEntry {
-  u64 mk0;  // masks 0..3: (s0 | n << 9), 16 bits each, in release order
-  u64 mk1;  // masks 4..7
-  u64 crn;  // the core of each mask, 5 bits each (40 bits) | number of masks << 40 | mask 0 is a provision << 44
-};
-// compact form (single-core families in the persistent kernel's LDS window).  A release frees the SAME slots on every link of
-// its path, so the masks need not be copied into per-link entries: per env one table of masks — entry 0 the step's provision,
-// entry k (1..ORL_REL_MAX) its k-th release in heap-pop order, 16 bits each (first slot: 9 | slots: 6 — the split pipeline
-// serves services of at most 63 slots, orl_api.hip) — and per (env, link) ONE 32-bit word of which of them touch the link.
-// Appending is one LDS atomic OR (its return value says whether the entry was empty, i.e. whether a new work item opens);
-// there is no per-link capacity any more (8 masks per 16-byte entry before: a tally pass guarded it), only the 31 releases
-// per env-step of the table; and the table is 4 bytes per link and env instead of 16 (cfg2: 1 216 B with the masks instead
-// of 2 816 B + 192 B of tallies), which is what lets the LDS window of the 4-wave form fit 16 times into a CU.
-struct SinkEntryC {
-  u32 bits;  // bit 0: the provision; bit k: the k-th release of this step
-};
-#define ORL_REL_MAX 31
-#define ORL_MTAB 32  // masks per env in the table
+// (SinkEntry, SinkEntryC, ORL_REL_MAX, ORL_MTAB: orl_device.h, beside the other sizes the LDS window is laid out from)
 struct Mask2 { u64 lo, hi; int w0; };
 __device__ __forceinline__ Mask2 mask2(int s0, int n) {
   Mask2 m;
@@ -633,8 +616,7 @@ __device__ __forceinline__ u64 slog_w2(int d_nh, int d_br) { return (u64)(u32)d_
 // that went through L2 in the step's dependent chain become LDS accesses or disappear (the pending service's source /
 // destination / bit rate are the descriptor's: written to the record when the launch ends, svc_words).  The free-slot stack,
 // the flags and the statistics' words stay where the record is.  448 bytes: with them cfg2's window keeps its eight LDS pieces.
-#define ORL_MINI_WORDS 6
-#define ORL_MINI_STRIDE 7
+// (ORL_MINI_WORDS, ORL_MINI_STRIDE: orl_device.h)
 __device__ __forceinline__ int mini_slot(int k) {  // record slot of mini word k
   return k == 0 ? SC_NOW : k == 1 ? SC_HT : k == 2 ? SC_NEXTREL : k == 3 ? SC_TSOON : k == 4 ? SC_EV : SC_HINT;
 }

@@ -45,17 +45,16 @@ struct orl_batch {
   TkRec* tk = nullptr;
   int parity = 0;        // two-kernel form (ORL_ALT_IMPLS): which deferred-env buffer the next step writes
   int persist = 0;       // device-resident runs go through the persistent kernel (k_persist)
-  int lds_state = 0;     // ... with the slot maps and link statistics of a wavefront's envs resident in LDS
   int agent_step = 0;    // host- / agent-driven steps with auto reset go through k_agent (the phases of k_persist) instead of k_step
   int two_kernel = 0;    // ORL_ALT_IMPLS builds, ORL_STEP_IMPL=2 ORL_PERSIST=0: the phases of k_persist as separate launches
   int64_t persist_launches = 0;
   int persist_spec = 0;            // 1: the last launch of k_persist used the instantiation built for this configuration
-  int persist_form_last = -1;      // the form (index into kPersistForms) of the last launch of k_persist
+  int persist_form_last = -1;      // the form (index into kPersistForms, orl_persist_form.h) of the last launch of k_persist
   // a specialisation library attached by orl_batch_load_spec: k_persist with this batch's sizes as compile-time constants
   void* spec_handle = nullptr;
   void (*spec_launch)(const orl::DevParams*, unsigned, size_t, hipStream_t, int, int, int*, unsigned int*, unsigned int*) = nullptr;
   void (*spec_agent_launch)(const orl::DevParams*, unsigned, size_t, hipStream_t, int, int) = nullptr;  // k_agent of the same library
-  int spec_lds = -1, spec_waves = -1;
+  int spec_lds = -1, spec_waves = -1, spec_rw = -1;  // the form it was built for: k_persist's LDS argument, waves per SIMD, two-wavefront form
   int* d_wg_step = nullptr;        // [ceil(B/8)] steps each workgroup of the persistent kernel has completed since run_base was 0
   int64_t run_base = 0;            // ... all of them, between runs (no per-run clearing of d_wg_step)
   bool wg_dirty = true;            // a run did not complete (or none has run yet): clear d_wg_step and run_base first
@@ -92,6 +91,16 @@ struct orl_batch {
                                     // orl_batch_matrix_paths_observation; what ORL_BUF_MATRIX_PATHS_OBS hands out
 };
 
+// Anything but the row-cache-keeping forms of the persistent kernel is about to write slot maps: the row caches the persistent
+// kernel left with the state (DevParams::row_cache) no longer describe them.  The key of the next persistent launch differs from
+// every stored stamp.
+static inline void slot_maps_change(orl_batch* b, hipStream_t st) {
+  if (++b->cache_epoch >= (1 << 22)) {  // (the key keeps 22 bits of it: start over with no stamp left standing)
+    if (b->P.row_cache_stamp) hipMemsetAsync(b->P.row_cache_stamp, 0, (size_t)((b->P.B + 7) / 8) * sizeof(int), st);
+    b->cache_epoch = 1;
+  }
+}
+
 #define ORL_TK(B_, NAME)                                                                 \
   do {                                                                                   \
     if ((B_)->tk) {                                                                      \
@@ -113,12 +122,9 @@ template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, i
 // k_persist over the env range of view VP up to step `target` of this run, then k_rel_tail, on stream st
 template <int W> void persist(orl_batch* b, const orl::DevParams& VP, hipStream_t st, int pol, int target, int* wg_step, unsigned int* unfinished,
                               unsigned int* clear_next, int finish);  // finish: this launch ends the run (DevParams::persist_finish)
-template <int W> int persist_resident(orl_batch* b, int n_cu);              // wavefronts of k_persist the GPU holds at once
-template <int W> int persist_uses_lds(orl_batch* b);                       // 1: the persistent kernel keeps slot maps / link statistics in LDS
 template <int W> int prof_read(unsigned long long* out48, int reset);      // -DORL_TIMING builds: per-phase cycle sums
-template <int W> void step2(orl_batch* b, int pol);
-template <int W> void agent_step(orl_batch* b, int auto_reset, int pol);
-template <int W> void persist_form(const orl::DevParams& VP, int* lds_state, int* waves);  // the form persist() takes for this configuration                            // k_agent: one step, actions in P.actions, info / obs written                        // ORL_ALT_IMPLS: k_step_a2 ; k_rows2 ; k_rel_tail
+template <int W> void step2(orl_batch* b, int pol);                        // ORL_ALT_IMPLS: k_step_a2 ; k_rows2 ; k_rel_tail
+template <int W> void agent_step(orl_batch* b, int auto_reset, int pol);   // k_agent: one step, actions in P.actions, info / obs written
 }  // namespace orl_launch
 
 #define ORL_DISPATCH_W(B_, CALL)      \

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "orl_host.h"
+#include "orl_persist_form.h"
 #include "orl_device_g8.h"
 #include "orl_device_split.h"
 
@@ -240,46 +241,7 @@ __global__ void __launch_bounds__(ORL_ROWS2_THREADS) k_rows2(DevParams P, int pa
 // A wavefront in which an env's releases did not fit the item form (one env-step in 10^7) leaves the loop after that step's
 // row phase and counts as unfinished; at the start of its next launch it releases them in place and resumes from its own
 // step count.
-struct PersistLds {  // byte offsets into the workgroup's dynamic LDS window (all multiples of 16)
-  int tab, mtab, tally, tw, list, clk, misc, bm, ls, cs, csw, sc, ic, mini, total;  // (ic: inner-run cache, then the occ / fb cache)
-};
-// state: 0 = only the per-step tables, 1 = + slot maps, per-core sums and env records, 2 = + link statistics, 3 = slot maps and
-// per-core sums but the env records stay in global memory (the window of the 4-wave forms: cfg2 8 832 B, 16 per CU);
-// compact: the bit-word sink of the single-core families (4 bytes per link and env + a mask table per env);
-// inner: 0 = no row caches, 1 = the per-word longest-run cache of every row, 2 = + every row's contribution to the compactness
-// sums, (occ << 16) | free blocks (4 bytes per row each)
-// mini: the eight record words the deferred-statistics control phase works on, for the forms whose records stay in global memory
-// rd: the rows-deferred form (round 6) — no row phase in the loop, hence no sink table, mask table, item list, clock pairs, row
-// caches or per-core sums: the window is the slot maps, the record words the control phase works on, and 16 bytes
-__host__ __device__ inline PersistLds persist_lds_layout(int E, int H, int bm_words, int C, int state, bool compact, int inner, bool mini = false,
-                                                         bool rd = false) {
-  PersistLds L;
-  int o = 0;
-  L.tab = o; if (!rd) o += (8 * E * (int)(compact ? sizeof(sp::SinkEntryC) : sizeof(sp::SinkEntry)) + 15) & ~15;
-  L.mtab = o; if (compact && !rd) o += 8 * ORL_MTAB * 2;
-  L.tw = compact ? 0 : (E + 3) >> 2;
-  L.tally = o; o += 8 * L.tw * 4;
-  // one entry per touched link and env, a second one where the step's provision meets a release (at most its hops)
-  L.list = o; if (!rd) o += ((8 * (E + (H < E ? H : E)) * 2) + 15) & ~15;
-  // {provision clock, step clock} of the 8 envs for the row phase (the deferred-statistics control phase never writes SC_NOWA,
-  // which the replay owns, so the forms with the records in LDS have the pair too; the full-LDS test form reads the records)
-  L.clk = o; if (state != 2 && !rd) o += 8 * 2 * 8;
-  L.misc = o; o += 16;
-  L.bm = o; if (state >= 1) o += 8 * bm_words * 8;
-  L.csw = (4 * C + 3) & ~3;  // sums + their release part, ints per env
-  L.cs = o; if ((state >= 1 || mini) && !rd) o += 8 * L.csw * 4;  // (the global-state form of the deferred-statistics kernel keeps them in LDS too)
-  L.sc = o; if (state == 1 || state == 2) o += 8 * ORL_SCAL_LDS_WORDS * 8;
-  L.ic = o; if (state >= 1 && inner && !rd) o += inner * ((8 * E * 4 + 15) & ~15);
-  L.ls = o; if (state == 2) o += 8 * E * 32;
-  L.mini = o; if (mini && (state == 0 || state == 3)) o += (8 * ORL_MINI_STRIDE * 8 + 15) & ~15;
-  L.total = o;
-  return L;
-}
-template <int ENV, int LDS> struct PersistCompact { static constexpr bool value = ENV != ENV_RMCSA; };
-static inline bool persist_compact(int env_type, int state) { return env_type != ENV_RMCSA; }
-// (rows of one or two words: searching both costs less than the bookkeeping — cfg3 measured 1.20e9 without, 1.01e9 with)
-template <int ENV, int W, int LDS> struct PersistInner { static constexpr bool value = LDS >= 1 && W >= 3 && W <= 5 && (ENV == ENV_RMSA || ENV == ENV_DEEPRMSA); };
-static inline bool persist_inner(int env_type, int W, int state) { return state >= 1 && W >= 3 && W <= 5 && (env_type == ENV_RMSA || env_type == ENV_DEEPRMSA); }
+// (the window's layout, the table of forms and the choice among them: orl_persist_form.h)
 // The LDS window of a wavefront's 8 envs, filled from their (contiguous) global arrays.  Everything is REQUESTED before
 // anything is waited for (blocks of 8 x 64 pieces of 16 bytes; the records and the sums with the first block).  A copy loop
 // `l[i] = g[i]` compiles to load - wait - store per iteration: 13 dependent memory round trips at the start of every
@@ -963,9 +925,7 @@ k_rowstats(DevParams P, int G) {
 // in LDS a step later.  A group that is out of phase with the others (its window of generator words once held fewer services than
 // asked for) and runs dry while their batch is on order gets one on the spot, into the second staging area.  Only the row
 // wavefront touches the generator's state.
-#define ORL_RW_SYNC_WORDS 12
-#define ORL_RW_STAGE_BYTES (2 * 64 * 24)  // two batches: the one asked for a step ahead, and one asked for on the spot
-#define ORL_RW_EXTRA_BYTES (ORL_RW_SYNC_WORDS * 4 + ORL_RW_STAGE_BYTES)
+// (ORL_RW_SYNC_WORDS, ORL_RW_STAGE_BYTES, ORL_RW_EXTRA_BYTES: orl_persist_form.h)
 __device__ __forceinline__ u32 rw_load(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 // (Everything the pair shares is in LDS.  Round 6: the hand-over is a workgroup-scope release / acquire on the LOCAL address space
 // only — sp::rw_release_lds / rw_acquire_lds: the release drains the wavefront's LDS operations (s_waitcnt lgkmcnt(0)) before the
@@ -1093,9 +1053,9 @@ __device__ __forceinline__ void wave_prio_rotate(int slot, int shift) {
 }
 template <int ENV, int W, int LDS_, bool PF, bool RW = false>
 __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int target, int* wg_step, u32* n_unfinished) {
-  constexpr bool RD = (LDS_ == 4 || LDS_ == 5);
-  constexpr int LDS = (LDS_ == 4) ? 3 : ((LDS_ == 5) ? 1 : LDS_);
-  constexpr bool CP = PersistCompact<ENV, LDS>::value;
+  constexpr bool RD = persist_rd_of(LDS_);
+  constexpr int LDS = persist_state_of(LDS_);
+  constexpr bool CP = PersistCompact<ENV>::value;
   static_assert(!RD || (CP && !RW), "rows deferred: single-core families, one wavefront per 8 envs");
   static_assert(!RW || (CP && (LDS == 1 || LDS == 3)), "two-wavefront form: single-core families, slot maps in LDS");
 // (one wavefront per workgroup: a barrier is an ordering point of the wavefront; the control wavefront of a pair must not wait at
@@ -1699,12 +1659,12 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
 // from orl_batch_spec_flags) into a small shared library of its own — one k_persist instantiation and the launch entry
 // orl_spec_launch — which orl_batch_load_spec attaches to the batch after comparing every field.  The main library holds the
 // generic kernels only.
-struct PersistSpec { int env, W, lds, waves, N, E, K, H, M, S, C, J, bit_rate_mode, br_lo, n_br, rand_n, rand_bits, ev_cap, bm_words, cs_words, obs_dim, n_info; };
+struct PersistSpec { int env, W, lds, waves, rw, N, E, K, H, M, S, C, J, bit_rate_mode, br_lo, n_br, rand_n, rand_bits, ev_cap, bm_words, cs_words, obs_dim, n_info; };
 #ifdef ORL_SPEC_ONLY
 #ifndef ORL_SPEC_RW
 #define ORL_SPEC_RW 0  // 1: the two-wavefront form (small batches)
 #endif
-static constexpr PersistSpec kPersistSpec = {ORL_SPEC_ENV, ORL_W, ORL_SPEC_LDS, ORL_SPEC_WAVES + 16 * ORL_SPEC_RW, ORL_SPEC_N, ORL_SPEC_E, ORL_SPEC_K, ORL_SPEC_H,
+static constexpr PersistSpec kPersistSpec = {ORL_SPEC_ENV, ORL_W, ORL_SPEC_LDS, ORL_SPEC_WAVES, ORL_SPEC_RW, ORL_SPEC_N, ORL_SPEC_E, ORL_SPEC_K, ORL_SPEC_H,
                                              ORL_SPEC_M, ORL_SPEC_S, ORL_SPEC_C, ORL_SPEC_J, ORL_SPEC_BRMODE, ORL_SPEC_BRLO, ORL_SPEC_NBR,
                                              ORL_SPEC_RANDN, ORL_SPEC_RANDBITS, ORL_SPEC_EVCAP, ORL_SPEC_BMWORDS, ORL_SPEC_CSWORDS,
                                              ORL_SPEC_OBSDIM, ORL_SPEC_NINFO};
@@ -1733,10 +1693,7 @@ k_persist(DevParams P, int pol, int target, int* wg_step, u32* n_unfinished, u32
   // the counters the NEXT launch of this half of the batch uses (it starts after this one has ended)
   if (blockIdx.x == 0 && threadIdx.x == 0) { clear_next[0] = 0u; clear_next[1] = 0u; }
   persist_spec_apply<SPEC>(P);
-  #ifndef ORL_PF_WAVES
-#define ORL_PF_WAVES 3  // forms of at most this many waves per SIMD keep the soon list in registers and request early
-#endif
-  persist_body<ENV, W, LDS, (WAVES <= ORL_PF_WAVES), RW>(P, pol, target, wg_step, n_unfinished);
+  persist_body<ENV, W, LDS, persist_soon_in_registers(WAVES), RW>(P, pol, target, wg_step, n_unfinished);
 }
 
 
@@ -2167,24 +2124,9 @@ extern "C" int orl_debug_rs_prof(unsigned long long* out16, int reset) {
 }
 #endif
 #endif
-#ifdef ORL_SPEC_ONLY
-// ---- the whole of a specialisation library: one instantiation and its launch entry ----------------------------------------
-extern "C" int orl_spec_struct_bytes(void) { return (int)sizeof(DevParams); }
-extern "C" void orl_spec_describe(int* out /*[22]*/) {
-  const PersistSpec& s = kPersistSpec;
-  const int v[22] = {s.env, s.W, s.lds, s.waves, s.N, s.E, s.K, s.H, s.M, s.S, s.C, s.J, s.bit_rate_mode, s.br_lo, s.n_br, s.rand_n, s.rand_bits,
-                     s.ev_cap, s.bm_words, s.cs_words, s.obs_dim, s.n_info};
-  for (int i = 0; i < 22; i++) out[i] = v[i];
-}
-extern "C" void orl_spec_launch(const DevParams* VP, unsigned grid, size_t lds, hipStream_t st, int pol, int target, int* wg_step,
-                                unsigned int* unfinished, unsigned int* clear_next) {
-  if (lds > 48 * 1024)
-    hipFuncSetAttribute((const void*)k_persist<ORL_SPEC_ENV, ORL_W, ORL_SPEC_LDS, ORL_SPEC_WAVES, 1, ORL_SPEC_RW != 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((k_persist<ORL_SPEC_ENV, ORL_W, ORL_SPEC_LDS, ORL_SPEC_WAVES, 1, ORL_SPEC_RW != 0>), dim3(grid), dim3(ORL_SPEC_RW ? 128 : 64), lds, st, *VP, pol,
-                     target, wg_step, unfinished, clear_next);
-}
-// (diagnostic builds, -DORL_TIMING: the per-phase cycle sums of this library's kernel — tools/pair_prof.py)
-extern "C" int orl_spec_prof(unsigned long long* out48, int reset) {
+// diagnostic builds (-DORL_TIMING): per-phase cycle sums of this unit's persistent kernels, summed over the wavefronts (reset 1:
+// cleared afterwards; 2: the wavefront timeline, 3: the sums per wavefront, unsummed); zeros otherwise
+static int persist_prof_read(unsigned long long* out48, int reset) {
 #ifdef ORL_TIMING
   if (reset == 2) return hipMemcpyFromSymbol(out48, HIP_SYMBOL(g_wts), 16384 * 8 * 8) == hipSuccess ? 0 : -1;
   if (reset == 3) return hipMemcpyFromSymbol(out48, HIP_SYMBOL(sp::g_prof), (size_t)ORL_PROF_WAVES * ORL_PROF_SLOTS * 8) == hipSuccess ? 0 : -1;
@@ -2204,6 +2146,24 @@ extern "C" int orl_spec_prof(unsigned long long* out48, int reset) {
 #endif
   return 0;
 }
+#ifdef ORL_SPEC_ONLY
+// ---- the whole of a specialisation library: one instantiation and its launch entry ----------------------------------------
+extern "C" int orl_spec_struct_bytes(void) { return (int)sizeof(DevParams); }
+extern "C" void orl_spec_describe(int* out /*[23]*/) {
+  const PersistSpec& s = kPersistSpec;
+  const int v[23] = {s.env, s.W, s.lds, s.waves, s.rw, s.N, s.E, s.K, s.H, s.M, s.S, s.C, s.J, s.bit_rate_mode, s.br_lo, s.n_br, s.rand_n, s.rand_bits,
+                     s.ev_cap, s.bm_words, s.cs_words, s.obs_dim, s.n_info};
+  for (int i = 0; i < 23; i++) out[i] = v[i];
+}
+extern "C" void orl_spec_launch(const DevParams* VP, unsigned grid, size_t lds, hipStream_t st, int pol, int target, int* wg_step,
+                                unsigned int* unfinished, unsigned int* clear_next) {
+  if (lds > 48 * 1024)
+    hipFuncSetAttribute((const void*)k_persist<ORL_SPEC_ENV, ORL_W, ORL_SPEC_LDS, ORL_SPEC_WAVES, 1, ORL_SPEC_RW != 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((k_persist<ORL_SPEC_ENV, ORL_W, ORL_SPEC_LDS, ORL_SPEC_WAVES, 1, ORL_SPEC_RW != 0>), dim3(grid), dim3(ORL_SPEC_RW ? 128 : 64), lds, st, *VP, pol,
+                     target, wg_step, unfinished, clear_next);
+}
+// (diagnostic builds, -DORL_TIMING: the per-phase cycle sums of this library's kernel — tools/pair_prof.py)
+extern "C" int orl_spec_prof(unsigned long long* out48, int reset) { return persist_prof_read(out48, reset); }
 extern "C" void orl_spec_agent_launch(const DevParams* VP, unsigned grid, size_t lds, hipStream_t st, int auto_reset, int pol) {
   if (pol >= 0) hipLaunchKernelGGL((k_agent<ORL_SPEC_ENV, ORL_W, 1, true>), dim3(grid), dim3(64), lds, st, *VP, auto_reset, pol);
   else hipLaunchKernelGGL((k_agent<ORL_SPEC_ENV, ORL_W, 1, false>), dim3(grid), dim3(64), lds, st, *VP, auto_reset, -1);
@@ -2286,221 +2246,57 @@ template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, i
   return 0;
 }
 
-// Forms of the persistent kernel: (what lives in LDS, waves per SIMD the registers are budgeted for).  The LDS window decides
-// how many wavefronts a CU holds.  The hardware allocates LDS in pieces of 1 280 bytes (tools/probe/lds_resident.hip,
-// measured on MI355X: 12 workgroups share a CU's 160 KiB up to 12 800 B each, 11 up to 14 080, 16 up to 10 240 —
-// hipOccupancyMaxActiveBlocksPerMultiprocessor says 12 up to 13 648).
-struct PersistForm { int lds, waves; };
-// (round 6: 7 and 8 are the rows-deferred forms — state 4 / 5 = the window of state 3 / 1 without the row phase's tables)
-static const PersistForm kPersistForms[] = {{0, 4}, {0, 3}, {2, 2}, {2, 3}, {1, 3}, {1, 4}, {3, 4}, {4, 4}, {5, 4}};
-constexpr int kNumPersistForms = 9;
-static inline bool persist_rd_state(int state) { return state == 4 || state == 5; }
-static int lds_wgs_per_cu(size_t lds) {
-  if (lds == 0) return 1 << 20;
-  const size_t alloc = (lds + 1279) / 1280 * 1280;
-  return (int)((size_t)(160 * 1024) / alloc);
-}
-struct PersistChoice { int form; size_t lds; int inner; int rw; int evl; };
-static size_t persist_window(const DevParams& VP, int state, int inner) {
-  const bool rd = persist_rd_state(state);
-  const int base = state == 4 ? 3 : (state == 5 ? 1 : state);
-  return (size_t)persist_lds_layout(VP.E, VP.H, VP.bm_words, VP.C, base, persist_compact(VP.env_type, base), rd ? 0 : inner,
-                                    orl_persist_deferred(VP.env_type), rd).total;
-}
-// the rows-deferred forms: single-core families with the statistics deferred, a bit per link in a 64-bit event word, services of
-// at most 63 slots in a 9-bit first slot (the compact sink's own limits), and an event log to write to
-static bool persist_rd_possible(const DevParams& VP) {
-  return orl_persist_deferred(VP.env_type) && VP.env_type != ENV_RMCSA && VP.E <= 64 && VP.S <= 512;
-}
-// `tuned`: the choice for a specialisation library (built without machine-level LICM and with the soon list in registers in the
-// 4-wave forms, _build.py SPEC_TUNING) — for the flags such a library is built with, and at launch when one is attached
-static PersistChoice persist_choose(const DevParams& VP, bool tuned = false) {
-  // Measured on MI355X, env-steps/s: cfg2 65 536 envs: form 0 (global state, 4 waves) 8.3e8, form 4 (LDS
-  // state, 3 waves) 1.02e9 at 11 wavefronts per CU with the inner-run cache, 1.05e9 at 12 without it — 69 MB of HBM traffic
-  // and 0.85 M L2<->fabric requests per batched step against 206 MB / 2.63 M; cfg1 65 536: form 4 1.13e9, form 5 (LDS state,
-  // 4 waves) 1.18e9; cfg3: 1.25e9 / 1.27e9.  A wavefront more per CU is worth 3-5 %: the 4-wave form is taken if its
-  // window keeps 16 on a CU, the 3-wave form down to 10, and the inner-run cache (+2.5 %) only where it costs no wavefront.
-  const bool can_inner = persist_inner(VP.env_type, ORL_W, 1);
-  // the row caches (level 1: inner free runs, +2.5 %; level 2: + each row's occ / free-block contribution, +2 %) are taken at the
-  // highest level that costs no wavefront per CU
-  auto level = [&](int state, int cap) {
-    if (!can_inner) return 0;
-    const int r_none = lds_wgs_per_cu(persist_window(VP, state, 0));
-    for (int lv = 2; lv >= 1; lv--) {
-      const int r = lds_wgs_per_cu(persist_window(VP, state, lv));
-      if ((r < cap ? r : cap) == (r_none < cap ? r_none : cap)) return lv;
-    }
-    return 0;
-  };
-  const size_t l0 = persist_window(VP, 1, 0), g0 = persist_window(VP, 3, 0);  // (g: records in global memory)
-  const int r0 = lds_wgs_per_cu(l0);
-  PersistChoice c;
-  // (round 3, cfg2 with the 4-byte sink entries: form 4 with the cache 1.23e9; form 6 — 4 waves per SIMD, 16 per CU, but the
-  // records in global memory, the soon list in memory and 9 spilled VGPRs — 1.14e9: what a wavefront keeps next to itself is
-  // worth more than a fourth wavefront per SIMD.  Form 6 is taken only where the 3-wave window does not fit at all.)
-  if (r0 >= 16) { c.form = 5; c.inner = level(1, 16); }
-  // (round 4: a tuned instantiation of form 6 needs 128 VGPRs with the soon list in registers and no spills, and 16 wavefronts
-  // per CU are 4 096 resident = exactly two generations of a 65 536-env batch: cfg2 20-step launches 1.135e9 -> 1.190e9, 300-step
-  // runs 1.467e9 -> 1.474e9 against form 4)
-  // ... for batches of more wavefronts than form 4 keeps resident (12 per CU x 256 CUs); below that no generation is cut short, and
-  // the records in LDS are a dependent round trip per step less: 4 096 envs +1.7 %, 8 192 +2.1 %, 16 384 +4.1 % for form 4
-  else if (tuned && VP.env_type != ENV_RMCSA && r0 >= 10 && lds_wgs_per_cu(g0) >= 16 && (VP.B + 7) / 8 > 12 * 256) { c.form = 6; c.inner = level(3, 16); }
-  else if (r0 >= 10) { c.form = 4; c.inner = level(1, 12); }
-  else if (lds_wgs_per_cu(g0) >= 16) { c.form = 6; c.inner = level(3, 16); }
-  // (global state: the 4-wave form except for RMCSA — round 3, with the 4-byte sink entries: cfg5 Germany50 32 768 envs 5.6e8 at 4
-  // waves per SIMD, 5.2e8 at 3; cfg4 RMCSA 5.0e8 / 5.3e8)
-  else { c.form = (VP.env_type == ENV_RMCSA) ? 1 : 0; c.inner = 0; }
-  // Small batches (round 5): at most 1 536 workgroups — 6 pairs per CU, all resident at 3 waves per SIMD — need the window to fit
-  // at most six times — form 4
-  // (everything in LDS, 3 waves per SIMD: soon list in registers) for every single-core configuration whose window fits a
-  // workgroup's 64 KiB, in its two-wavefront form (below).  4 096 envs, form 4 as a pair against the form chosen above alone:
-  // cfg2 +16 %, cfg3 +7 %, cfg1 +2 %, cfg5 (Germany50, global state above) +19 %.
-  const i64 n_wg = (VP.B + 7) / 8;
-  bool small_pair = false;
-  if (tuned && VP.env_type != ENV_RMCSA && n_wg <= 1536) {
-    const size_t w = persist_window(VP, 1, can_inner ? 2 : 0) + ORL_RW_EXTRA_BYTES;
-    if (w <= 64 * 1024 && lds_wgs_per_cu(w) >= (int)((n_wg + 255) / 256)) { c.form = 4; small_pair = true; }
-  }
-  if (const char* e = getenv("ORL_PERSIST_VARIANT")) {  // A/B measurements and cross-checks
-    const int f = atoi(e);
-    bool built = f >= 0 && f < kNumPersistForms;
-#ifndef ORL_ALT_IMPLS
-    built = built && f != 2 && f != 3;
-#endif
-    if (f >= 7) built = built && persist_rd_possible(VP);
-    if (built && persist_window(VP, kPersistForms[f].lds, 0) <= 64 * 1024 && f != c.form) {
-      c.form = f;
-      const int st = kPersistForms[f].lds;
-      c.inner = (st >= 1 && st <= 3 && persist_inner(VP.env_type, ORL_W, st)) ? level(st, 4 * kPersistForms[f].waves) : 0;
-    }
-  }
-  // RMCSA (24-byte sink entries, a core per mask, the general row loop) does not fit the 128-VGPR budget of the 4-wave forms — 25-32
-  // spilled VGPRs, measured slower than its 3-wave forms wherever both fit — and is not built in them: routed to the 3-wave form
-  // with the same state (global: 1; maps + records in LDS: 4, where that window fits a workgroup; else global)
-  if (VP.env_type == ENV_RMCSA && kPersistForms[c.form].waves == 4) {
-    const bool lds_ok = kPersistForms[c.form].lds != 0 && persist_window(VP, 1, 0) <= 64 * 1024 && lds_wgs_per_cu(persist_window(VP, 1, 0)) >= 4;
-    c.form = lds_ok ? 4 : 1;
-    c.inner = 0;
-  }
-  if (const char* e = getenv("ORL_PERSIST_INNER")) {  // A/B and cross-checks: 0 = no row caches, 1 = inner runs, 2 = + occ / free blocks
-    const int v = atoi(e);
-    c.inner = (v >= 0 && v <= 2 && !persist_rd_state(kPersistForms[c.form].lds) && persist_inner(VP.env_type, ORL_W, kPersistForms[c.form].lds)) ? v : 0;
-  }
-  // The two-wavefront form (k_persist<..., RW>, specialisation libraries only): batches whose pairs are all resident at once
-  // (measured: +20 % at 10 240 and 12 288 envs of cfg2, -20 % at 14 336, where a second generation starts).  LDS is no constraint
-  // there: both row caches, and ORL_RW_EXTRA_BYTES for the pair's counters and the staged batch of services.  ORL_PERSIST_RW=0/1: A/B measurements and cross-checks at
-  // any batch size.
-  c.rw = 0;
-  if (tuned && VP.env_type != ENV_RMCSA && kPersistForms[c.form].lds == 1) {
-    c.rw = small_pair ? 1 : 0;
-    if (const char* e = getenv("ORL_PERSIST_RW")) c.rw = atoi(e) != 0 ? 1 : 0;
-  }
-  if (c.rw && !getenv("ORL_PERSIST_INNER")) c.inner = can_inner ? 2 : 0;
-  c.lds = persist_window(VP, kPersistForms[c.form].lds, c.inner) + (c.rw ? ORL_RW_EXTRA_BYTES : 0);
-  // ... and, where it still fits a workgroup's 64 KiB and the batch's workgroups a CU, the 8 envs' pending release times (cfg2:
-  // 36 KiB: two workgroups per CU, batches of at most 4 096 envs)
-  c.evl = 0;
-  if (c.rw) {
-    const size_t w = c.lds + (size_t)8 * VP.ev_cap * 8;
-    if (w <= 64 * 1024 && lds_wgs_per_cu(w) >= (int)(((VP.B + 7) / 8 + 255) / 256)) c.evl = 1;
-    if (const char* e = getenv("ORL_PERSIST_EVL")) c.evl = (atoi(e) != 0 && w <= 64 * 1024) ? 1 : 0;
-    if (c.evl) c.lds = w;
-  }
-  return c;
-}
-static int persist_variant(const DevParams& VP, size_t* lds_bytes, bool tuned = false) {
-  const PersistChoice c = persist_choose(VP, tuned);
-  *lds_bytes = c.lds;
-  return c.form;
-}
-// the form the launcher takes for this configuration: what is in the LDS window, waves per SIMD (the key of a specialisation)
-template <int W> void persist_form(const DevParams& VP, int* lds_state, int* waves) {
-  const PersistChoice c = persist_choose(VP, true);
-  *lds_state = kPersistForms[c.form].lds;
-  *waves = kPersistForms[c.form].waves + 16 * c.rw;  // (bit 4: the two-wavefront form)
-}
-template <int W> int persist_uses_lds(orl_batch* b) {
-  size_t lds;
-  return kPersistForms[persist_variant(b->P, &lds, b->spec_launch != nullptr)].lds;
-}
-// Workgroups per CU the form allows (LDS window, register budget).  ORL_PERSIST_WGS_PER_CU=r lowers the residency by padding
-// the LDS request (experiments).
-static int persist_max_per_cu(int v, size_t lds) {
-  int per_cu = 4 * kPersistForms[v].waves;
-  if (lds_wgs_per_cu(lds) < per_cu) per_cu = lds_wgs_per_cu(lds);
-  return per_cu < 1 ? 1 : per_cu;
-}
-static size_t persist_tuned_lds(int v, size_t lds) {
-  const int rmax = persist_max_per_cu(v, lds);
-  int want_r = rmax;
-  if (const char* e = getenv("ORL_PERSIST_WGS_PER_CU")) { int f = atoi(e); if (f >= 1 && f <= rmax) want_r = f; }
-  if (want_r == rmax) return lds;
-  const size_t want = ((size_t)(160 * 1024) / (size_t)want_r) / 1280 * 1280;  // the largest window that still fits want_r times
-  return want > lds ? want : lds;
-}
-// forms 2 and 3 (link statistics and sums in LDS too) measured slower everywhere: they are built only into the
-// -DORL_ALT_IMPLS library, as one more independent form for the cross-implementation tests
-#ifdef ORL_ALT_IMPLS
-#define ORL_FULL_LDS_CASES(E_) case 2: LAUNCH(E_, 2, 2); break; case 3: LAUNCH(E_, 2, 3); break;
-#else
-#define ORL_FULL_LDS_CASES(E_)
-#endif
+// The persistent kernel in the form persist_choose (orl_persist_form.h) takes for the whole batch, over the env range of view VP0.
 template <int W> void persist(orl_batch* b, const DevParams& VP0, hipStream_t st, int pol, int target, int* wg_step, unsigned int* unfinished,
                               unsigned int* clear_next, int finish) {
   DevParams VP = VP0;
   VP.persist_finish = finish;
   dim3 gc((unsigned)((VP.B + 7) / 8)), blk(64);
-  bool use_spec = b->spec_launch != nullptr;
-  if (const char* e = getenv("ORL_PERSIST_SPEC")) { if (atoi(e) == 0) use_spec = false; }
-  // the form is chosen for the WHOLE batch (its wavefront count decides between the 3- and the 4-wave form, and a specialisation
-  // library is built for that choice): a run in two halves launches the same kernel on both views
+  const PersistOverrides ov = persist_overrides_from_env();
+  const bool use_spec = persist_use_spec(b->spec_launch != nullptr, ov);
+  // the form is chosen for the WHOLE batch: a run in two halves launches the same kernel on both views
   DevParams VC = VP;
   VC.B = b->P.B;
-  const PersistChoice ch = persist_choose(VC, use_spec);
+  const PersistChoice ch = persist_choose(VC, use_spec, ov);
   const int v = ch.form;
+  const PersistForm& F = kPersistForms[v];
   VP.persist_ic = ch.inner;
   VP.persist_evl = ch.evl;
-  VP.persist_fair = 11;  // (20 us per priority level: about one step)
-  if (const char* e = getenv("ORL_PERSIST_FAIR")) { const int f = atoi(e); if (f >= 0 && f <= 30) VP.persist_fair = f; }  // A/B: 0 = the arbiter's oldest-first
-  VP.row_cache_key = VP.row_cache ? ((b->cache_epoch << 8) | (v << 4) | ch.inner) : 0;
-  if (const char* e = getenv("ORL_ROW_CACHE_KEEP")) { if (atoi(e) == 0) VP.row_cache_key = 0; }  // A/B: rebuild at every launch
-  size_t lds_a = persist_tuned_lds(v, ch.lds);
-#define LAUNCH(E_, LDS_, WV_)                                                                                                 \
-  do {                                                                                                                       \
-    if (lds_a > 48 * 1024) hipFuncSetAttribute((const void*)k_persist<E_, W, LDS_, WV_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a); \
-    hipLaunchKernelGGL((k_persist<E_, W, LDS_, WV_>), gc, blk, lds_a, st, VP, pol, target, wg_step, unfinished, clear_next); \
-  } while (0)
-  // an instantiation built for this very configuration (orl_batch_load_spec)?  (ORL_PERSIST_SPEC=0: the generic kernel)
-  bool spec = b->spec_launch != nullptr && b->spec_lds == kPersistForms[v].lds && b->spec_waves == kPersistForms[v].waves + 16 * ch.rw;
-  if (const char* e = getenv("ORL_PERSIST_SPEC")) { if (atoi(e) == 0) spec = false; }
+  VP.persist_fair = ch.fair;
+  VP.row_cache_key = (VP.row_cache && ch.row_cache_keep) ? ((b->cache_epoch << 8) | (v << 4) | ch.inner) : 0;
+  const size_t lds_a = ch.launch_lds;
+  // an instantiation built for this very configuration and form (orl_batch_load_spec)?
+  const bool spec = use_spec && b->spec_lds == F.lds_arg && b->spec_waves == F.waves && b->spec_rw == ch.rw;
   b->persist_spec = spec ? (ch.rw ? 2 : 1) : 0;  // (debug query: 2 = the two-wavefront form)
   b->persist_form_last = v;
   if (spec) {
     b->spec_launch(&VP, gc.x, lds_a, st, pol, target, wg_step, unfinished, clear_next);
   } else {
-#define PER_ENV(E_)                                                                                                          \
-  switch (v) {                                                                                                               \
-    case 0: if constexpr (E_ != ENV_RMCSA) LAUNCH(E_, 0, 4); break;                                                          \
-    case 1: LAUNCH(E_, 0, 3); break;                                                                                         \
-    ORL_FULL_LDS_CASES(E_)                                                                                                   \
-    case 4: LAUNCH(E_, 1, 3); break;                                                                                         \
-    case 6: if constexpr (E_ != ENV_RMCSA) LAUNCH(E_, 3, 4); break;                                                          \
-    case 7: if constexpr (E_ != ENV_RMCSA) LAUNCH(E_, 4, 4); break;                                                          \
-    case 8: if constexpr (E_ != ENV_RMCSA) LAUNCH(E_, 5, 4); break;                                                          \
-    default: if constexpr (E_ != ENV_RMCSA) LAUNCH(E_, 1, 4); break;                                                         \
-  }
+    // one case per row of the table: the generic kernel of every form this library carries for the family (persist_form_built);
+    // any other number launches nothing — persist_choose never returns one
+    static_assert(kPersistFormCount == 9, "a case per form below");
+#define FORM(E_, F_)                                                                                                          \
+  case F_:                                                                                                                   \
+    if constexpr (persist_form_built(E_, F_)) {                                                                              \
+      constexpr int LDS_ = kPersistForms[F_].lds_arg, WV_ = kPersistForms[F_].waves;                                        \
+      if (lds_a > 48 * 1024) hipFuncSetAttribute((const void*)k_persist<E_, W, LDS_, WV_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a); \
+      hipLaunchKernelGGL((k_persist<E_, W, LDS_, WV_>), gc, blk, lds_a, st, VP, pol, target, wg_step, unfinished, clear_next); \
+      launched = true;                                                                                                       \
+    }                                                                                                                        \
+    break;
+// (form 5 named last: the order in which the instantiations have always been emitted into the code object)
+#define PER_ENV(E_) \
+  switch (v) { FORM(E_, 0) FORM(E_, 1) FORM(E_, 2) FORM(E_, 3) FORM(E_, 4) FORM(E_, 6) FORM(E_, 7) FORM(E_, 8) FORM(E_, 5) }
+    bool launched = false;
     ORL_FOR_ENV(b, PER_ENV)
 #undef PER_ENV
+#undef FORM
+    assert(launched && "persist_choose returned a form this library does not carry");
   }
-#undef LAUNCH
   // rows-deferred forms: the link statistics and the compactness sums of the launch's events, one lane per link row, behind the
   // launch on its stream and in front of k_stats (which reads the sums it puts into the statistics log)
-  if (persist_rd_state(kPersistForms[v].lds)) {
-    // (this form writes slot maps without keeping the other forms' row caches: a stamp they left must not match again)
-    if (++b->cache_epoch >= (1 << 22)) {
-      if (b->P.row_cache_stamp) hipMemsetAsync(b->P.row_cache_stamp, 0, (size_t)((b->P.B + 7) / 8) * sizeof(int), st);
-      b->cache_epoch = 1;
-    }
+  if (F.rd) {
+    slot_maps_change(b, st);  // (this form writes slot maps without keeping the other forms' row caches: a stamp they left must not match again)
     int G = ORL_ROWSTATS_THREADS / VP.E;
     G = G > ORL_RS_GMAX ? ORL_RS_GMAX : G;
     const size_t lds_r = (size_t)rowstats_lds_layout(G).total;
@@ -2517,7 +2313,7 @@ template <int W> void persist(orl_batch* b, const DevParams& VP0, hipStream_t st
   // on its stream; the forms that keep it in the loop logged nothing
   if (orl_persist_deferred(VP.env_type) && VP.slog) {
     dim3 gs((unsigned)((VP.B + ORL_STATS_LANES - 1) / ORL_STATS_LANES));
-    const bool rd = persist_rd_state(kPersistForms[v].lds);
+    const bool rd = F.rd;
     // (discrete bit rates: the per-rate counts of a launch in LDS, 2 n_br counters per lane)
     const int br_lds = (VP.bit_rate_mode == 1 && VP.br_hist && (size_t)ORL_STATS_LANES * 2 * VP.n_br * 4 <= 48 * 1024) ? 1 : 0;
     const size_t brb = br_lds ? (size_t)ORL_STATS_LANES * 2 * VP.n_br * 4 : 0;
@@ -2555,9 +2351,7 @@ template <int W> void agent_step(orl_batch* b, int auto_reset, int pol) {
   }
   const size_t lds = (size_t)persist_lds_layout(VP.E, VP.H, VP.bm_words, VP.C, 0, VP.env_type != ENV_RMCSA, 0, true).total + (size_t)8 * VP.E * 16;
   // the instantiation built for this configuration, when a specialisation library is attached (ORL_PERSIST_SPEC=0: generic)
-  bool spec = b->spec_agent_launch != nullptr;
-  if (const char* e = getenv("ORL_PERSIST_SPEC")) { if (atoi(e) == 0) spec = false; }
-  if (spec) {
+  if (persist_use_spec(b->spec_agent_launch != nullptr, persist_overrides_from_env())) {
     b->spec_agent_launch(&VP, g.x, lds, b->stream, auto_reset, pol);
     ORL_TK(b, "k_agent");
     return;
@@ -2568,13 +2362,6 @@ template <int W> void agent_step(orl_batch* b, int auto_reset, int pol) {
   ORL_FOR_ENV(b, PER_ENV)
 #undef PER_ENV
   ORL_TK(b, "k_agent");
-}
-
-// wavefronts of the persistent kernel a GPU of `n_cu` CUs holds at once for this batch (LDS window and register budget)
-template <int W> int persist_resident(orl_batch* b, int n_cu) {
-  size_t lds = 0;
-  const int v = persist_variant(b->P, &lds, b->spec_launch != nullptr);
-  return persist_max_per_cu(v, lds) * n_cu;
 }
 
 template <int W> void step2(orl_batch* b, int pol) {
@@ -2607,27 +2394,7 @@ template <int W> void step2(orl_batch* b, int pol) {
 #endif
 }
 
-// diagnostic builds (-DORL_TIMING): per-phase cycle sums of this unit's persistent kernels; zeros otherwise
-template <int W> int prof_read(unsigned long long* out48, int reset) {
-#ifdef ORL_TIMING
-  if (reset == 2) return hipMemcpyFromSymbol(out48, HIP_SYMBOL(g_wts), 16384 * 8 * 8) == hipSuccess ? 0 : -1;
-  if (reset == 3) return hipMemcpyFromSymbol(out48, HIP_SYMBOL(sp::g_prof), (size_t)ORL_PROF_WAVES * ORL_PROF_SLOTS * 8) == hipSuccess ? 0 : -1;
-#endif
-  for (int k = 0; k < ORL_PROF_SLOTS; k++) out48[k] = 0;
-#ifdef ORL_TIMING
-  std::vector<unsigned long long> h((size_t)ORL_PROF_WAVES * ORL_PROF_SLOTS);
-  if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(sp::g_prof), h.size() * 8) != hipSuccess) return -1;
-  for (size_t w = 0; w < ORL_PROF_WAVES; w++)
-    for (int k = 0; k < ORL_PROF_SLOTS; k++) out48[k] += h[w * ORL_PROF_SLOTS + k];
-  if (reset) {
-    std::fill(h.begin(), h.end(), 0ull);
-    if (hipMemcpyToSymbol(HIP_SYMBOL(sp::g_prof), h.data(), h.size() * 8) != hipSuccess) return -1;
-  }
-#else
-  (void)reset;
-#endif
-  return 0;
-}
+template <int W> int prof_read(unsigned long long* out48, int reset) { return persist_prof_read(out48, reset); }
 
 template void reset<ORL_W>(orl_batch*, int, const unsigned char*);
 template int prof_read<ORL_W>(unsigned long long*, int);
@@ -2636,11 +2403,8 @@ template void step64<ORL_W>(orl_batch*, int, int, int);
 template void obs<ORL_W>(orl_batch*, int);
 template int action_mask<ORL_W>(orl_batch*, int, unsigned char*, int);
 template void persist<ORL_W>(orl_batch*, const DevParams&, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);
-template int persist_resident<ORL_W>(orl_batch*, int);
-template int persist_uses_lds<ORL_W>(orl_batch*);
 template void step2<ORL_W>(orl_batch*, int);
 template void agent_step<ORL_W>(orl_batch*, int, int);
-template void persist_form<ORL_W>(const DevParams&, int*, int*);
 
 }  // namespace orl_launch
 #endif  // ORL_SPEC_ONLY

@@ -333,12 +333,29 @@ class BatchedOpticalEnv:
     def spec_flags(cls, batch=1 << 20, **kwargs):
         """The -D flags of this configuration's specialisation for a batch of `batch` envs (the kernel form depends on it),
         computed without a device (pre-building, __graft_entry__.build)."""
-        self = cls.__new__(cls)
-        self._derive_only = True
-        self.__init__(num_envs=1, **kwargs)
+        self = cls._derived(**kwargs)
         buf = C.create_string_buffer(1024)
         n = self.lib.orl_spec_flags_for_batch(C.byref(self._cfg), C.byref(self._desc), int(batch), buf, len(buf))
         return buf.value.decode() if n > 0 else None
+
+    @classmethod
+    def _derived(cls, **kwargs):
+        """This configuration as the C ABI takes it (_cfg, _desc), without a device or a batch."""
+        self = cls.__new__(cls)
+        self._derive_only = True
+        self.__init__(num_envs=1, **kwargs)
+        return self
+
+    PERSIST_CHOICE_FIELDS = ("form", "lds_arg", "waves", "rw", "inner", "evl", "window_bytes", "launch_lds_bytes", "wgs_per_cu")
+
+    def persist_choice(self, batch, tuned=True, variant=None):
+        """What the launcher of the persistent kernel chooses for a batch of `batch` envs of this configuration (include/orl.h,
+        orl_debug_persist_choice; no device needed): a tuple in the order of PERSIST_CHOICE_FIELDS, None where the persistent
+        kernel does not serve the configuration.  `variant`: the library build asked ("alt" carries forms 2 and 3)."""
+        out = (C.c_int32 * len(self.PERSIST_CHOICE_FIELDS))()
+        lib = _lib.lib(variant) if variant else self.lib
+        n = lib.orl_debug_persist_choice(C.byref(self._cfg), C.byref(self._desc), int(batch), int(bool(tuned)), out)
+        return tuple(out) if n > 0 else None
 
     def _ck(self, rc):
         _lib.check(rc, self.lib)

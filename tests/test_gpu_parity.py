@@ -9,8 +9,9 @@ from tests.helpers import golden_names, load_golden, replay, replay_h, replay_q,
 pytestmark = pytest.mark.gpu
 
 # Device-resident runs go through the persistent kernel (k_persist) wherever it applies, host-driven step() through the
-# one-wavefront-per-env kernel (k_step).  The small parity cases run against every implementation by forcing it (the
-# variables are read when a batch is created): "wave64" = k_step for everything, "persist" = the default, "split2" = the
+# one-wavefront-per-env kernel (k_step).  The small parity cases run against every implementation by forcing it
+# (ORL_STEP_IMPL, ORL_PERSIST and ORL_AGENT_STEP are read when a batch is created; the form overrides — ORL_PERSIST_VARIANT,
+# _INNER, _RW — at every launch of the persistent kernel): "wave64" = k_step for everything, "persist" = the default, "split2" = the
 # phases of the persistent kernel as two separate launches (liborlgpu_alt.so, the -DORL_ALT_IMPLS build).
 IMPLS = ["wave64", "split2", "persist", "persist_global", "persist_lds", "agent8", "persist_pair", "persist_rd"]
 IMPL_ENV = {"wave64": dict(ORL_STEP_IMPL="64", ORL_PERSIST="0", ORL_LIB_VARIANT="default", ORL_PERSIST_VARIANT=None, ORL_PERSIST_INNER=None),

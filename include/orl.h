@@ -58,7 +58,11 @@ extern "C" {
 #define ORL_POLICY_PATH_FF 4
 
 /* Flattened topology: what the reference keeps in topology.graph["ksp"] / ["modulations"] and in the
- * networkx edge attributes (examples/create_topology.py:96-147).  All arrays are copied. */
+ * networkx edge attributes (examples/create_topology.py:96-147).  All arrays are copied.
+ * Accepted: 2..512 nodes, 1..128 links, k_paths 1..64, max_hops 1..30, 1..255 modulations, n_paths[i] <= k_paths, every link
+ * index < n_links, edge_iter_order a permutation; anything else is ORL_E_INVALID.  (A connected topology has at most
+ * n_links + 1 nodes, so the link limit is the one that binds: 129 nodes — a tree of 128 links — is the largest connected
+ * network the library takes; more nodes only with node pairs that have no path.) */
 typedef struct {
   int32_t n_nodes, n_links, k_paths, max_hops, n_modulations;
   const int32_t* n_paths;         /* [n_nodes*n_nodes]            paths available for (src,dst) */

@@ -1278,8 +1278,7 @@ static int mask_check(const orl_batch* b, int layout) {
     return fail(ORL_E_INVALID, "action masks are not available for %s (RMSA, DeepRMSA and RWA only)", t == ENV_RMCSA ? "RMCSA" : "QoSConstrainedRA");
   if (layout != ORL_MASK_JOINT && layout != ORL_MASK_PATH) return fail(ORL_E_INVALID, "unknown action-mask layout %d", layout);
   if (!mask_dim(b->P, layout)) return fail(ORL_E_INVALID, "DeepRMSA has no path-only action space: use ORL_MASK_JOINT");
-  if (t == ENV_DEEPRMSA && b->P.J > 64) return fail(ORL_E_INVALID, "action masks support j <= 64 blocks per path (j = %d)", b->P.J);
-  return ORL_OK;
+  return ORL_OK;  // (DeepRMSA: a path's blocks are bits of one u64, and batch_create_impl admits j <= 8)
 }
 
 extern "C" int orl_batch_action_mask_shape(const orl_batch* b, int layout, int32_t* dim, int32_t* pitch) try {

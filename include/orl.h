@@ -430,6 +430,17 @@ int orl_batch_debug_persist_form(orl_batch* b);
  * per CU.  `tuned`: the choice made when a specialisation library is attached.  The ORL_PERSIST_* overrides are read from the
  * environment as at a launch.  Returns 9, or 0 when the configuration does not run the persistent kernel. */
 int orl_debug_persist_choice(const orl_env_config* cfg, const orl_topology_desc* topo, int64_t n_envs, int tuned, int32_t* out);
+/* The host-side decisions for a batch of n_envs envs of this configuration, without a device (tests/test_run_plan.py).  The step
+ * route taken at creation: out[0..4] = device-resident runs through the persistent kernel, the two-kernel form (ORL_ALT_IMPLS
+ * builds), host-driven steps through k_agent, DevParams::item_masks, DevParams::rel_limit.  The plan of a device-resident run of
+ * n_steps steps on a GPU of n_cu CUs, for a batch whose statistics log holds log_cap_have steps, whose workgroups stand at step
+ * run_base and whose last run did not complete (wg_dirty): out[5..10] = steps per launch, parts (1, or 2: two halves on two
+ * streams), envs of the first half, steps the statistics log must hold, events per env the event log must hold (0 unless the
+ * chosen form is rows-deferred), step counters cleared first; zeros where the persistent kernel does not serve the batch.
+ * `tuned` as for orl_debug_persist_choice.  Every override is read from the environment as at creation / at a run.  Returns 11,
+ * or 0 for an invalid configuration. */
+int orl_debug_run_plan(const orl_env_config* cfg, const orl_topology_desc* topo, int64_t n_envs, int64_t n_steps, int tuned, int n_cu,
+                       int log_cap_have, int64_t run_base, int wg_dirty, int32_t* out);
 /* Which kernel orl_batch_step launches for this batch: 2 = k_agent (8 lanes per env, the persistent kernel's phases for one
  * step; QoSConstrainedRA: k_agent_qos, from 20 480 envs), 0 = k_step (one wavefront per env). */
 int orl_batch_debug_step_kernel(orl_batch* b);

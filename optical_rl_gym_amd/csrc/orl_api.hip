@@ -16,10 +16,11 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "orl_host.h"
-#include "orl_persist_form.h"
+#include "orl_run_plan.h"
 
 using namespace orl;
 
@@ -326,52 +327,12 @@ extern "C" void orl_topology_destroy(orl_topology* t) try {
 ORL_ABI_CATCH_VOID
 
 // ---- launch dispatch over the row width ---------------------------------------------------------------
-static void launch_reset(orl_batch* b, int full, const unsigned char* dmask) {
-  slot_maps_change(b, b->stream);
-#define CALL(WW) orl_launch::reset<WW>(b, full, dmask)
-  ORL_DISPATCH_W(b, CALL)
-#undef CALL
-}
-static void launch_policy(orl_batch* b, int pol) {
-#define CALL(WW) orl_launch::policy<WW>(b, pol)
-  ORL_DISPATCH_W(b, CALL)
-#undef CALL
-}
-static void launch_step64(orl_batch* b, int auto_reset, int want_info, int fused_policy) {
-  slot_maps_change(b, b->stream);
-#define CALL(WW) orl_launch::step64<WW>(b, auto_reset, want_info, fused_policy)
-  ORL_DISPATCH_W(b, CALL)
-#undef CALL
-}
-static void launch_agent_step(orl_batch* b, int auto_reset, int pol = -1) {
-  slot_maps_change(b, b->stream);
-#define CALL(WW) orl_launch::agent_step<WW>(b, auto_reset, pol)
-  ORL_DISPATCH_W(b, CALL)
-#undef CALL
-}
-static void launch_obs(orl_batch* b, int with_terminal) {
-#define CALL(WW) orl_launch::obs<WW>(b, with_terminal)
-  ORL_DISPATCH_W(b, CALL)
-#undef CALL
-}
-static int launch_action_mask(orl_batch* b, int layout, unsigned char* out, int pitch) {
-  int r = 0;
-#define CALL(WW) r = orl_launch::action_mask<WW>(b, layout, out, pitch)
-  ORL_DISPATCH_W(b, CALL)
-#undef CALL
-  return r;
-}
-static void launch_persist(orl_batch* b, const DevParams& VP, hipStream_t st, int pol, int target, int* wg_step, unsigned int* unfinished,
-                           unsigned int* clear_next, int finish) {
-#define CALL(WW) orl_launch::persist<WW>(b, VP, st, pol, target, wg_step, unfinished, clear_next, finish)
-  ORL_DISPATCH_W(b, CALL)
-#undef CALL
-}
-// wavefronts of the persistent kernel the GPU holds at once for this batch (LDS window and register budget).  (An attached
-// specialisation library counts here whatever ORL_PERSIST_SPEC says.)
-static int persist_resident(orl_batch* b) {
-  return persist_choose(b->P, b->spec_launch != nullptr, persist_overrides_from_env()).wgs_per_cu * b->n_cu;
-}
+// ORL_LAUNCH(fn, args...): orl_launch::fn<W>(args...) for the row width of the batch `b` in scope
+#define ORL_W_RETURN_(WW) return f(std::integral_constant<int, WW>{})
+template <typename F> static auto dispatch_w(const orl_batch* b, F f) { ORL_DISPATCH_W(b, ORL_W_RETURN_) }
+#define ORL_LAUNCH(FN, ...) dispatch_w(b, [&](auto w_) { return orl_launch::FN<decltype(w_)::value>(__VA_ARGS__); })
+// ... in front of the kernels that write slot maps outside the persistent kernel (reset, step64, agent_step, step2)
+#define ORL_LAUNCH_MAPS(FN, ...) (slot_maps_change(b, b->stream), ORL_LAUNCH(FN, __VA_ARGS__))
 // the per-env arrays of envs [lo, lo + cnt) as a batch of their own (lo a multiple of 8: wavefronts own 8 consecutive envs)
 static DevParams env_view(const DevParams& P, i64 lo, i64 cnt, int part) {
   DevParams q = P;
@@ -397,12 +358,6 @@ static DevParams env_view(const DevParams& P, i64 lo, i64 cnt, int part) {
   q.q_a += (lo / 8) * P.q_wave * 2; q.q_cnt_a += lo / 8;
   q.q_def = P.q_def + (size_t)part * P.q_def_stride;  // each part has its own list of deferred envs (indices relative to lo)
   return q;
-}
-static void launch_step2(orl_batch* b, int pol) {
-  slot_maps_change(b, b->stream);
-#define CALL(WW) orl_launch::step2<WW>(b, pol)
-  ORL_DISPATCH_W(b, CALL)
-#undef CALL
 }
 // OR of the env flag words into d_unfinished[17] (the pair report_flags owns; the persistent launches have their own slots)
 static void launch_finish2(orl_batch* b, int finish) {
@@ -541,37 +496,14 @@ static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int
   derive_sizes(c, t->N, t->E, t->K, t->H, t->M, n_envs, P, &b->wt, per_env ? max_load : -1.0);
   if (per_env) P.pf_window = pf_window_of(h_rates);
   if (P.lds_bytes > 64 * 1024) FAIL_B(ORL_E_INVALID, "per-env LDS window too large (%d B)", P.lds_bytes);
-  {
-    // The persistent kernel (k_persist) serves the device-resident loop wherever its 8-lanes-per-env slot scan applies
-    // (k <= 8 paths, release slots indexed with 8 + 3 bits): cfg2 64 envs 2.6e6 vs 2.1e6 env-steps/s for the per-env kernel;
-    // 4 096: 1.6e8 vs 7.6e7; 32 768: 6.3e8 vs 4.0e8; RWA 4 096: 2.4e8 vs 8.3e7.  ORL_STEP_IMPL=64 forces the per-env kernel
-    // (cross-checks); ORL_STEP_IMPL=2 with ORL_PERSIST=0 selects the two-kernel form in ORL_ALT_IMPLS builds.
-    const char* impl = getenv("ORL_STEP_IMPL");
-    const bool pipeline_ok = pipeline_applies(c, P);
-    b->persist = pipeline_ok && !(impl && atoi(impl) == 64);
-    if (const char* pv = getenv("ORL_PERSIST")) {
-      if (atoi(pv) == 0 && b->persist) {
-        b->persist = 0;
-#ifdef ORL_ALT_IMPLS
-        b->two_kernel = (impl && atoi(impl) == 2) ? 1 : 0;
-#endif
-      }
-    }
-  }
+  // which kernels serve this batch's steps (orl_run_plan.h)
+  const StepRoute route = step_route(P, pipeline_applies(c, P), step_overrides_from_env());
+  b->persist = route.persist;
+  b->two_kernel = route.two_kernel;
+  b->agent_step = route.agent_step;
+  P.item_masks = route.item_masks;
+  P.rel_limit = route.rel_limit;
   P.pipeline2 = (b->persist || b->two_kernel) ? 1 : 0;
-  {
-    // Host- / agent-driven steps with auto reset (what SB3's VecEnv issues) through the phases of the persistent kernel
-    // (k_agent) wherever they apply and the batch is large enough to fill the GPU with 8 envs per wavefront: cfg2 65 536 envs
-    // 305 us per step in k_step (one wavefront per env), ~90 us in k_agent.  ORL_AGENT_STEP=1 forces it for any batch size
-    // (parity tests), 0 disables it.
-    // (QoSConstrainedRA, which no persistent kernel serves, has its own 8-lanes-per-env step kernel, k_agent_qos: its releases
-    // are found by 8 lanes scanning the env's release times where k_step has 64, a longer chain per step that pays once the
-    // batch fills the GPU — 65 536 envs 120 against 225 us per step, 32 768: 77 / 109, 16 384: 65 / 66, 4 096: 47 / 33)
-    const char* impl64 = getenv("ORL_STEP_IMPL");
-    const bool fits = (b->persist && P.E <= 128) || (qos && P.K <= 8 && !(impl64 && atoi(impl64) == 64));
-    b->agent_step = fits && n_envs >= (qos ? 20480 : 2048);
-    if (const char* av = getenv("ORL_AGENT_STEP")) b->agent_step = fits && atoi(av) != 0;
-  }
 
   P.n_paths = t->n_paths;
   P.path_length = t->path_length; P.edge_iter_order = t->edge_iter_order; P.link_pos = t->link_pos;
@@ -617,10 +549,6 @@ static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int
     // a provision touches <= H links, the releases of a step <= E links (one item per link)
     const size_t waves = ((B + 31) / 32 + 16) * 4;
     P.q_wave = 8 * (P.H > P.E ? P.H : P.E);
-    P.item_masks = ORL_IMASKS;
-    // test knob: a smaller limit sends far more env-steps through the serial tail (and, RMCSA, the tally pass)
-    P.rel_limit = 31;
-    if (const char* mv = getenv("ORL_ITEM_MASKS")) { int v = atoi(mv); if (v >= 1 && v <= ORL_IMASKS) { P.item_masks = v; P.rel_limit = v; } }
     P.q_cap = (i64)waves * P.q_wave;
     rc |= dalloc(b, &P.q_a, (size_t)P.q_cap * 2);  // 32-byte items
     rc |= dalloc(b, &P.q_cnt_a, waves);
@@ -705,8 +633,8 @@ static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int
     hipLaunchKernelGGL(k_seed_mt, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, b->stream, dseeds, (i64)B, raw);
   }
   hipLaunchKernelGGL(k_init_mt, dim3((unsigned)B), dim3(64), 624 * 4, b->stream, P, raw, (const unsigned char*)nullptr, 0);
-  launch_reset(b, 1, nullptr);
-  if (P.obs_dim) launch_obs(b, 0);
+  ORL_LAUNCH_MAPS(reset, b, 1, nullptr);
+  if (P.obs_dim) ORL_LAUNCH(obs, b, 0);
   HIPCHK_B(hipStreamSynchronize(b->stream));
   HIPCHK_B(hipGetLastError());
   hipFree(raw);
@@ -783,8 +711,8 @@ extern "C" int orl_batch_reset(orl_batch* b, int full, const uint8_t* env_mask) 
   HIPCHK(hipSetDevice(b->device));
   DevMask m;
   if (m.upload(b, env_mask)) return ORL_E_HIP;
-  launch_reset(b, full ? 1 : 0, m.d);
-  if (b->P.obs_dim) launch_obs(b, 0);
+  ORL_LAUNCH_MAPS(reset, b, full ? 1 : 0, m.d);
+  if (b->P.obs_dim) ORL_LAUNCH(obs, b, 0);
   HIPCHK(hipStreamSynchronize(b->stream));
   HIPCHK(hipGetLastError());
   // (a full reset of every env leaves nothing of an abandoned run behind: k_reset dropped the parked services of the envs it
@@ -989,7 +917,7 @@ extern "C" int orl_batch_policy(orl_batch* b, int policy_id, int32_t* actions_ou
   if (!b) return fail(ORL_E_INVALID, "null batch");
   if (!policy_ok(b, policy_id)) return fail(ORL_E_INVALID, "policy %d is not defined for this env family", policy_id);
   HIPCHK(hipSetDevice(b->device));
-  launch_policy(b, policy_id);
+  ORL_LAUNCH(policy, b, policy_id);
   if (actions_out) {
     HIPCHK(hipMemcpyAsync(actions_out, b->P.actions, (size_t)b->P.B * 4 * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
@@ -999,23 +927,6 @@ extern "C" int orl_batch_policy(orl_batch* b, int policy_id, int32_t* actions_ou
 }
 ORL_ABI_CATCH_INT
 
-// the index ranges of the reference's actions_output arrays (rmsa_env.py:126-137, 167; rwa_env.py:52-58, 103;
-// rmcsa_env.py:145-153, 219); DeepRMSA takes any integer (deeprmsa_env.py:48-58)
-static int64_t first_bad_action(const orl_batch* b, const int32_t* a) {
-  const DevParams& P = b->P;
-  const int rej = P.allow_rejection ? 1 : 0;
-  for (i64 i = 0; i < P.B; i++) {
-    const int32_t* r = a + 4 * i;
-    bool bad = false;
-    if (P.env_type == ENV_RMSA) bad = r[0] < 0 || r[0] > P.K || r[1] < 0 || r[1] > P.S;
-    else if (P.env_type == ENV_RWA) bad = r[0] < 0 || r[0] >= P.K + rej || r[1] < 0 || r[1] >= P.S + rej;
-    else if (P.env_type == ENV_RMCSA) bad = r[0] < 0 || r[0] > P.K || r[1] < 0 || r[1] > P.M || r[2] < 0 || r[2] > P.C || r[3] < 0 || r[3] > P.S;
-    else if (P.env_type == ENV_QOS) bad = r[0] < 0 || r[0] >= P.K + rej;  // qos_constrained_ra.py:101
-    if (bad) return i;
-  }
-  return -1;
-}
-
 static int flags_to_rc(const orl_batch* b, unsigned int f) {
   if (f & ORL_FLAG_EV_OVERFLOW)
     return fail(ORL_E_OVERFLOW, "an env ran out of pending-release slots (event_capacity %d): its state is no longer valid", b->P.ev_cap);
@@ -1023,15 +934,74 @@ static int flags_to_rc(const orl_batch* b, unsigned int f) {
     return fail(ORL_E_ACTION, "a device-resident action was outside the action space (it was treated as a rejection)");
   return ORL_OK;
 }
-// after a synchronous call: report what the kernels flagged (device-resident actions cannot be checked beforehand)
-static int report_flags(orl_batch* b) {
-  unsigned int* f = b->h_tail + 16;
+// what the kernels flagged (device-resident actions cannot be checked beforehand), queued: the OR of the flag words -> h_tail[17]
+static int queue_flags(orl_batch* b) {
   HIPCHK(hipMemsetAsync(b->d_unfinished + 16, 0, 2 * sizeof(unsigned int), b->stream));
   launch_finish2(b, 0);
-  HIPCHK(hipMemcpyAsync(f, b->d_unfinished + 16, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipMemcpyAsync(b->h_tail + 16, b->d_unfinished + 16, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, b->stream));
+  return ORL_OK;
+}
+// ... and reported, after a synchronous call
+static int report_flags(orl_batch* b) {
+  if (const int rc = queue_flags(b)) return rc;
   HIPCHK(hipStreamSynchronize(b->stream));
   HIPCHK(hipGetLastError());
-  return flags_to_rc(b, f[1]);
+  return flags_to_rc(b, b->h_tail[17]);
+}
+// the observation array as float32, queued: cast on the device (the buffer is allocated on first use), then the copy
+static int queue_obs_f32(orl_batch* b, float* obs_out) {
+  const i64 n = b->P.B * b->P.obs_dim;
+  if (!b->obs_f32) {
+    HIPCHK(hipMalloc((void**)&b->obs_f32, (size_t)n * sizeof(float) + 64));
+    b->allocs.push_back(b->obs_f32);
+  }
+  hipLaunchKernelGGL(k_cast_f32, dim3(2048), dim3(256), 0, b->stream, b->P.obs, b->obs_f32, n);
+  HIPCHK(hipMemcpyAsync(obs_out, b->obs_f32, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+  return ORL_OK;
+}
+
+// one pass over the caller's compact action rows: range check (the reference's IndexError at its first statement — the index
+// ranges of its actions_output arrays, rmsa_env.py:126-137, 167; rwa_env.py:52-58, 103; rmcsa_env.py:145-153, 219;
+// qos_constrained_ra.py:101; DeepRMSA takes any integer, deeprmsa_env.py:48-58) and, with `dst`, expansion into the [n][4] int32
+// rows the kernels read; returns the first bad env or -1
+template <typename T> static int64_t stage_actions(const orl_batch* b, const T* src, int width, int32_t* dst) {
+  const DevParams& P = b->P;
+  const int rej = P.allow_rejection ? 1 : 0;
+  int hi[4] = {0, 0, 0, 0};  // exclusive upper bounds per column (0: any value, DeepRMSA)
+  if (P.env_type == ENV_RMSA) { hi[0] = P.K + 1; hi[1] = P.S + 1; }
+  else if (P.env_type == ENV_RWA) { hi[0] = P.K + rej; hi[1] = P.S + rej; }
+  else if (P.env_type == ENV_RMCSA) { hi[0] = P.K + 1; hi[1] = P.M + 1; hi[2] = P.C + 1; hi[3] = P.S + 1; }
+  else if (P.env_type == ENV_QOS) { hi[0] = P.K + rej; }
+  int64_t bad = -1;
+  for (i64 i = 0; i < P.B; i++) {
+    const T* r = src + (size_t)i * width;
+    for (int c = 0; c < 4; c++) {
+      const long long v = c < width ? (long long)r[c] : 0;
+      if (hi[c] > 0 && c < width && (v < 0 || v >= hi[c]) && bad < 0) bad = i;
+      if (dst) dst[4 * i + c] = (int32_t)v;
+    }
+  }
+  return bad;
+}
+
+// one step with info / obs written, queued on the batch's stream.  pol < 0: the actions in P.actions; else the heuristic's:
+// where k_agent serves the batch (and k <= 8) the slot scan is the step kernel's first phase, else k_policy goes in front
+static void queue_step(orl_batch* b, int auto_reset, int pol = -1) {
+  const bool fused = pol >= 0 && b->agent_step && b->P.K <= 8;
+  if (pol >= 0 && !fused) ORL_LAUNCH(policy, b, pol);
+  if (b->agent_step) ORL_LAUNCH_MAPS(agent_step, b, auto_reset ? 1 : 0, fused ? pol : -1);
+  else ORL_LAUNCH_MAPS(step64, b, auto_reset ? 1 : 0, 1, -1);
+}
+// the copies of whatever results the caller asked for, queued behind the step; 1: something was queued, 0: nothing, < 0: an error
+static int queue_results(orl_batch* b, int32_t* actions_out, double* obs_out, double* reward_out, uint8_t* done_out, double* info_out) {
+  const size_t B = (size_t)b->P.B;
+  int any = 0;
+  if (actions_out) { HIPCHK(hipMemcpyAsync(actions_out, b->P.actions, B * 4 * sizeof(int), hipMemcpyDeviceToHost, b->stream)); any = 1; }
+  if (reward_out) { HIPCHK(hipMemcpyAsync(reward_out, b->P.reward, B * sizeof(double), hipMemcpyDeviceToHost, b->stream)); any = 1; }
+  if (done_out) { HIPCHK(hipMemcpyAsync(done_out, b->P.done, B, hipMemcpyDeviceToHost, b->stream)); any = 1; }
+  if (info_out) { HIPCHK(hipMemcpyAsync(info_out, b->P.info, B * b->P.n_info * sizeof(double), hipMemcpyDeviceToHost, b->stream)); any = 1; }
+  if (obs_out && b->P.obs_dim) { HIPCHK(hipMemcpyAsync(obs_out, b->P.obs, B * b->P.obs_dim * sizeof(double), hipMemcpyDeviceToHost, b->stream)); any = 1; }
+  return any;
 }
 
 extern "C" int orl_batch_step(orl_batch* b, const int32_t* actions, int auto_reset, double* obs_out, double* reward_out,
@@ -1040,20 +1010,15 @@ extern "C" int orl_batch_step(orl_batch* b, const int32_t* actions, int auto_res
   HIPCHK(hipSetDevice(b->device));
   const size_t B = (size_t)b->P.B;
   if (actions) {
-    const int64_t bad = first_bad_action(b, actions);
+    const int64_t bad = stage_actions(b, actions, 4, nullptr);
     if (bad >= 0)  // like the reference's IndexError at its first statement: nothing has been modified
       return fail(ORL_E_ACTION, "action (%d, %d, %d, %d) of env %lld is outside the action space", actions[4 * bad],
                   actions[4 * bad + 1], actions[4 * bad + 2], actions[4 * bad + 3], (long long)bad);
     HIPCHK(hipMemcpyAsync(b->P.actions, actions, B * 4 * sizeof(int), hipMemcpyHostToDevice, b->stream));
   }
-  if (b->agent_step) launch_agent_step(b, auto_reset ? 1 : 0);
-  else launch_step64(b, auto_reset ? 1 : 0, 1, -1);
-  bool any = false;
-  if (reward_out) { HIPCHK(hipMemcpyAsync(reward_out, b->P.reward, B * sizeof(double), hipMemcpyDeviceToHost, b->stream)); any = true; }
-  if (done_out) { HIPCHK(hipMemcpyAsync(done_out, b->P.done, B, hipMemcpyDeviceToHost, b->stream)); any = true; }
-  if (info_out) { HIPCHK(hipMemcpyAsync(info_out, b->P.info, B * b->P.n_info * sizeof(double), hipMemcpyDeviceToHost, b->stream)); any = true; }
-  if (obs_out && b->P.obs_dim) { HIPCHK(hipMemcpyAsync(obs_out, b->P.obs, B * b->P.obs_dim * sizeof(double), hipMemcpyDeviceToHost, b->stream)); any = true; }
-  if (any) return report_flags(b);  // synchronises
+  queue_step(b, auto_reset);
+  const int any = queue_results(b, nullptr, obs_out, reward_out, done_out, info_out);
+  if (any) return any < 0 ? any : report_flags(b);  // synchronises
   if (actions) {
     HIPCHK(hipStreamSynchronize(b->stream));
     HIPCHK(hipGetLastError());
@@ -1067,29 +1032,6 @@ ORL_ABI_CATCH_INT
 // stay valid until the second half; page-locked ones from orl_host_alloc make the copies asynchronous), the flag word — on the
 // batch's stream and returns; the second waits for the stream and reports like orl_batch_step.  Host work done in between
 // (the agent's bookkeeping of the previous step) overlaps the device's.
-// one pass over the caller's compact action rows: range check (the reference's IndexError) and expansion into the [n][4] int32
-// rows the kernels read; returns the first bad env or -1
-template <typename T> static int64_t stage_actions(const orl_batch* b, const T* src, int width, int32_t* dst) {
-  const DevParams& P = b->P;
-  const int rej = P.allow_rejection ? 1 : 0;
-  int hi[4] = {0, 0, 0, 0};  // exclusive upper bounds per column (0: any value, DeepRMSA)
-  if (P.env_type == ENV_RMSA) { hi[0] = P.K + 1; hi[1] = P.S + 1; }
-  else if (P.env_type == ENV_RWA) { hi[0] = P.K + rej; hi[1] = P.S + rej; }
-  else if (P.env_type == ENV_RMCSA) { hi[0] = P.K + 1; hi[1] = P.M + 1; hi[2] = P.C + 1; hi[3] = P.S + 1; }
-  else if (P.env_type == ENV_QOS) { hi[0] = P.K + rej; }
-  int64_t bad = -1;
-  for (i64 i = 0; i < P.B; i++) {
-    const T* r = src + (size_t)i * width;
-    int32_t* d = dst + 4 * i;
-    for (int c = 0; c < 4; c++) {
-      const long long v = c < width ? (long long)r[c] : 0;
-      if (hi[c] > 0 && c < width && (v < 0 || v >= hi[c]) && bad < 0) bad = i;
-      d[c] = (int32_t)v;
-    }
-  }
-  return bad;
-}
-
 extern "C" int orl_batch_step_async(orl_batch* b, const void* actions, int action_width, int action_elem_bytes, int auto_reset,
                                     double* obs_out, float* obs_f32_out, double* reward_out, uint8_t* done_out, double* info_out) try {
   if (!b) return fail(ORL_E_INVALID, "null batch");
@@ -1108,26 +1050,11 @@ extern "C" int orl_batch_step_async(orl_batch* b, const void* actions, int actio
     }
     HIPCHK(hipMemcpyAsync(b->P.actions, b->h_actions, B * 4 * sizeof(int), hipMemcpyHostToDevice, b->stream));
   }
-  if (b->agent_step) launch_agent_step(b, auto_reset ? 1 : 0);
-  else launch_step64(b, auto_reset ? 1 : 0, 1, -1);
-  if (reward_out) HIPCHK(hipMemcpyAsync(reward_out, b->P.reward, B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  if (done_out) HIPCHK(hipMemcpyAsync(done_out, b->P.done, B, hipMemcpyDeviceToHost, b->stream));
-  if (info_out) HIPCHK(hipMemcpyAsync(info_out, b->P.info, B * b->P.n_info * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  if (b->P.obs_dim && obs_out)
-    HIPCHK(hipMemcpyAsync(obs_out, b->P.obs, B * b->P.obs_dim * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  if (b->P.obs_dim && obs_f32_out) {
-    const i64 n = b->P.B * b->P.obs_dim;
-    if (!b->obs_f32) {
-      HIPCHK(hipMalloc((void**)&b->obs_f32, (size_t)n * sizeof(float) + 64));
-      b->allocs.push_back(b->obs_f32);
-    }
-    hipLaunchKernelGGL(k_cast_f32, dim3(2048), dim3(256), 0, b->stream, b->P.obs, b->obs_f32, n);
-    HIPCHK(hipMemcpyAsync(obs_f32_out, b->obs_f32, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-  }
-  // what the kernels flagged (device-resident actions cannot be checked beforehand), as report_flags gathers it
-  HIPCHK(hipMemsetAsync(b->d_unfinished + 16, 0, 2 * sizeof(unsigned int), b->stream));
-  launch_finish2(b, 0);
-  HIPCHK(hipMemcpyAsync(b->h_tail + 16, b->d_unfinished + 16, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, b->stream));
+  queue_step(b, auto_reset);
+  if (const int rc = queue_results(b, nullptr, obs_out, reward_out, done_out, info_out); rc < 0) return rc;
+  if (b->P.obs_dim && obs_f32_out)
+    if (const int rc = queue_obs_f32(b, obs_f32_out)) return rc;
+  if (const int rc = queue_flags(b)) return rc;
   b->step_pending = 1;
   return ORL_OK;
 }
@@ -1153,22 +1080,9 @@ extern "C" int orl_batch_policy_step(orl_batch* b, int policy_id, int auto_reset
   if (!policy_ok(b, policy_id)) return fail(ORL_E_INVALID, "policy %d is not defined for this env family", policy_id);
   if (b->step_pending) return fail(ORL_E_INVALID, "orl_batch_policy_step: a step queued by orl_batch_step_async has not been waited for");
   HIPCHK(hipSetDevice(b->device));
-  const size_t B = (size_t)b->P.B;
-  if (b->agent_step && b->P.K <= 8) {
-    launch_agent_step(b, auto_reset ? 1 : 0, policy_id);
-  } else {
-    launch_policy(b, policy_id);
-    if (b->agent_step) launch_agent_step(b, auto_reset ? 1 : 0);
-    else launch_step64(b, auto_reset ? 1 : 0, 1, -1);
-  }
-  bool any = false;
-  if (actions_out) { HIPCHK(hipMemcpyAsync(actions_out, b->P.actions, B * 4 * sizeof(int), hipMemcpyDeviceToHost, b->stream)); any = true; }
-  if (reward_out) { HIPCHK(hipMemcpyAsync(reward_out, b->P.reward, B * sizeof(double), hipMemcpyDeviceToHost, b->stream)); any = true; }
-  if (done_out) { HIPCHK(hipMemcpyAsync(done_out, b->P.done, B, hipMemcpyDeviceToHost, b->stream)); any = true; }
-  if (info_out) { HIPCHK(hipMemcpyAsync(info_out, b->P.info, B * b->P.n_info * sizeof(double), hipMemcpyDeviceToHost, b->stream)); any = true; }
-  if (obs_out && b->P.obs_dim) { HIPCHK(hipMemcpyAsync(obs_out, b->P.obs, B * b->P.obs_dim * sizeof(double), hipMemcpyDeviceToHost, b->stream)); any = true; }
-  if (any) return report_flags(b);  // synchronises
-  return ORL_OK;
+  queue_step(b, auto_reset, policy_id);
+  const int any = queue_results(b, actions_out, obs_out, reward_out, done_out, info_out);
+  return any > 0 ? report_flags(b) : any;  // (report_flags synchronises)
 }
 ORL_ABI_CATCH_INT
 
@@ -1247,7 +1161,7 @@ extern "C" int orl_batch_observation(orl_batch* b, double* obs_out) try {
   if (!b || !obs_out) return fail(ORL_E_INVALID, "null argument");
   if (!b->P.obs_dim) return fail(ORL_E_INVALID, "this env family has no array observation");
   HIPCHK(hipSetDevice(b->device));
-  launch_obs(b, 0);
+  ORL_LAUNCH(obs, b, 0);
   HIPCHK(hipMemcpyAsync(obs_out, b->P.obs, (size_t)b->P.B * b->P.obs_dim * sizeof(double), hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
   HIPCHK(hipGetLastError());
@@ -1259,13 +1173,7 @@ extern "C" int orl_batch_get_obs_f32(orl_batch* b, float* obs_out) try {
   if (!b || !obs_out) return fail(ORL_E_INVALID, "null argument");
   if (!b->P.obs_dim) return fail(ORL_E_INVALID, "this env family has no array observation");
   HIPCHK(hipSetDevice(b->device));
-  const i64 n = b->P.B * b->P.obs_dim;
-  if (!b->obs_f32) {
-    HIPCHK(hipMalloc((void**)&b->obs_f32, (size_t)n * sizeof(float) + 64));
-    b->allocs.push_back(b->obs_f32);
-  }
-  hipLaunchKernelGGL(k_cast_f32, dim3(2048), dim3(256), 0, b->stream, b->P.obs, b->obs_f32, n);
-  HIPCHK(hipMemcpyAsync(obs_out, b->obs_f32, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+  if (const int rc = queue_obs_f32(b, obs_out)) return rc;
   HIPCHK(hipStreamSynchronize(b->stream));
   HIPCHK(hipGetLastError());
   return ORL_OK;
@@ -1301,7 +1209,7 @@ extern "C" int orl_batch_action_mask(orl_batch* b, int layout, uint8_t* out) try
     HIPCHK(hipMalloc((void**)&buf, (size_t)(B * (int64_t)pitch)));
     b->allocs.push_back(buf);
   }
-  if (launch_action_mask(b, layout, buf, pitch))
+  if (ORL_LAUNCH(action_mask, b, layout, buf, pitch))
     return fail(ORL_E_INVALID, "action masks of k = %d paths x %d columns exceed the kernel's LDS budget", b->P.K, dim - 1);
   HIPCHK(hipGetLastError());
   b->mask_last = layout;
@@ -1392,11 +1300,6 @@ extern "C" int orl_batch_get_info_rows(orl_batch* b, const int64_t* env_index, i
 }
 ORL_ABI_CATCH_INT
 
-// The logs of a launch of the persistent kernel (deferred statistics: 24 bytes per env-step, DevParams::slog; rows-deferred forms:
-// 16 bytes per provision / release, DevParams::elog), allocated by the first device-resident run and sized for the launches that
-// run makes — `chunk` steps each, a wavefront that left a launch early catching up over at most two chunks — instead of the 256
-// steps' worth every batch used to get at creation (404 MB per 65 536-env batch whether it ever ran a device loop or not).  Each
-// log stays below 1 GiB: larger batches run shorter launches.  A later run with longer launches replaces them.
 template <typename T> static void dfree(orl_batch* b, T** p) {
   if (!*p) return;
   for (size_t i = 0; i < b->allocs.size(); i++)
@@ -1404,61 +1307,135 @@ template <typename T> static void dfree(orl_batch* b, T** p) {
   hipFree(*p);
   *p = nullptr;
 }
-static int ensure_logs(orl_batch* b, int64_t n_steps, int* chunk_io) {
+// The logs the plan of a run asks for (run_plan, orl_run_plan.h), allocated by the first device-resident run that needs them and
+// replaced when a later run needs longer ones; the event log and what goes with it only for the rows-deferred forms.  The
+// capacities are raised only when every buffer is there: after a failed allocation the batch has no logs, and the next run asks again.
+static int ensure_logs(orl_batch* b, const RunPlan& plan) {
   DevParams& P = b->P;
-  if (!b->persist || !orl_persist_deferred(P.env_type)) return ORL_OK;
-  const size_t B = (size_t)P.B;
-  int chunk = *chunk_io;
-  size_t want = (n_steps <= chunk) ? (size_t)(n_steps > 0 ? n_steps : 1) : (size_t)2 * chunk;
-  const size_t per_step = (size_t)ORL_SLOG_ROW_WORDS * 8 * B;
-  size_t most = ((size_t)1 << 30) / per_step;
-  most = most > 256 ? 256 : (most < 2 ? 2 : most);
-  if (want > most) want = most;
-  if (want < 2) want = 2;
-  if (const char* lv = getenv("ORL_LOG_CAP")) { const int v = atoi(lv); if (v >= 2 && v <= 256) want = (size_t)v; }  // tests
-  if ((size_t)b->log_cap < want) {
-    HIPCHK(hipStreamSynchronize(b->stream));
-    if (b->stream2) HIPCHK(hipStreamSynchronize(b->stream2));
-    dfree(b, &P.slog);
-    dfree(b, &P.elog);
-    dfree(b, &P.ssum);
-    int rc = dalloc(b, &P.slog, (want + 1) * (size_t)ORL_SLOG_ROW_WORDS * B);
-    if (rc) return rc;
-    if (!P.log_n) {
-      rc = dalloc(b, &P.log_n, (B + 7) / 8 + 16);
-      if (rc) return rc;
-      // (on the batch's stream: it is non-blocking, so a memset on the null stream is NOT ordered in front of the launch that writes
-      // log_n — the first run of a batch could have its first launch's step counts zeroed behind the kernel and its replay skipped:
-      // seen once in ~5 runs of the three-thread shard test)
-      HIPCHK(hipMemsetAsync(P.log_n, 0, ((B + 7) / 8 + 16) * sizeof(int), b->stream));
-    }
-    P.log_cap = (int)want;
-    P.log_stride = (i64)B;
-    b->log_cap = (int)want;
-    // events: a step logs its provision and its releases, two per step on average; a wavefront whose envs' logs cannot take
-    // another step stops early like one that used up the statistics log
-    if (P.env_type != ENV_RMCSA && P.E <= 64) {
-      size_t ecap = 3 * want + 40, emost = ((size_t)1 << 30) / (32 * B);
-      if (emost < 80) emost = 80;
-      if (ecap > emost) ecap = emost;
-      if (const char* ev = getenv("ORL_ELOG_CAP")) { const int v = atoi(ev); if (v >= 34 && v <= 4096) ecap = (size_t)v; }  // tests: wavefronts stop for a full event log
-      rc = dalloc(b, &P.elog, 2 * ecap * B);
-      if (rc) return rc;
-      if (!P.elog_n) {
-        rc = dalloc(b, &P.elog_n, B + 16);
-        if (rc) return rc;
-        rc = dalloc(b, &P.bitmap0, B * P.bm_words);
-        if (rc) return rc;
-      }
-      P.elog_cap = (int)ecap;
-    }
-    // (allocated for every family: k_stats names it in an expression the compiler may evaluate on both sides of a select)
-    rc = dalloc(b, &P.ssum, (want + 1) * B);
-    if (rc) return rc;
+  if (P.log_cap >= plan.log_cap && P.elog_cap >= plan.elog_cap) return ORL_OK;
+  const size_t B = (size_t)P.B, cap = (size_t)plan.log_cap, ecap = (size_t)plan.elog_cap;
+  HIPCHK(hipStreamSynchronize(b->stream));
+  if (b->stream2) HIPCHK(hipStreamSynchronize(b->stream2));
+  dfree(b, &P.slog);
+  dfree(b, &P.elog);
+  dfree(b, &P.ssum);
+  P.log_cap = P.elog_cap = 0;
+  int rc = dalloc(b, &P.slog, (cap + 1) * (size_t)ORL_SLOG_ROW_WORDS * B);
+  if (!rc && !P.log_n) {
+    rc = dalloc(b, &P.log_n, (B + 7) / 8 + 16);
+    // (on the batch's stream: it is non-blocking, so a memset on the null stream is NOT ordered in front of the launch that writes
+    // log_n — the first run of a batch could have its first launch's step counts zeroed behind the kernel and its replay skipped:
+    // seen once in ~5 runs of the three-thread shard test)
+    if (!rc) HIPCHK(hipMemsetAsync(P.log_n, 0, ((B + 7) / 8 + 16) * sizeof(int), b->stream));
   }
-  // (a launch logs at most log_cap steps per wavefront, a straggler up to two chunks)
-  if (n_steps > b->log_cap && chunk > b->log_cap / 2) chunk = b->log_cap / 2 > 0 ? b->log_cap / 2 : 1;
-  *chunk_io = chunk;
+  if (!rc && ecap) {
+    rc = dalloc(b, &P.elog, 2 * ecap * B);
+    if (!rc && !P.elog_n) rc = dalloc(b, &P.elog_n, B + 16);
+    if (!rc && !P.bitmap0) rc = dalloc(b, &P.bitmap0, B * P.bm_words);
+    if (!rc) rc = dalloc(b, &P.ssum, (cap + 1) * B);
+  }
+  if (rc) {
+    (void)hipGetLastError();  // (reported here: the next call does not meet it again)
+    return rc;
+  }
+  P.log_cap = (int)cap;
+  P.log_stride = (i64)B;
+  P.elog_cap = (int)ecap;
+  return ORL_OK;
+}
+
+// ---- device-resident runs: one function per mode of orl_batch_run -------------------------------------------------------
+// Each queues its launches behind ev0, records ev1, waits (run_wait) and fills its part of the statistics.
+static int run_wait(orl_batch* b, int64_t n_steps, orl_run_stats* stats) {
+  HIPCHK(hipStreamSynchronize(b->stream));
+  HIPCHK(hipGetLastError());
+  if (stats) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+    memset(stats, 0, sizeof *stats);
+    stats->ms_total = ms;
+    stats->launches = n_steps;
+  }
+  return ORL_OK;
+}
+
+// The persistent kernel.  `flags`: the OR of the env flag words, which the last launch of the run reduces itself (n_steps > 0).
+static int run_persist(orl_batch* b, int policy_id, int64_t n_steps, orl_run_stats* stats, unsigned int* flags) {
+  // The run is cut into chunks of steps: a wavefront that had to leave its loop for the serial tail resumes in the next
+  // launch and is at most one chunk behind (left to one launch per run, it would finish its remaining steps alone on
+  // the GPU: 3 000-step runs measured 5.6e8 env-steps/s against 6.3e8 for 100-step runs).  No host synchronisation
+  // between chunks; after the last one k_finish2 finalises the state and reduces the flags, and ONE 8-byte copy tells
+  // the host whether stragglers are left (then: relaunch) and what the envs flagged.
+  const PersistOverrides pov = persist_overrides_from_env();
+  const bool use_spec = persist_use_spec(b->spec_launch != nullptr, pov);
+  const PersistChoice ch = persist_choose(b->P, use_spec, pov);  // for the WHOLE batch: a run in two halves launches the same kernel on both
+  const RunPlan plan = run_plan(b->P, ch, b->n_cu, n_steps, b->P.log_cap, b->run_base, b->wg_dirty, run_overrides_from_env());
+  // (in front of everything that marks the run as begun: a batch that could not get its logs still answers orl_batch_get_state)
+  if (const int rc = ensure_logs(b, plan)) return rc;
+  const i64 n_wg = (b->P.B + 7) / 8;
+  if (plan.clear_counters) {
+    HIPCHK(hipMemsetAsync(b->d_wg_step, 0, (size_t)n_wg * sizeof(int), b->stream));
+    b->run_base = 0;
+  }
+  b->wg_dirty = true;  // until this run has completed
+  b->run_abandoned = true;
+  const int64_t base = b->run_base;
+  const int parts = plan.parts;
+  const i64 half = plan.half;
+  DevParams view[2] = {env_view(b->P, 0, half, 0), env_view(b->P, parts == 2 ? half : 0, b->P.B - half, 1)};
+  hipStream_t strm[2] = {b->stream, b->stream2};
+  int* wg_step[2] = {b->d_wg_step, b->d_wg_step + half / 8};
+  if (parts == 2) {
+    HIPCHK(hipEventRecord(b->ev_half, b->stream));
+    HIPCHK(hipStreamWaitEvent(b->stream2, b->ev_half, 0));
+  }
+  unsigned int stragglers = 0;
+  b->persist_launches = 0;
+  for (int64_t tgt = 0; tgt < n_steps;) {
+    tgt = (tgt + plan.chunk < n_steps) ? tgt + plan.chunk : n_steps;
+    for (int attempt = 0;; attempt++) {
+      b->persist_launches++;
+      unsigned int* cnt[2] = {nullptr, nullptr};  // the slot each half's launch counts into; it clears the other one
+      // the launch that reaches the end of the run finishes the state itself (pending network-compactness update, flags:
+      // DevParams::persist_finish); only a relaunch for stragglers — wavefronts that left that launch with releases still
+      // to do in place — is followed by k_finish2, which does the same for every env in a launch of its own
+      const int finish = (tgt >= n_steps && attempt == 0) ? 1 : 0;
+      for (int p = 0; p < parts; p++) {
+        cnt[p] = b->d_unfinished + 8 * p + 4 * b->un_slot[p];
+        ORL_LAUNCH(persist, b, view[p], ch, use_spec, strm[p], policy_id, (int)(base + tgt), wg_step[p], cnt[p],
+                   b->d_unfinished + 8 * p + 4 * (b->un_slot[p] ^ 1), finish);
+        b->un_slot[p] ^= 1;
+      }
+      if (tgt < n_steps) break;  // stragglers catch up in the next chunk's launch
+      if (attempt > 0)
+        for (int p = 0; p < parts; p++)  // (harmless for a straggler: it does what that env's next control phase would do first)
+          hipLaunchKernelGGL(k_finish2, dim3((unsigned)((view[p].B + 255) / 256)), dim3(256), 0, strm[p], view[p], 1, cnt[p] + 1);
+      if (parts == 2) {
+        HIPCHK(hipEventRecord(b->ev_half, b->stream2));
+        HIPCHK(hipStreamWaitEvent(b->stream, b->ev_half, 0));
+      }
+      HIPCHK(hipEventRecord(b->ev1, b->stream));
+      unsigned int* both = b->h_tail;
+      HIPCHK(hipMemcpyAsync(both, b->d_unfinished, 16 * sizeof(unsigned int), hipMemcpyDeviceToHost, b->stream));
+      HIPCHK(hipStreamSynchronize(b->stream));
+      const unsigned int* c0 = both + (cnt[0] - b->d_unfinished);
+      const unsigned int* c1 = parts == 2 ? both + (cnt[1] - b->d_unfinished) : nullptr;
+      stragglers = c0[0] + (c1 ? c1[0] : 0);
+      *flags |= c0[1] | (c1 ? c1[1] : 0);  // (accumulated: k_finish2 clears a reported flag in the records, a relaunch would lose it)
+      if (!stragglers) break;
+    }
+  }
+  if (n_steps == 0) HIPCHK(hipEventRecord(b->ev1, b->stream));
+  b->run_base = base + n_steps;  // every workgroup stands here now
+  b->wg_dirty = false;
+  b->run_abandoned = false;
+  if (const int rc = run_wait(b, n_steps, stats)) return rc;
+  if (stats && n_steps > 0) {  // the whole run was (re)launches of one kernel
+    stats->n_kernels = 1;
+    stats->launches = b->persist_launches > 0 ? b->persist_launches : 1;  // chunks of ORL_PERSIST_CHUNK steps
+    stats->ms_kernel[0] = stats->ms_total / (double)stats->launches;      // average duration of one launch (+ its k_rel_tail)
+    snprintf(stats->kernel_name[0], sizeof stats->kernel_name[0], "k_persist");
+  }
   return ORL_OK;
 }
 
@@ -1468,173 +1445,88 @@ struct EventPool {
   ~EventPool() { for (auto& e : ev) hipEventDestroy(e); }
 };
 
+// time_kernels == 2: the stand-alone slot scan and the per-env step kernel, an event pair (of `pool`, 3 per step) around each
+static int run_timed_pair(orl_batch* b, int policy_id, int64_t n_steps, const EventPool& pool, orl_run_stats* stats) {
+  for (int64_t s = 0; s < n_steps; s++) {
+    HIPCHK(hipEventRecord(pool.ev[3 * s], b->stream));
+    ORL_LAUNCH(policy, b, policy_id);
+    HIPCHK(hipEventRecord(pool.ev[3 * s + 1], b->stream));
+    ORL_LAUNCH_MAPS(step64, b, 1, 0, -1);
+    HIPCHK(hipEventRecord(pool.ev[3 * s + 2], b->stream));
+  }
+  HIPCHK(hipEventRecord(b->ev1, b->stream));
+  if (const int rc = run_wait(b, n_steps, stats)) return rc;
+  if (stats && n_steps > 0) {
+    double sp = 0, ss = 0;
+    for (int64_t s = 0; s < n_steps; s++) {
+      float a = 0, c2 = 0;
+      HIPCHK(hipEventElapsedTime(&a, pool.ev[3 * s], pool.ev[3 * s + 1]));
+      HIPCHK(hipEventElapsedTime(&c2, pool.ev[3 * s + 1], pool.ev[3 * s + 2]));
+      sp += a; ss += c2;
+    }
+    stats->ms_policy = sp / (double)n_steps;
+    stats->ms_step = ss / (double)n_steps;
+    stats->launches = 2 * n_steps;
+  }
+  return ORL_OK;
+}
+
+// the per-env kernel with the slot scan inside it (one launch per policy + step), or — ORL_ALT_IMPLS builds — the
+// two-kernel form of the persistent kernel's phases; time_each (time_kernels == 1): an event after every kernel
+static int run_per_step(orl_batch* b, int policy_id, int64_t n_steps, bool time_each, orl_run_stats* stats) {
+  TkRec tk;
+  struct TkGuard { TkRec& t; orl_batch* b; ~TkGuard() { b->tk = nullptr; for (auto& e : t.ev) hipEventDestroy(e); } } tkg{tk, b};
+  for (int64_t s = 0; s < n_steps; s++) {
+    if (time_each) { b->tk = &tk; ORL_TK(b, ""); }
+    if (b->two_kernel) ORL_LAUNCH_MAPS(step2, b, policy_id);
+    // (QoSConstrainedRA batches that step through k_agent_qos: the stand-alone scan + that kernel, two launches that together
+    // take half the time of k_step with the scan inside it — 65 536 envs 129 against 233 us)
+    else if (b->agent_step && b->P.env_type == ENV_QOS) ORL_LAUNCH_MAPS(agent_step, b, 1, policy_id);
+    else ORL_LAUNCH_MAPS(step64, b, 1, 0, policy_id);
+    b->tk = nullptr;
+  }
+  if (b->two_kernel) launch_finish2(b, 1);
+  HIPCHK(hipEventRecord(b->ev1, b->stream));
+  if (const int rc = run_wait(b, n_steps, stats)) return rc;
+  if (stats && time_each && n_steps > 0) {
+    const size_t per = tk.ev.size() / (size_t)n_steps;  // 1 start mark + one event per kernel
+    const int nk = (int)per - 1 < ORL_MAX_STEP_KERNELS ? (int)per - 1 : ORL_MAX_STEP_KERNELS;
+    stats->n_kernels = nk;
+    stats->launches = (int64_t)(per - 1) * n_steps;
+    for (int k = 0; k < nk; k++) {
+      double sum = 0;
+      for (int64_t s = 0; s < n_steps; s++) {
+        float a = 0;
+        HIPCHK(hipEventElapsedTime(&a, tk.ev[(size_t)s * per + k], tk.ev[(size_t)s * per + k + 1]));
+        sum += a;
+      }
+      stats->ms_kernel[k] = sum / (double)n_steps;
+      snprintf(stats->kernel_name[k], sizeof stats->kernel_name[k], "%s", tk.name[k + 1]);
+    }
+  }
+  return ORL_OK;
+}
+
 extern "C" int orl_batch_run(orl_batch* b, int policy_id, int64_t n_steps, int time_kernels, orl_run_stats* stats) try {
   if (!b || n_steps < 0) return fail(ORL_E_INVALID, "bad argument");
   if (n_steps > INT_MAX) return fail(ORL_E_INVALID, "n_steps must be <= %d per call", INT_MAX);
   if (!policy_ok(b, policy_id)) return fail(ORL_E_INVALID, "policy %d is not defined for this env family", policy_id);
   HIPCHK(hipSetDevice(b->device));
   EventPool pool;
-  TkRec tk;
-  struct TkGuard { TkRec& t; orl_batch* b; ~TkGuard() { b->tk = nullptr; for (auto& e : t.ev) hipEventDestroy(e); } } tkg{tk, b};
   if (time_kernels == 2) {
     pool.ev.resize((size_t)n_steps * 3);
     for (auto& e : pool.ev) HIPCHK(hipEventCreate(&e));
   }
   HIPCHK(hipStreamSynchronize(b->stream));
   HIPCHK(hipEventRecord(b->ev0, b->stream));
-  unsigned int tail[2] = {0, 0};  // straggler workgroups, OR of the env flags
-  bool have_flags = false;
-  if (!time_kernels && b->persist) {
-    // The run is cut into chunks of steps: a wavefront that had to leave its loop for the serial tail resumes in the next
-    // launch and is at most one chunk behind (left to one launch per run, it would finish its remaining steps alone on
-    // the GPU: 3 000-step runs measured 5.6e8 env-steps/s against 6.3e8 for 100-step runs).  No host synchronisation
-    // between chunks; after the last one k_finish2 finalises the state and reduces the flags, and ONE 8-byte copy tells
-    // the host whether stragglers are left (then: relaunch) and what the envs flagged.
-    const unsigned n_wg = (unsigned)((b->P.B + 7) / 8);
-    // d_wg_step counts steps since run_base was 0: between runs every workgroup stands at run_base, so a run needs no clearing
-    // (a fill kernel in front of every run: ~1 % of a 20-step run)
-    int64_t base_limit = (int64_t)1 << 30;  // the counters are ints
-    if (const char* lv = getenv("ORL_RUN_BASE_LIMIT")) { const long long v = atoll(lv); if (v >= 1) base_limit = v; }  // tests
-    if (b->wg_dirty || b->run_base + n_steps > base_limit) {
-      HIPCHK(hipMemsetAsync(b->d_wg_step, 0, n_wg * sizeof(int), b->stream));
-      b->run_base = 0;
-    }
-    b->wg_dirty = true;  // until this run has completed
-    b->run_abandoned = true;
-    const int64_t base = b->run_base;
-    // (launches of 128 steps: every launch boundary costs a wavefront its window fill / write-back and a cold first step —
-    // cfg2 1.265e9 with 64-step launches, 1.295e9 with 128; with the bit-word sink a wavefront practically never has to
-    // leave its loop early, so longer launches leave no stragglers behind)
-    int chunk = 128;
-    if (const char* cv = getenv("ORL_PERSIST_CHUNK")) { int v = atoi(cv); if (v >= 1) chunk = v; }
-    // (deferred statistics: the logs a launch writes, allocated on first use; a launch logs at most log_cap steps per wavefront)
-    { const int lrc = ensure_logs(b, n_steps, &chunk); if (lrc) return lrc; }
-    // A launch occupies the GPU in rounds of `resident` wavefronts, and a last round that is not full leaves CUs idle until
-    // the launch ends (cfg2: 8 192 wavefronts over 3 072 resident = 2.67 rounds, 11 % of the machine-time lost).  When the
-    // rounds do not come out even, the batch runs as two halves on two streams: the tail of one half's launch overlaps the
-    // other half's next one.  (ORL_PERSIST_PARTS=1|2 forces either.)
-    int parts = 1;
-    {
-      const int resident = persist_resident(b);
-      const double rounds = (double)n_wg / (double)(resident > 0 ? resident : 1);
-      // (a run of a single chunk has no next launch to overlap with: one part)
-      if (n_steps > chunk && n_wg >= 2048 && rounds > 1.0) parts = 2;
-      if (const char* pv = getenv("ORL_PERSIST_PARTS")) { int v = atoi(pv); if (v == 1 || (v == 2 && n_wg >= 2)) parts = v; }
-    }
-    const i64 half = parts == 2 ? (i64)((n_wg + 1) / 2) * 8 : b->P.B;
-    DevParams view[2] = {env_view(b->P, 0, parts == 2 ? half : b->P.B, 0), env_view(b->P, parts == 2 ? half : 0, parts == 2 ? b->P.B - half : 0, 1)};
-    hipStream_t strm[2] = {b->stream, b->stream2};
-    int* wg_step[2] = {b->d_wg_step, b->d_wg_step + half / 8};
-    if (parts == 2) {
-      HIPCHK(hipEventRecord(b->ev_half, b->stream));
-      HIPCHK(hipStreamWaitEvent(b->stream2, b->ev_half, 0));
-    }
-    b->persist_launches = 0;
-    for (int64_t tgt = 0; tgt < n_steps;) {
-      tgt = (tgt + chunk < n_steps) ? tgt + chunk : n_steps;
-      for (int attempt = 0;; attempt++) {
-        b->persist_launches++;
-        unsigned int* cnt[2] = {nullptr, nullptr};  // the slot each half's launch counts into; it clears the other one
-        // the launch that reaches the end of the run finishes the state itself (pending network-compactness update, flags:
-        // DevParams::persist_finish); only a relaunch for stragglers — wavefronts that left that launch with releases still
-        // to do in place — is followed by k_finish2, which does the same for every env in a launch of its own
-        const int finish = (tgt >= n_steps && attempt == 0) ? 1 : 0;
-        for (int p = 0; p < parts; p++) {
-          cnt[p] = b->d_unfinished + 8 * p + 4 * b->un_slot[p];
-          launch_persist(b, view[p], strm[p], policy_id, (int)(base + tgt), wg_step[p], cnt[p], b->d_unfinished + 8 * p + 4 * (b->un_slot[p] ^ 1), finish);
-          b->un_slot[p] ^= 1;
-        }
-        if (tgt < n_steps) break;  // stragglers catch up in the next chunk's launch
-        if (attempt > 0)
-          for (int p = 0; p < parts; p++)  // (harmless for a straggler: it does what that env's next control phase would do first)
-            hipLaunchKernelGGL(k_finish2, dim3((unsigned)((view[p].B + 255) / 256)), dim3(256), 0, strm[p], view[p], 1, cnt[p] + 1);
-        if (parts == 2) {
-          HIPCHK(hipEventRecord(b->ev_half, b->stream2));
-          HIPCHK(hipStreamWaitEvent(b->stream, b->ev_half, 0));
-        }
-        HIPCHK(hipEventRecord(b->ev1, b->stream));
-        unsigned int* both = b->h_tail;
-        HIPCHK(hipMemcpyAsync(both, b->d_unfinished, 16 * sizeof(unsigned int), hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-        const unsigned int* c0 = both + (cnt[0] - b->d_unfinished);
-        const unsigned int* c1 = parts == 2 ? both + (cnt[1] - b->d_unfinished) : nullptr;
-        tail[0] = c0[0] + (c1 ? c1[0] : 0);
-        tail[1] |= c0[1] | (c1 ? c1[1] : 0);  // (accumulated: k_finish2 clears a reported flag in the records, a relaunch would lose it)
-        if (!tail[0]) break;
-      }
-    }
-    if (n_steps == 0) HIPCHK(hipEventRecord(b->ev1, b->stream));
-    have_flags = n_steps > 0;
-    b->run_base = base + n_steps;  // every workgroup stands here now
-    b->wg_dirty = false;
-    b->run_abandoned = false;
-  } else if (time_kernels == 2) {
-    for (int64_t s = 0; s < n_steps; s++) {
-      HIPCHK(hipEventRecord(pool.ev[3 * s], b->stream));
-      launch_policy(b, policy_id);
-      HIPCHK(hipEventRecord(pool.ev[3 * s + 1], b->stream));
-      launch_step64(b, 1, 0, -1);
-      HIPCHK(hipEventRecord(pool.ev[3 * s + 2], b->stream));
-    }
-  } else {
-    // the per-env kernel with the slot scan inside it (one launch per policy + step), or — ORL_ALT_IMPLS builds — the
-    // two-kernel form of the persistent kernel's phases; time_kernels == 1: an event after every kernel
-    for (int64_t s = 0; s < n_steps; s++) {
-      if (time_kernels == 1) { b->tk = &tk; ORL_TK(b, ""); }
-      if (b->two_kernel) launch_step2(b, policy_id);
-      // (QoSConstrainedRA batches that step through k_agent_qos: the stand-alone scan + that kernel, two launches that together
-      // take half the time of k_step with the scan inside it — 65 536 envs 129 against 233 us)
-      else if (b->agent_step && b->P.env_type == ENV_QOS) launch_agent_step(b, 1, policy_id);
-      else launch_step64(b, 1, 0, policy_id);
-      b->tk = nullptr;
-    }
-    if (b->two_kernel) launch_finish2(b, 1);
-  }
-  if (!(!time_kernels && b->persist)) HIPCHK(hipEventRecord(b->ev1, b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  HIPCHK(hipGetLastError());
-  if (stats) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-    memset(stats, 0, sizeof *stats);
-    stats->ms_total = ms;
-    stats->launches = n_steps;
-    if (!time_kernels && b->persist && n_steps > 0) {  // the whole run was (re)launches of one kernel
-      stats->n_kernels = 1;
-      stats->launches = b->persist_launches > 0 ? b->persist_launches : 1;  // chunks of ORL_PERSIST_CHUNK steps
-      stats->ms_kernel[0] = ms / (double)stats->launches;                   // average duration of one launch (+ its k_rel_tail)
-      snprintf(stats->kernel_name[0], sizeof stats->kernel_name[0], "k_persist");
-    }
-    if (time_kernels == 2 && n_steps > 0) {
-      double sp = 0, ss = 0;
-      for (int64_t s = 0; s < n_steps; s++) {
-        float a = 0, c2 = 0;
-        HIPCHK(hipEventElapsedTime(&a, pool.ev[3 * s], pool.ev[3 * s + 1]));
-        HIPCHK(hipEventElapsedTime(&c2, pool.ev[3 * s + 1], pool.ev[3 * s + 2]));
-        sp += a; ss += c2;
-      }
-      stats->ms_policy = sp / (double)n_steps;
-      stats->ms_step = ss / (double)n_steps;
-      stats->launches = 2 * n_steps;
-    }
-    if (time_kernels == 1 && n_steps > 0) {
-      const size_t per = tk.ev.size() / (size_t)n_steps;  // 1 start mark + one event per kernel
-      const int nk = (int)per - 1 < ORL_MAX_STEP_KERNELS ? (int)per - 1 : ORL_MAX_STEP_KERNELS;
-      stats->n_kernels = nk;
-      stats->launches = (int64_t)(per - 1) * n_steps;
-      for (int k = 0; k < nk; k++) {
-        double sum = 0;
-        for (int64_t s = 0; s < n_steps; s++) {
-          float a = 0;
-          HIPCHK(hipEventElapsedTime(&a, tk.ev[(size_t)s * per + k], tk.ev[(size_t)s * per + k + 1]));
-          sum += a;
-        }
-        stats->ms_kernel[k] = sum / (double)n_steps;
-        snprintf(stats->kernel_name[k], sizeof stats->kernel_name[k], "%s", tk.name[k + 1]);
-      }
-    }
-  }
-  return have_flags ? flags_to_rc(b, tail[1]) : report_flags(b);
+  const bool persistent = !time_kernels && b->persist;
+  unsigned int flags = 0;
+  int rc;
+  if (persistent) rc = run_persist(b, policy_id, n_steps, stats, &flags);
+  else if (time_kernels == 2) rc = run_timed_pair(b, policy_id, n_steps, pool, stats);
+  else rc = run_per_step(b, policy_id, n_steps, time_kernels == 1, stats);
+  if (rc) return rc;
+  return (persistent && n_steps > 0) ? flags_to_rc(b, flags) : report_flags(b);
 }
 ORL_ABI_CATCH_INT
 
@@ -1925,13 +1817,13 @@ extern "C" int orl_batch_spec_flags(orl_batch* b, char* buf, int capacity) try {
   return spec_flags(b->P, b->wt, buf, capacity);
 }
 catch (...) { return 0; }
-// the sizes of a batch of n_envs envs of this configuration, without a device; false: not one the persistent kernel serves
-static bool persist_sizes_for(const orl_env_config* cfg, const orl_topology_desc* topo, int64_t n_envs, DevParams& P, int* wt) {
+// the sizes of a batch of n_envs envs of this configuration, without a device; false: not a configuration
+static bool sizes_for(const orl_env_config* cfg, const orl_topology_desc* topo, int64_t n_envs, DevParams& P, int* wt) {
   if (!cfg || !topo || n_envs < 1) return false;
   if (cfg->struct_size != sizeof(orl_env_config) || cfg->env_type < 0 || cfg->env_type > ORL_ENV_QOS || !(cfg->lambda_arrival > 0) || !(cfg->lambda_holding > 0)) return false;
   memset(&P, 0, sizeof P);
   derive_sizes(cfg, topo->n_nodes, topo->n_links, topo->k_paths, topo->max_hops, topo->n_modulations, n_envs, P, wt);
-  return pipeline_applies(cfg, P);
+  return true;
 }
 extern "C" int orl_spec_flags_for(const orl_env_config* cfg, const orl_topology_desc* topo, char* buf, int capacity) {
   return orl_spec_flags_for_batch(cfg, topo, (int64_t)1 << 20, buf, capacity);
@@ -1941,19 +1833,34 @@ extern "C" int orl_spec_flags_for_batch(const orl_env_config* cfg, const orl_top
   buf[0] = 0;
   DevParams P;
   int wt = 1;
-  if (!persist_sizes_for(cfg, topo, n_envs, P, &wt)) return 0;
+  if (!sizes_for(cfg, topo, n_envs, P, &wt) || !pipeline_applies(cfg, P)) return 0;
   return spec_flags(P, wt, buf, capacity);
 }
 catch (...) { return 0; }
 extern "C" int orl_debug_persist_choice(const orl_env_config* cfg, const orl_topology_desc* topo, int64_t n_envs, int tuned, int32_t* out) try {
   DevParams P;
   int wt = 1;
-  if (!out || !persist_sizes_for(cfg, topo, n_envs, P, &wt)) return 0;
+  if (!out || !sizes_for(cfg, topo, n_envs, P, &wt) || !pipeline_applies(cfg, P)) return 0;
   const PersistChoice ch = persist_choose(P, tuned != 0, persist_overrides_from_env());
   const PersistForm& F = kPersistForms[ch.form];
   const int32_t v[9] = {ch.form, F.lds_arg, F.waves, ch.rw, ch.inner, ch.evl, (int32_t)ch.lds, (int32_t)ch.launch_lds, ch.wgs_per_cu};
   memcpy(out, v, sizeof v);
   return 9;
+}
+catch (...) { return 0; }
+extern "C" int orl_debug_run_plan(const orl_env_config* cfg, const orl_topology_desc* topo, int64_t n_envs, int64_t n_steps, int tuned, int n_cu,
+                                  int log_cap_have, int64_t run_base, int wg_dirty, int32_t* out) try {
+  DevParams P;
+  int wt = 1;
+  if (!out || n_steps < 0 || !sizes_for(cfg, topo, n_envs, P, &wt)) return 0;
+  const StepRoute rt = step_route(P, pipeline_applies(cfg, P), step_overrides_from_env());
+  RunPlan pl = {};
+  if (rt.persist)
+    pl = run_plan(P, persist_choose(P, tuned != 0, persist_overrides_from_env()), n_cu, n_steps, log_cap_have, run_base, wg_dirty != 0, run_overrides_from_env());
+  const int32_t v[11] = {rt.persist, rt.two_kernel, rt.agent_step, rt.item_masks, rt.rel_limit, pl.chunk, pl.parts, (int32_t)pl.half, pl.log_cap, pl.elog_cap,
+                         pl.clear_counters ? 1 : 0};
+  memcpy(out, v, sizeof v);
+  return 11;
 }
 catch (...) { return 0; }
 extern "C" int orl_batch_load_spec(orl_batch* b, const char* so_path) try {
@@ -2109,7 +2016,7 @@ extern "C" int orl_batch_set_state(orl_batch* b, const void* in) try {
   if (b->P.svc_cnt) HIPCHK(hipMemsetAsync(b->P.svc_cnt, 0, (size_t)((b->P.B + 7) / 8) * 64 * sizeof(int), b->stream));
   b->run_abandoned = false;  // (the step counters of an abandoned run are cleared by the next run: wg_dirty stays set)
   slot_maps_change(b, b->stream);
-  if (b->P.obs_dim) launch_obs(b, 0);
+  if (b->P.obs_dim) ORL_LAUNCH(obs, b, 0);
   HIPCHK(hipStreamSynchronize(b->stream));
   return ORL_OK;
 }
@@ -2120,11 +2027,7 @@ extern "C" int orl_batch_debug_prof(orl_batch* b, uint64_t* out48, int reset) tr
   if (!b || !out48) return fail(ORL_E_INVALID, "bad argument");
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());
-  int rc = 0;
-#define CALL(WW) rc = orl_launch::prof_read<WW>((unsigned long long*)out48, reset)
-  ORL_DISPATCH_W(b, CALL)
-#undef CALL
-  return rc ? fail(ORL_E_HIP, "reading the profile failed") : ORL_OK;
+  return ORL_LAUNCH(prof_read, (unsigned long long*)out48, reset) ? fail(ORL_E_HIP, "reading the profile failed") : ORL_OK;
 }
 ORL_ABI_CATCH_INT
 extern "C" int orl_batch_debug_persist_spec(orl_batch* b) try {

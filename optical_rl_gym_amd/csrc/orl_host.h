@@ -27,6 +27,8 @@ static inline bool orl_persist_deferred(int env_type) {
          (env_type == orl::ENV_RMSA || env_type == orl::ENV_DEEPRMSA || env_type == orl::ENV_RWA || env_type == orl::ENV_RMCSA);
 }
 
+struct PersistChoice;  // orl_persist_form.h
+
 struct orl_topology {
   int device;
   int N, E, K, H, M;
@@ -75,7 +77,6 @@ struct orl_batch {
   int32_t* h_actions = nullptr;    // page-locked [B][4]: where orl_batch_step_async expands the caller's compact action rows
   int step_pending = 0;            // orl_batch_step_async queued a step that orl_batch_step_wait has not collected yet
   unsigned int* h_tail = nullptr;  // page-locked: where the straggler count / flag words of a run land (a pageable target is staged)
-  int log_cap = 0;                 // deferred statistics: steps one launch of k_persist can log per wavefront (0: no log)
   int cache_epoch = 1;             // bumped by every call that may change slot maps outside the persistent kernel (DevParams::row_cache_key)
   long long* gather_idx = nullptr;  // orl_batch_get_info_rows: row indices and gathered rows on the device, grown on demand
   double* gather_out = nullptr;
@@ -119,9 +120,10 @@ template <int W> void policy(orl_batch* b, int pol);                       // st
 template <int W> void step64(orl_batch* b, int auto_reset, int want_info, int fused_policy);  // one wavefront per env
 template <int W> void obs(orl_batch* b, int with_terminal);                // DeepRMSA observation
 template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, int pitch);  // k_action_mask -> out [B][pitch]
-// k_persist over the env range of view VP up to step `target` of this run, then k_rel_tail, on stream st
-template <int W> void persist(orl_batch* b, const orl::DevParams& VP, hipStream_t st, int pol, int target, int* wg_step, unsigned int* unfinished,
-                              unsigned int* clear_next, int finish);  // finish: this launch ends the run (DevParams::persist_finish)
+// k_persist in the form `ch` (the run's choice for the whole batch; use_spec: made for the attached specialisation library) over the
+// env range of view VP up to step `target` of this run, then k_rel_tail, on stream st
+template <int W> void persist(orl_batch* b, const orl::DevParams& VP, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,
+                              int* wg_step, unsigned int* unfinished, unsigned int* clear_next, int finish);  // finish: this launch ends the run (DevParams::persist_finish)
 template <int W> int prof_read(unsigned long long* out48, int reset);      // -DORL_TIMING builds: per-phase cycle sums
 template <int W> void step2(orl_batch* b, int pol);                        // ORL_ALT_IMPLS: k_step_a2 ; k_rows2 ; k_rel_tail
 template <int W> void agent_step(orl_batch* b, int auto_reset, int pol);   // k_agent: one step, actions in P.actions, info / obs written

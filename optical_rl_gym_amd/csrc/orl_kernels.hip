@@ -2246,18 +2246,13 @@ template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, i
   return 0;
 }
 
-// The persistent kernel in the form persist_choose (orl_persist_form.h) takes for the whole batch, over the env range of view VP0.
-template <int W> void persist(orl_batch* b, const DevParams& VP0, hipStream_t st, int pol, int target, int* wg_step, unsigned int* unfinished,
-                              unsigned int* clear_next, int finish) {
+// The persistent kernel in the form `ch` — what persist_choose (orl_persist_form.h) took for the whole batch when the run began:
+// a run in two halves launches the same kernel on both views — over the env range of view VP0.
+template <int W> void persist(orl_batch* b, const DevParams& VP0, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,
+                              int* wg_step, unsigned int* unfinished, unsigned int* clear_next, int finish) {
   DevParams VP = VP0;
   VP.persist_finish = finish;
   dim3 gc((unsigned)((VP.B + 7) / 8)), blk(64);
-  const PersistOverrides ov = persist_overrides_from_env();
-  const bool use_spec = persist_use_spec(b->spec_launch != nullptr, ov);
-  // the form is chosen for the WHOLE batch: a run in two halves launches the same kernel on both views
-  DevParams VC = VP;
-  VC.B = b->P.B;
-  const PersistChoice ch = persist_choose(VC, use_spec, ov);
   const int v = ch.form;
   const PersistForm& F = kPersistForms[v];
   VP.persist_ic = ch.inner;
@@ -2402,7 +2397,7 @@ template void policy<ORL_W>(orl_batch*, int);
 template void step64<ORL_W>(orl_batch*, int, int, int);
 template void obs<ORL_W>(orl_batch*, int);
 template int action_mask<ORL_W>(orl_batch*, int, unsigned char*, int);
-template void persist<ORL_W>(orl_batch*, const DevParams&, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);
+template void persist<ORL_W>(orl_batch*, const DevParams&, const PersistChoice&, bool, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);
 template void step2<ORL_W>(orl_batch*, int);
 template void agent_step<ORL_W>(orl_batch*, int, int);
 

@@ -115,8 +115,8 @@ struct PersistOverrides {
   std::optional<int> wgs_per_cu;      // ORL_PERSIST_WGS_PER_CU: lowers the residency by padding the LDS request (experiments)
   std::optional<int> row_cache_keep;  // ORL_ROW_CACHE_KEEP: 0 = rebuild the row caches at every launch
 };
-// Read where a choice is made — every launch, residency query and flags query — so that a script may change a variable between
-// two runs of one batch.
+// Read where a choice is made — once per device-resident run, and at every flags query — so that a script may change a variable
+// between two runs of one batch (not between two launches of one run: every launch of a run gets the run's one choice).
 static inline PersistOverrides persist_overrides_from_env() {
   PersistOverrides o;
   if (const char* e = getenv("ORL_PERSIST_VARIANT")) o.variant = atoi(e);
@@ -144,7 +144,8 @@ static inline size_t persist_window(const orl::DevParams& VP, int lds_arg, int i
                                     orl_persist_deferred(VP.env_type), rd).total;
 }
 // the rows-deferred forms: single-core families with the statistics deferred, a bit per link in a 64-bit event word, services of
-// at most 63 slots in a 9-bit first slot (the compact sink's own limits), and an event log to write to
+// at most 63 slots in a 9-bit first slot (the compact sink's own limits).  (The event log they write to: the plan of a run asks for
+// one whenever the chosen form is one of them, run_plan / ensure_logs.)
 static inline bool persist_rd_possible(const orl::DevParams& VP) {
   return orl_persist_deferred(VP.env_type) && VP.env_type != orl::ENV_RMCSA && VP.E <= 64 && VP.S <= 512;
 }

@@ -357,6 +357,19 @@ class BatchedOpticalEnv:
         n = lib.orl_debug_persist_choice(C.byref(self._cfg), C.byref(self._desc), int(batch), int(bool(tuned)), out)
         return tuple(out) if n > 0 else None
 
+    RUN_PLAN_FIELDS = ("persist", "two_kernel", "agent_step", "item_masks", "rel_limit", "chunk", "parts", "half", "log_cap", "elog_cap",
+                       "clear_counters")
+
+    def run_plan(self, batch, n_steps, tuned=True, n_cu=256, log_cap_have=0, run_base=0, wg_dirty=False, variant=None):
+        """The step route of a batch of `batch` envs of this configuration and the plan of a device-resident run of `n_steps` steps
+        (include/orl.h, orl_debug_run_plan; no device needed): a tuple in the order of RUN_PLAN_FIELDS, None for a configuration
+        the library refuses."""
+        out = (C.c_int32 * len(self.RUN_PLAN_FIELDS))()
+        lib = _lib.lib(variant) if variant else self.lib
+        n = lib.orl_debug_run_plan(C.byref(self._cfg), C.byref(self._desc), int(batch), int(n_steps), int(bool(tuned)), int(n_cu),
+                                   int(log_cap_have), int(run_base), int(bool(wg_dirty)), out)
+        return tuple(out) if n > 0 else None
+
     def _ck(self, rc):
         _lib.check(rc, self.lib)
 

@@ -438,13 +438,18 @@ def test_pair_form_hand_over_under_jitter(monkeypatch):
         chk(k, "item", x, y)
 
 
-@pytest.mark.parametrize("workload,batch", [("cfg2", 4096), ("cfg2", 20000), ("cfg3", 4096), ("cfg5", 2048)])
-def test_short_statistics_log_and_early_exits(workload, batch, monkeypatch):
+@pytest.mark.parametrize("workload,batch,late_rd", [pytest.param("cfg2", 4096, False, id="cfg2-4096"), pytest.param("cfg2", 20000, False, id="cfg2-20000"),
+                                                    pytest.param("cfg3", 4096, False, id="cfg3-4096"), pytest.param("cfg5", 2048, False, id="cfg5-2048"),
+                                                    pytest.param("cfg2", 20000, True, id="cfg2-20000-late_rd")])
+def test_short_statistics_log_and_early_exits(workload, batch, late_rd, monkeypatch):
     """The statistics log of a launch shortened to 12 steps (ORL_LOG_CAP; launches are then 6 steps long) and the item form limited
     to one release per step: wavefronts that left early catch up over more steps than a launch can log, stop at the end of the log
     and count as unfinished — with the batch of services the row wavefront of a pair has on order, and with services parked, at
     every kind of exit.  Every env against the one-wavefront-per-env kernel (4 096 / 2 048 envs: the two-wavefront form; 20 000:
-    one wavefront per 8 envs)."""
+    one wavefront per 8 envs).
+    late_rd: logs of the default capacity, and ONE batch that runs 200 steps in the library's own form — which leaves it a
+    statistics log long enough for any later run and no event log — and then goes on in the rows-deferred form
+    (ORL_PERSIST_VARIANT=7 set between the two runs): that run has to get its event log although the statistics log is enough."""
     import optical_rl_gym_amd as orl
     from bench import WORKLOADS
 
@@ -452,6 +457,26 @@ def test_short_statistics_log_and_early_exits(workload, batch, monkeypatch):
     kw = dict(kw, episode_length=70)
     seeds = [5 + 11 * i for i in range(batch)]
     out = {}
+    if late_rd:
+        for name in ("wave64", "persist"):
+            force_impl(monkeypatch, name)
+            for k in ("ORL_ITEM_MASKS", "ORL_LOG_CAP", "ORL_ELOG_CAP"):
+                monkeypatch.delenv(k, raising=False)
+            env = orl.make(fam, topology=topo, num_envs=batch, seeds=seeds, **kw)
+            env.run(policy, 200)
+            if name == "persist":
+                assert int(env.lib.orl_batch_debug_persist_form(env._h)) not in (7, 8)
+                force_impl(monkeypatch, "persist_rd")
+            env.run(policy, 110)
+            if name == "persist":
+                assert int(env.lib.orl_batch_debug_persist_form(env._h)) == 7
+            out[name] = [env.counters().copy(), env.services().copy(), env.active().copy(), env.flags().copy(),
+                         env.net_stats_all().copy(), env.link_stats_all().copy(), env.slots_packed().copy()]
+            env.close()
+        chk = _exact("%s %d, own form then rows-deferred" % (workload, batch))
+        for k, (x, y) in enumerate(zip(out["persist"], out["wave64"])):
+            chk(k, "item", x, y)
+        return
     # (persist_rd: the rows-deferred form with the same short statistics log; persist_rd_ev: its EVENT log shortened to 40 events per
     # env and launch instead, so that wavefronts stop because that one is full — Germany50 has more links than an event's link bits:
     # the library's own form runs there)

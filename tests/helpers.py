@@ -1,4 +1,5 @@
-"""Shared helpers for the parity tests: golden-trace loading and trace replay."""
+"""Shared helpers for the parity tests: golden-trace loading and trace replay, the step implementations a test can force, and the
+exact comparison."""
 import glob
 import json
 import os
@@ -184,3 +185,64 @@ def replay_q(env, g, check):
             check(t, "utilization", ls[0], ref[0])
             check(t, "last_update", ls[3], ref[3])
     check(meta["n_steps"], "svc", env.services()[0], g["svc"][meta["n_steps"]])
+
+
+# ---- step implementations -------------------------------------------------------------------------------------------------
+# Device-resident runs go through the persistent kernel (k_persist) wherever it applies, host-driven step() through the
+# one-wavefront-per-env kernel (k_step).  The small parity cases run against every implementation by forcing it
+# (ORL_STEP_IMPL, ORL_PERSIST and ORL_AGENT_STEP are read when a batch is created; the form overrides — ORL_PERSIST_VARIANT,
+# _INNER, _RW — at every launch of the persistent kernel): "wave64" = k_step for everything, "persist" = the default, "split2" = the
+# phases of the persistent kernel as two separate launches (liborlgpu_alt.so, the -DORL_ALT_IMPLS build).
+IMPLS = ["wave64", "split2", "persist", "persist_global", "persist_lds", "agent8", "persist_pair", "persist_rd"]
+IMPL_ENV = {"wave64": dict(ORL_STEP_IMPL="64", ORL_PERSIST="0", ORL_LIB_VARIANT="default", ORL_PERSIST_VARIANT=None, ORL_PERSIST_INNER=None),
+            "split2": dict(ORL_STEP_IMPL="2", ORL_PERSIST="0", ORL_LIB_VARIANT="alt", ORL_PERSIST_VARIANT=None, ORL_PERSIST_INNER=None),
+            # the persistent kernel in the form the library picks, with all state in global memory, and with slot maps +
+            # link statistics + per-core sums resident in LDS (a form only liborlgpu_alt.so carries; where it does not fit
+            # the library's default form runs) and the per-row cache of inner free runs switched on (the library uses it only
+            # where it costs no wavefront per CU)
+            "persist": dict(ORL_STEP_IMPL="2", ORL_PERSIST="1", ORL_LIB_VARIANT="default", ORL_PERSIST_VARIANT=None, ORL_PERSIST_INNER=None),
+            "persist_global": dict(ORL_STEP_IMPL="2", ORL_PERSIST="1", ORL_LIB_VARIANT="default", ORL_PERSIST_VARIANT="0", ORL_PERSIST_INNER=None),
+            "persist_lds": dict(ORL_STEP_IMPL="2", ORL_PERSIST="1", ORL_LIB_VARIANT="alt", ORL_PERSIST_VARIANT="2", ORL_PERSIST_INNER="2"),
+            # host- / agent-driven steps through k_agent (the phases of the persistent kernel for one step, with info) whatever
+            # the batch size — the library takes it from 2 048 envs — for all four families (RMSA, DeepRMSA, RWA, RMCSA: every
+            # g* / w* / h* fixture of theirs replays through it); device-resident runs as "persist"
+            "agent8": dict(ORL_STEP_IMPL="2", ORL_PERSIST="1", ORL_LIB_VARIANT="default", ORL_PERSIST_VARIANT=None, ORL_PERSIST_INNER=None,
+                           ORL_AGENT_STEP="1"),
+            # the two-wavefront form of the persistent kernel (a control and a row wavefront per 8 envs; the library takes it for
+            # batches of at most 12 288 envs of the single-core families) at every batch size: it exists in specialisation libraries
+            # only, so one is built for every configuration (RMCSA: the one-wavefront kernel, specialised)
+            "persist_pair": dict(ORL_STEP_IMPL="2", ORL_PERSIST="1", ORL_LIB_VARIANT="default", ORL_PERSIST_VARIANT="4", ORL_PERSIST_INNER=None,
+                                 ORL_PERSIST_RW="1", ORL_JIT_SPEC="1"),
+            # the rows-deferred form (round 6): the loop is slot scan + control phase, which changes the slot maps itself and logs an
+            # event per provision / release; k_rowstats replays link statistics and compactness sums after every launch, one lane per
+            # link row (single-core families with at most 64 links; elsewhere the library's own choice runs)
+            "persist_rd": dict(ORL_STEP_IMPL="2", ORL_PERSIST="1", ORL_LIB_VARIANT="default", ORL_PERSIST_VARIANT="7", ORL_PERSIST_INNER=None,
+                               ORL_PERSIST_RW="0")}
+for _name, _env in IMPL_ENV.items():
+    _env.setdefault("ORL_AGENT_STEP", None)
+    _env.setdefault("ORL_PERSIST_RW", None)
+    _env.setdefault("ORL_JIT_SPEC", None)
+
+
+def force_impl(monkeypatch, name):
+    for k, v in IMPL_ENV[name].items():
+        if v is None:
+            monkeypatch.delenv(k, raising=False)
+        else:
+            monkeypatch.setenv(k, v)
+
+
+def _ran_pair_form(env):
+    """The last device-resident run of `env` was launches of the two-wavefront kernel (debug query: 2)."""
+    return int(env.lib.orl_batch_debug_persist_spec(env._h)) == 2
+
+
+def _exact(name):
+    def check(t, what, got, exp):
+        got, exp = np.asarray(got), np.asarray(exp)
+        if got.dtype.kind == "f" or exp.dtype.kind == "f":
+            ok = np.array_equal(got.astype(np.float64), exp.astype(np.float64), equal_nan=True)
+        else:
+            ok = np.array_equal(got, exp)
+        assert ok, "%s: step %d: %s differs\n got %r\n exp %r" % (name, t, what, got, exp)
+    return check

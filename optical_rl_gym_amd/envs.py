@@ -904,8 +904,14 @@ class BatchedOpticalEnv:
         return buf
 
     def set_state(self, buf):
+        """Restore a get_state() snapshot of this batch.  The snapshot's size follows what the batch holds — the first seed() of
+        a batch adds the second stream of every env — and the library takes no length: a snapshot of another size (taken before
+        that seed(), or from a reseeded batch for a fresh one) is refused here with ValueError and nothing is changed."""
         buf = np.ascontiguousarray(buf, np.uint8)
-        assert buf.size == self.lib.orl_batch_state_bytes(self._h)
+        need = int(self.lib.orl_batch_state_bytes(self._h))
+        if buf.size != need:
+            raise ValueError("set_state: the snapshot holds %d bytes, this batch's state %d (a seed() between the two adds every "
+                             "env's second stream to the state)" % (buf.size, need))
         self._ck(self.lib.orl_batch_set_state(self._h, buf.ctypes.data))
 
     def totals(self):

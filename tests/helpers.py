@@ -12,7 +12,8 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 def golden_names(prefix="g"):
-    """g* = step traces (gen_golden.py), w* = wrappers / seed / full reset (gen_golden_wrappers.py)."""
+    """g* = step traces (gen_golden.py), w* = wrappers / seed / full reset (gen_golden_wrappers.py), v* = seed() on a live env of
+    the other families (gen_golden_seed.py)."""
     return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, prefix + "*.npz")))
 
 
@@ -185,6 +186,77 @@ def replay_q(env, g, check):
             check(t, "utilization", ls[0], ref[0])
             check(t, "last_update", ls[3], ref[3])
     check(meta["n_steps"], "svc", env.services()[0], g["svc"][meta["n_steps"]])
+
+
+def replay_v(env, g, check, on_event=None):
+    """Replay a v* fixture (seed() on a live env, oracle/gen_golden_seed.py) on a 1-env batch object `env` (oracle or
+    product): seed() and full resets at the recorded steps as replay_w does, with the DeepRMSA observation of every step, the
+    QoSConstrainedRA quantities of replay_q, link statistics at the recorded steps, and at the end the slot map, the network
+    statistics and — discrete bit rates — the four bit-rate histograms through the info values that are made of them.
+    on_event(t, kind) is called after every event."""
+    meta = g["meta"]
+    qos = meta["env"] == "QoSConstrainedRA"
+    events = {int(k): v for k, v in meta["events"].items()}
+    width = g["actions"].shape[1]
+    done = True
+    info = None
+    for t in range(meta["n_steps"]):
+        for kind, arg in events.get(t, []):
+            if kind == "seed":
+                env.seed([arg])
+            else:
+                env.reset(full=True)
+                done = False
+            if on_event is not None:
+                on_event(t, kind)
+        if done:
+            env.reset(full=False)
+        check(t, "svc", env.services()[0], g["svc"][t])
+        if "obs" in g:
+            check(t, "obs", env.observation()[0], g["obs"][t])
+        a = env.policy(meta["policy"])
+        check(t, "action", np.asarray(a[0, :width], np.int64), g["actions"][t])
+        _, reward, done_a, info = env.step(a)
+        done = bool(done_a[0])
+        check(t, "reward", reward[0], g["reward"][t])
+        check(t, "done", int(done), int(g["done"][t]))
+        check(t, "info", info[0, : g["info"].shape[1]], g["info"][t])
+        check(t, "n_active", env.n_active(0), int(g["n_active"][t]))
+        if qos:
+            check(t, "counters", env.counters()[0, :4], g["counters"][t][:4])
+            check(t, "spectrum", env.spectrum(0), g["spectrum"][t])
+        else:
+            check(t, "counters", env.counters()[0], g["counters"][t])
+            sl = env.slots(0)
+            if sl.shape[0] == 1:
+                sl = sl[0]
+            check(t, "crc", crc_slots(sl), int(g["crc"][t]))
+        if (t + 1) in meta["snapshot_steps"]:
+            ls, ref = env.link_stats(0), g["snap%d_link_stats" % (t + 1)]
+            if qos:
+                check(t, "utilization", ls[0], ref[0])
+                check(t, "last_update", ls[3], ref[3])
+            else:
+                check(t, "link_stats", ls, ref)
+    T = meta["n_steps"]
+    check(T, "svc", env.services()[0], g["svc"][T])
+    if not qos:
+        sl = env.slots(0)
+        if sl.shape[0] == 1:
+            sl = sl[0]
+        check(T, "final_slots", np.packbits(sl, axis=-1, bitorder="little"), g["final_slots"])
+        check(T, "final_net_stats", env.net_stats(0), g["final_net_stats"])
+    if "bit_rate_histograms" in g:
+        # rmsa_env.py:258-282: bit_rate_blocking_<rate> = (requested - provisioned) / requested of the rate's two histograms,
+        # fairness = max - min of them.  The recorded requested histogram already counts the pending service (drawn after the
+        # last step's info was made, rmsa_env.py:283 / 545-580): taken out here
+        req, prov = g["bit_rate_histograms"][0].astype(np.float64), g["bit_rate_histograms"][1].astype(np.float64)
+        req[list(g["bit_rates"]).index(int(g["svc"][T][4]))] -= 1
+        blocking = np.where(req > 0, (req - prov) / np.where(req > 0, req, 1.0), 0.0)
+        keys = meta["info_keys"]
+        col = [keys.index("bit_rate_blocking_%d" % int(r)) for r in g["bit_rates"]]
+        check(T, "blocking per bit rate from the recorded histograms", info[0, col], blocking)
+        check(T, "fairness from the recorded histograms", info[0, keys.index("fairness")], blocking.max() - blocking.min())
 
 
 # ---- step implementations -------------------------------------------------------------------------------------------------

@@ -384,11 +384,11 @@ __device__ __forceinline__ void svc_generate(const DevParams& P, u64* rec, u32* 
         const int c = o + FIXED;
         int a = c - 1;
         if (seek) {
-          u64 x = 0ull;
-          if (c < 64) x = (m_lo >> c) | ((u64)acc2 << (64 - c));  // (c >= 8: the shift is in range)
-          else if (c < 8 * ORL_SVC_WIN) x = (u64)(acc2 >> (c - 64));
-          if (x == 0ull) ok = false;
-          else a = c + (int)__builtin_ctzll(x);
+          // the first accepted word at or behind word c: among words c .. 63, else among words 64 .. 95 (all of them behind c then)
+          const u64 xl = (c < 64) ? (m_lo >> c) : 0ull;  // (c >= 8: the shift is in range)
+          const u32 xh = (c <= 64) ? acc2 : ((c < 8 * ORL_SVC_WIN) ? ((acc2 >> (c - 64)) << (c - 64)) : 0u);
+          if (xl == 0ull && xh == 0u) ok = false;
+          else a = (xl != 0ull) ? c + (int)__builtin_ctzll(xl) : 64 + (int)__builtin_ctz(xh);
         } else if (c > 8 * ORL_SVC_WIN) {
           ok = false;
         }

@@ -102,12 +102,21 @@ class BatchedOpticalEnv:
                bit_rate_selection="continuous", bit_rates=(10, 40, 100), bit_rate_probabilities=None,
                bit_rate_lower_bound=25, bit_rate_higher_bound=100, j=1, num_spatial_resources=1,
                modulations=None, worst_xt=None, event_capacity=0, action_histograms=False, num_service_classes=1,
-               classes_arrival_probabilities=(1.0,), classes_reward=(1.0,)):
+               classes_arrival_probabilities=(1.0,), classes_reward=(1.0,), mt_state=None):
         self.lib = _lib.lib()  # ORL_LIB_VARIANT=alt selects the -DORL_ALT_IMPLS build (cross-implementation tests)
         self.action_histograms = bool(action_histograms)
         self.topology = Topology.load(topology) if isinstance(topology, str) else topology
         t = self.topology
         self.num_envs = int(num_envs)
+        if mt_state is not None:
+            # the generators' states themselves instead of seeds: [num_envs][625] uint32, random.Random.getstate()[1] of every env
+            # (624 MT19937 words + the index 0 .. 624, include/orl.h orl_batch_create)
+            if seeds is not None:
+                raise ValueError("seeds or mt_state, not both")
+            mt_state = np.ascontiguousarray(mt_state, np.uint32)
+            if mt_state.shape != (self.num_envs, 625) or (mt_state[:, 624] > 624).any():
+                raise ValueError("mt_state must be [num_envs][625] uint32: 624 words and an index of at most 624 per env")
+        self._mt_state = mt_state
         if seeds is None:
             seeds = [None] * self.num_envs
         elif np.isscalar(seeds):
@@ -250,7 +259,7 @@ class BatchedOpticalEnv:
         self._h = C.c_void_p()
         int_seeds = [41 if s_ is None else int(s_) for s_ in self.seeds]
         lam_a, lam_h = self._rate_arrays
-        if all(-2**63 < s_ < 2**63 for s_ in int_seeds):
+        if mt_state is None and all(-2**63 < s_ < 2**63 for s_ in int_seeds):
             # device-side random.Random(seed): no 2.5 KB/env upload, no Python loop over envs
             sd = np.array(int_seeds, np.int64)
             if lam_a is None:
@@ -259,8 +268,8 @@ class BatchedOpticalEnv:
             else:
                 self._ck(self.lib.orl_batch_create_with_rates(C.byref(cfg), self._topo_h, self.num_envs, None, sd.ctypes.data,
                                                                 lam_a.ctypes.data, lam_h.ctypes.data, C.byref(self._h)))
-        else:  # seeds beyond 64 bits: let CPython expand them
-            st = mt_states(self.seeds)
+        else:  # given states; seeds beyond 64 bits: let CPython expand them
+            st = mt_states(self.seeds) if mt_state is None else mt_state
             if lam_a is None:
                 self._ck(self.lib.orl_batch_create(C.byref(cfg), self._topo_h, self.num_envs, st.ctypes.data,
                                                      C.byref(self._h)))
@@ -929,10 +938,10 @@ class BatchedRMSAEnv(BatchedOpticalEnv):
                  mean_service_holding_time=10800.0, num_spectrum_resources=100, bit_rate_selection="continuous",
                  bit_rates=(10, 40, 100), bit_rate_probabilities=None, node_request_probabilities=None,
                  bit_rate_lower_bound=25.0, bit_rate_higher_bound=100.0, seed=None, allow_rejection=False,
-                 reset=True, channel_width=12.5, event_capacity=0, action_histograms=False):
+                 reset=True, channel_width=12.5, event_capacity=0, action_histograms=False, mt_state=None):
         if seeds is None and seed is not None:
             seeds = seed
-        self._setup(topology, num_envs, seeds, device_id, episode_length=episode_length, load=load,
+        self._setup(topology, num_envs, seeds, device_id, episode_length=episode_length, load=load, mt_state=mt_state,
                     mean_service_holding_time=mean_service_holding_time,
                     num_spectrum_resources=num_spectrum_resources, allow_rejection=allow_rejection,
                     node_request_probabilities=node_request_probabilities, channel_width=channel_width,
@@ -954,7 +963,7 @@ class BatchedDeepRMSAEnv(BatchedOpticalEnv):
     def __init__(self, topology=None, num_envs=1, seeds=None, device_id=0, j=1, episode_length=1000,
                  mean_service_holding_time=25.0, mean_service_inter_arrival_time=0.1, num_spectrum_resources=100,
                  node_request_probabilities=None, seed=None, allow_rejection=False, event_capacity=0,
-                 action_histograms=False):
+                 action_histograms=False, mt_state=None):
         if seeds is None and seed is not None:
             seeds = seed
         mht_v = per_env_values(mean_service_holding_time, num_envs, "mean_service_holding_time")
@@ -966,7 +975,7 @@ class BatchedDeepRMSAEnv(BatchedOpticalEnv):
             a = miat_v if miat_v is not None else [_check_scalar(mean_service_inter_arrival_time, "mean_service_inter_arrival_time")] * int(num_envs)
             load = [float(h[i]) / float(a[i]) for i in range(int(num_envs))]
         self._setup(topology, num_envs, seeds, device_id, episode_length=episode_length,
-                    load=load,
+                    load=load, mt_state=mt_state,
                     mean_service_holding_time=mean_service_holding_time,
                     num_spectrum_resources=num_spectrum_resources, allow_rejection=allow_rejection,
                     node_request_probabilities=node_request_probabilities, channel_width=12.5, j=j,
@@ -982,10 +991,10 @@ class BatchedRWAEnv(BatchedOpticalEnv):
     def __init__(self, topology=None, num_envs=1, seeds=None, device_id=0, episode_length=1000, load=10,
                  mean_service_holding_time=10800.0, num_spectrum_resources=80, node_request_probabilities=None,
                  allow_rejection=True, seed=None, reset=True, channel_width=50.0, event_capacity=0,
-                 action_histograms=False):
+                 action_histograms=False, mt_state=None):
         if seeds is None and seed is not None:
             seeds = seed
-        self._setup(topology, num_envs, seeds, device_id, episode_length=episode_length, load=load,
+        self._setup(topology, num_envs, seeds, device_id, episode_length=episode_length, load=load, mt_state=mt_state,
                     mean_service_holding_time=mean_service_holding_time,
                     num_spectrum_resources=num_spectrum_resources, allow_rejection=allow_rejection,
                     node_request_probabilities=node_request_probabilities, channel_width=channel_width,
@@ -1007,7 +1016,7 @@ class BatchedRMCSAEnv(BatchedOpticalEnv):
                  modulation_formats=None, worst_xt=None, node_request_probabilities=None,
                  bit_rate_selection="continuous", bit_rates=(10, 40, 100), bit_rate_probabilities=None,
                  bit_rate_lower_bound=25, bit_rate_higher_bound=100, seed=None, allow_rejection=False, reset=True,
-                 channel_width=12.5, event_capacity=0, action_histograms=False):
+                 channel_width=12.5, event_capacity=0, action_histograms=False, mt_state=None):
         import copy
 
         if seeds is None and seed is not None:
@@ -1019,7 +1028,7 @@ class BatchedRMCSAEnv(BatchedOpticalEnv):
         for m in mods:  # rmcsa_env.py:127-129: +4 dB margin on both limits
             m.inband_xt += 4
         worst_xt += 4
-        self._setup(topo, num_envs, seeds, device_id, episode_length=episode_length, load=load,
+        self._setup(topo, num_envs, seeds, device_id, episode_length=episode_length, load=load, mt_state=mt_state,
                     mean_service_holding_time=mean_service_holding_time,
                     num_spectrum_resources=num_spectrum_resources, allow_rejection=allow_rejection,
                     node_request_probabilities=node_request_probabilities, channel_width=channel_width,
@@ -1043,10 +1052,10 @@ class BatchedQoSConstrainedRA(BatchedOpticalEnv):
     def __init__(self, topology=None, num_envs=1, seeds=None, device_id=0, episode_length=1000, load=10,
                  mean_service_holding_time=10800.0, num_spectrum_resources=80, num_service_classes=1,
                  classes_arrival_probabilities=(1.0,), classes_reward=(1.0,), node_request_probabilities=None,
-                 allow_rejection=True, k_paths=5, seed=None, reset=True, event_capacity=0):
+                 allow_rejection=True, k_paths=5, seed=None, reset=True, event_capacity=0, mt_state=None):
         if seeds is None and seed is not None:
             seeds = seed
-        self._setup(topology, num_envs, seeds, device_id, episode_length=episode_length, load=load,
+        self._setup(topology, num_envs, seeds, device_id, episode_length=episode_length, load=load, mt_state=mt_state,
                     mean_service_holding_time=mean_service_holding_time,
                     num_spectrum_resources=num_spectrum_resources, allow_rejection=allow_rejection,
                     node_request_probabilities=node_request_probabilities, channel_width=12.5,

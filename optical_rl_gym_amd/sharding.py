@@ -70,10 +70,18 @@ class MultiDeviceBatch:
 
     PER_ENV_KWARGS = ("load", "mean_service_holding_time", "mean_service_inter_arrival_time")
 
-    def __init__(self, env_id, num_envs, seeds=None, device_ids=(0,), **kwargs):
+    def __init__(self, env_id, num_envs, seeds=None, device_ids=(0,), mt_state=None, **kwargs):
         from .envs import ENV_CLASSES
 
-        if seeds is None:
+        if mt_state is not None:  # the generators' states instead of seeds ([num_envs][625] uint32): each shard gets its rows
+            if seeds is not None:
+                raise ValueError("seeds or mt_state, not both")
+            mt_state = np.ascontiguousarray(mt_state, np.uint32)
+            if mt_state.shape != (num_envs, 625):
+                raise ValueError("mt_state must be [num_envs][625] uint32")
+        if mt_state is not None:
+            seeds = None
+        elif seeds is None:
             seeds = [None] * num_envs
         elif np.isscalar(seeds):
             seeds = [int(seeds) + i for i in range(num_envs)]
@@ -81,7 +89,10 @@ class MultiDeviceBatch:
         for r, dev in enumerate(device_ids):
             lo, hi = shard_range(num_envs, r, len(device_ids))
             kw = cut_per_env_kwargs(kwargs, self.PER_ENV_KWARGS, num_envs, lo, hi)
-            shards.append(ENV_CLASSES[env_id](num_envs=hi - lo, seeds=list(seeds[lo:hi]), device_id=int(dev), **kw))
+            if mt_state is not None:
+                shards.append(ENV_CLASSES[env_id](num_envs=hi - lo, mt_state=mt_state[lo:hi], device_id=int(dev), **kw))
+            else:
+                shards.append(ENV_CLASSES[env_id](num_envs=hi - lo, seeds=list(seeds[lo:hi]), device_id=int(dev), **kw))
         self._init_from(shards)
 
     @classmethod

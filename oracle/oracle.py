@@ -96,8 +96,15 @@ def load_topology_tables(name_or_path):
 class OracleBatch:
     """n independent reference-equivalent envs, each constructed with seed=seeds[i]."""
 
-    def __init__(self, env_type, topology, seeds, omp=False, **kw):
+    def __init__(self, env_type, topology, seeds=None, omp=False, mt_state=None, **kw):
+        """mt_state: [n][625] uint32 (624 MT19937 words + index, random.Random.getstate()[1]) in place of the seeds' expansion:
+        env i starts from that state of its generator, whatever its index (the crafted-state tests)."""
         self.lib = _lib(omp)
+        if mt_state is not None:
+            assert seeds is None, "seeds or mt_state, not both"
+            mt_state = np.ascontiguousarray(mt_state, np.uint32)
+            assert mt_state.ndim == 2 and mt_state.shape[1] == 625 and (mt_state[:, 624] <= 624).all()
+            seeds = [None] * len(mt_state)
         t = load_topology_tables(topology) if isinstance(topology, str) else topology
         self.tables = t
         et = ENV_TYPES[env_type]
@@ -166,7 +173,7 @@ class OracleBatch:
         self.n = len(seeds)
         self.n_info = self.lib.orc_info_dim(C.byref(cfg))
         self.obs_dim = self.lib.orc_obs_dim(C.byref(cfg))
-        st = mt_states(seeds)
+        st = mt_states(seeds) if mt_state is None else mt_state
         self.h = self.lib.orc_create(C.byref(cfg), C.byref(tb), self.n, st.ctypes.data)
         self.C, self.E, self.S, self.k = cores, E, S, k
 

@@ -318,3 +318,15 @@ def _exact(name):
             ok = np.array_equal(got, exp)
         assert ok, "%s: step %d: %s differs\n got %r\n exp %r" % (name, t, what, got, exp)
     return check
+
+
+def _exact_bits(name):
+    """_exact with floats compared as their uint64 bit patterns: -0.0 differs from 0.0, a nan equals the nan of the same bits"""
+    def check(t, what, got, exp):
+        got, exp = np.asarray(got), np.asarray(exp)
+        if got.dtype.kind == "f" or exp.dtype.kind == "f":
+            got = np.ascontiguousarray(got, np.float64).view(np.uint64)
+            exp = np.ascontiguousarray(exp, np.float64).view(np.uint64)
+        ok = np.array_equal(got, exp)
+        assert ok, "%s: step %d: %s differs (floats as bit patterns)\n got %r\n exp %r" % (name, t, what, got, exp)
+    return check

@@ -395,6 +395,44 @@ int orl_batch_matrix_paths_observation(orl_batch* b, uint8_t* out);
 int64_t orl_batch_state_bytes(orl_batch* b);
 int orl_batch_get_state(orl_batch* b, void* out);
 int orl_batch_set_state(orl_batch* b, const void* in);
+/* The snapshot's format, so that a caller can address one env inside a get_state() buffer: returns the number of sections and,
+ * for the first max_sections of them, row_bytes[s] = bytes per env of section s, in snapshot order (section s occupies
+ * n_envs * row_bytes[s] bytes, env i at i * row_bytes[s]).  The sections: the scalar record, the pending service, the slot maps,
+ * the pending releases (times, records), the random stream, the link statistics, the compactness sums, the soon list (times,
+ * slots), then where the batch keeps them the bit-rate histograms, RWA's action marginals, the action histograms and the second
+ * random stream of a reseeded batch. */
+int orl_batch_state_layout(orl_batch* b, int64_t* row_bytes, int max_sections);
+
+/* Fork env states on the device: for every p < n, env dst_idx[p] of `dst` becomes a copy of env src_idx[p] of `src` (NULL = dst
+ * itself) — every per-env row a snapshot holds (orl_batch_state_layout), taken whole, so that right after the call the
+ * destination's rows equal the source's byte for byte and the copy continues exactly as its source does under every step route,
+ * given the same actions.  One source may feed many destinations.  The flag word of the env (ORL_E_OVERFLOW / bad action marks)
+ * travels with the record, as with orl_batch_set_state.
+ * flags & ORL_COPY_KEEP_RNG: the destination takes the source's network state, clock, counters, pending service and pending
+ * releases but keeps its OWN random streams: its stream and, in a reseeded batch, its second stream, their positions and the
+ * mark that the env was reseeded.  A lookahead child that shared its parent's stream would have seen the parent's future
+ * arrivals.  The service id still comes from the source.
+ * What does NOT travel: the traffic rates (configuration, as for orl_batch_set_state: orl_batch_get_rates of both batches is
+ * unchanged; follow up with orl_batch_set_rates to fork across loads); the path column of ORL_POLICY_PATH_FF (ORL_BUF_PATHS) and
+ * the actions / reward / done / info / terminal observation rows of the last step; the armed episode log; the info mode.
+ * Afterwards the destination's observation (DeepRMSA) is rebuilt as by orl_batch_set_state.
+ * Ordering: everything is queued on the destination's stream; between two batches that stream first waits for what is queued on
+ * the source's, and the source's stream then waits for the copy, so later steps of the source cannot overtake the read.  The
+ * call returns without waiting for the device (it waits only for its own previous upload of index arrays, which are host
+ * arrays); it is not graph-capturable.
+ * Refused with ORL_E_INVALID and a specific orl_last_error(), before anything is modified or queued: n < 0 (n == 0 is ORL_OK
+ * and does nothing); a null index array with n > 0; an index outside its batch; a destination that occurs twice; inside one
+ * batch, a destination that is also the source of another pair (pairs with src == dst are dropped as no-ops first: the kernel
+ * is a single pass, a permutation goes through a scratch batch); batches on different devices; batches whose per-env layout
+ * differs (family, topology sizes or path tables, spectrum, cores, j, event capacity, bit-rate table size and mode, histograms
+ * on / off, QoS classes); one batch reseeded (it carries second streams) and the other not — orl_batch_reseed the other first,
+ * an all-zero mask allocates the streams without reseeding an env; either batch's last device-resident run abandoned. */
+#define ORL_COPY_KEEP_RNG 1
+int orl_batch_copy_envs(orl_batch* dst, orl_batch* src /* NULL = dst */, int64_t n, const int64_t* src_idx, const int64_t* dst_idx,
+                        uint32_t flags);
+/* The index rules of orl_batch_copy_envs without a device (tests/test_copy_plan.py): the number of pairs that remain after
+ * dropping the no-ops, or ORL_E_INVALID with the refusal in orl_last_error(). */
+int orl_debug_copy_pairs_check(int64_t B_src, int64_t B_dst, int same_batch, int64_t n, const int64_t* src_idx, const int64_t* dst_idx);
 
 /* Profiling aid: reads the whole slot-map array once with 8-B (width16 = 0) or 16-B (1) loads per lane and returns the
  * number of bytes read, so that rocprofv3's FETCH_SIZE can be calibrated on a known byte count. */

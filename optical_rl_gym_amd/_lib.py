@@ -53,6 +53,9 @@ EXPORTS = {
     "orl_batch_state_bytes": (C.c_int64, [C.c_void_p]),
     "orl_batch_get_state": (C.c_int, [C.c_void_p, C.c_void_p]),
     "orl_batch_set_state": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "orl_batch_state_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "orl_batch_copy_envs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "orl_debug_copy_pairs_check": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "orl_batch_info_dim": (C.c_int, [C.c_void_p]),
     "orl_batch_obs_dim": (C.c_int, [C.c_void_p]),
     "orl_batch_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

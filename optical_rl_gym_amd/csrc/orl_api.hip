@@ -21,6 +21,7 @@
 
 #include "orl_host.h"
 #include "orl_run_plan.h"
+#include "orl_copy_plan.h"
 
 using namespace orl;
 
@@ -130,6 +131,8 @@ __global__ void k_matrix_obs(DevParams P, unsigned char* out) {
 }
 
 #include "orl_qos_obs.h"  // k_qos_matrix_obs: MatrixObservationWithPaths of QoSConstrainedRA (qos_constrained_ra.py:440-493)
+
+#include "orl_copy.h"  // k_copy_envs: the rows of env src[p] of one batch into env dst[p] of another (orl_batch_copy_envs)
 
 // end of a device-resident run: the network-compactness update the last step left pending (one thread per env), so
 // that every host-visible state is final; also the OR of every env's flag word (as k_flags_or) — one launch, and
@@ -438,6 +441,20 @@ static double pf_window_of(const std::vector<double>& rates) {
   return 4.0 / (sum / (double)(rates.size() / 2));
 }
 
+// what two batches must share for the path indices in one's pending releases to mean the same in the other's (orl_batch_copy_envs)
+static uint64_t topology_hash(const orl_topology* t) {
+  uint64_t h = 0xcbf29ce484222325ull;
+  auto mix = [&](const void* p, size_t n) {
+    for (size_t i = 0; i < n; i++) h = (h ^ ((const unsigned char*)p)[i]) * 0x100000001b3ull;
+  };
+  const int dims[5] = {t->N, t->E, t->K, t->H, t->M};
+  mix(dims, sizeof dims);
+  mix(t->h_hops.data(), t->h_hops.size() * sizeof(int32_t));
+  mix(t->h_links.data(), t->h_links.size() * sizeof(int32_t));
+  mix(t->h_mod.data(), t->h_mod.size() * sizeof(int32_t));
+  return h;
+}
+
 static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int64_t n_envs, const uint32_t* mt_state,
                              const int64_t* seeds, const double* lambda_arrival, const double* lambda_holding, orl_batch** out) {
   if (!c || !t || !out || (!mt_state && !seeds) || n_envs < 1) return fail(ORL_E_INVALID, "null/invalid argument");
@@ -490,6 +507,7 @@ static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int
   orl_batch* b = hold.get();
   memset(&b->P, 0, sizeof b->P);
   b->device = t->device;
+  b->topo_hash = topology_hash(t);
 #define FAIL_B(...) do { return fail(__VA_ARGS__); } while (0)
 #define HIPCHK_B(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) FAIL_B(ORL_E_HIP, "%s failed: %s", #x, hipGetErrorString(e_)); } while (0)
   DevParams& P = b->P;
@@ -676,6 +694,9 @@ extern "C" void orl_batch_destroy(orl_batch* b) try {
   if (b->ev1) hipEventDestroy(b->ev1);
   if (b->h_tail) hipHostFree(b->h_tail);
   if (b->h_actions) hipHostFree(b->h_actions);
+  if (b->h_copy_idx) hipHostFree(b->h_copy_idx);
+  if (b->ev_copy_up) hipEventDestroy(b->ev_copy_up);
+  if (b->ev_copy) hipEventDestroy(b->ev_copy);
   if (b->spec_handle) dlclose(b->spec_handle);
   for (void* p : b->allocs) hipFree(p);
   delete b;
@@ -1964,25 +1985,27 @@ extern "C" int orl_multi_run(orl_multi* m, int policy_id, int64_t n_steps, orl_r
 ORL_ABI_CATCH_INT
 
 // ---- snapshot / restore: the per-env arrays, concatenated in a fixed order -------------------------
-struct Section { void* ptr; size_t bytes; };
+// (row: bytes per env; kind: what orl_batch_copy_envs with ORL_COPY_KEEP_RNG does to the section, COPY_* of orl_copy.h)
+struct Section { void* ptr; size_t bytes; size_t row; int kind; };
 static std::vector<Section> state_sections(orl_batch* b) {
   const DevParams& P = b->P;
   const size_t B = (size_t)P.B;
   std::vector<Section> v;
-  v.push_back({P.scal, B * ORL_SCAL_WORDS * 8});
-  v.push_back({P.svc_desc, B * 8});
-  v.push_back({P.bitmap, B * P.bm_words * 8});
-  v.push_back({P.ev_time, B * P.ev_cap * 8});
-  v.push_back({P.ev_info, B * P.ev_cap * 8});
-  v.push_back({P.mt, B * 624 * 4});
-  v.push_back({P.lstat, B * 4 * P.E * 8});
-  v.push_back({P.core_sums, B * P.cs_words * 4});
-  v.push_back({P.soon_t, B * ORL_SOON * 8});
-  v.push_back({P.soon_i, B * ORL_SOON * 4});
-  if (P.br_hist) v.push_back({P.br_hist, B * 2 * P.n_br * 8});
-  if (P.act_hist) v.push_back({P.act_hist, B * ((P.K + 1) + (P.S + 1)) * 8});
-  if (P.act2d) v.push_back({P.act2d, B * (size_t)P.act2d_words * 4});
-  if (P.mt2) v.push_back({P.mt2, B * 624 * 4});
+  auto add = [&](void* ptr, size_t row, int kind) { v.push_back({ptr, B * row, row, kind}); };
+  add(P.scal, ORL_SCAL_WORDS * 8, COPY_SCAL);
+  add(P.svc_desc, 8, COPY_PLAIN);
+  add(P.bitmap, (size_t)P.bm_words * 8, COPY_PLAIN);
+  add(P.ev_time, (size_t)P.ev_cap * 8, COPY_PLAIN);
+  add(P.ev_info, (size_t)P.ev_cap * 8, COPY_PLAIN);
+  add(P.mt, 624 * 4, COPY_RNG);
+  add(P.lstat, (size_t)4 * P.E * 8, COPY_PLAIN);
+  add(P.core_sums, (size_t)P.cs_words * 4, COPY_PLAIN);
+  add(P.soon_t, ORL_SOON * 8, COPY_PLAIN);
+  add(P.soon_i, ORL_SOON * 4, COPY_PLAIN);
+  if (P.br_hist) add(P.br_hist, (size_t)2 * P.n_br * 8, COPY_PLAIN);
+  if (P.act_hist) add(P.act_hist, (size_t)((P.K + 1) + (P.S + 1)) * 8, COPY_PLAIN);
+  if (P.act2d) add(P.act2d, (size_t)P.act2d_words * 4, COPY_PLAIN);
+  if (P.mt2) add(P.mt2, 624 * 4, COPY_RNG);
   return v;
 }
 extern "C" int64_t orl_batch_state_bytes(orl_batch* b) try {
@@ -2018,6 +2041,107 @@ extern "C" int orl_batch_set_state(orl_batch* b, const void* in) try {
   slot_maps_change(b, b->stream);
   if (b->P.obs_dim) ORL_LAUNCH(obs, b, 0);
   HIPCHK(hipStreamSynchronize(b->stream));
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+/* the snapshot's format: bytes per env of every section, in snapshot order */
+extern "C" int orl_batch_state_layout(orl_batch* b, int64_t* row_bytes, int max_sections) try {
+  if (!b) return fail(ORL_E_INVALID, "null batch");
+  const std::vector<Section> secs = state_sections(b);
+  if (row_bytes)
+    for (size_t s = 0; s < secs.size() && (int)s < max_sections; s++) row_bytes[s] = (int64_t)secs[s].row;
+  return (int)secs.size();
+}
+ORL_ABI_CATCH_INT
+
+extern "C" int orl_debug_copy_pairs_check(int64_t B_src, int64_t B_dst, int same_batch, int64_t n, const int64_t* src_idx,
+                                          const int64_t* dst_idx) try {
+  if (B_src < 1 || B_dst < 1 || (same_batch && B_src != B_dst)) return fail(ORL_E_INVALID, "bad batch sizes");
+  char why[ORL_COPY_WHY];
+  const CopyPairs cp = copy_pairs_check(B_src, B_dst, same_batch != 0, n, src_idx, dst_idx, why);
+  if (!cp.ok) return fail(ORL_E_INVALID, "copy_envs: %s", why);
+  return (int)cp.dst.size();
+}
+ORL_ABI_CATCH_INT
+
+// Fork env states on the device: env dst_idx[p] of `b` becomes a copy of env src_idx[p] of `src` (include/orl.h).  Everything is
+// refused before anything is modified or queued; then one upload of the pairs, one launch of k_copy_envs and the observation
+// rebuild on the destination's stream, ordered with the source's stream by two events when the batches differ.
+extern "C" int orl_batch_copy_envs(orl_batch* b, orl_batch* src, int64_t n, const int64_t* src_idx, const int64_t* dst_idx,
+                                   uint32_t flags) try {
+  if (!b) return fail(ORL_E_INVALID, "null batch");
+  if (!src) src = b;
+  const bool same = src == b;
+  if (flags & ~(uint32_t)ORL_COPY_KEEP_RNG) return fail(ORL_E_INVALID, "copy_envs: unknown flags 0x%x", flags);
+  const int keep_rng = (flags & ORL_COPY_KEEP_RNG) ? 1 : 0;
+  char why[ORL_COPY_WHY];
+  if (!same) {
+    if (src->device != b->device)
+      return fail(ORL_E_INVALID, "copy_envs: the batches live on different devices (%d and %d): copies between GPUs are not supported",
+                  src->device, b->device);
+    if (!copy_layout_compatible(src->P, b->P, why)) return fail(ORL_E_INVALID, "copy_envs: %s", why);
+    if (src->P.n_paths != b->P.n_paths && src->topo_hash != b->topo_hash)
+      return fail(ORL_E_INVALID, "copy_envs: the batches were created on topologies with different path tables");
+  }
+  if (b->run_abandoned || src->run_abandoned)
+    return fail(ORL_E_INVALID, "copy_envs: the last device-resident run of the %s batch did not complete: reset or restore it first",
+                src->run_abandoned ? "source" : "destination");
+  const CopyPairs cp = copy_pairs_check(src->P.B, b->P.B, same, n, src_idx, dst_idx, why);
+  if (!cp.ok) return fail(ORL_E_INVALID, "copy_envs: %s", why);
+  const int64_t m = (int64_t)cp.dst.size();
+  if (m == 0) return ORL_OK;
+
+  const std::vector<Section> ss = state_sections(src), ds = state_sections(b);
+  if (ss.size() != ds.size() || ss.size() > ORL_COPY_MAX_SECTIONS) return fail(ORL_E_INTERNAL, "copy_envs: section tables differ");
+  CopyTable T;
+  memset(&T, 0, sizeof T);
+  for (size_t s = 0; s < ss.size(); s++) {
+    if (ss[s].row != ds[s].row || ss[s].row > 0xffffffffull) return fail(ORL_E_INTERNAL, "copy_envs: section %zu differs", s);
+    const uintptr_t bits = (uintptr_t)ss[s].ptr | (uintptr_t)ds[s].ptr | (uintptr_t)ss[s].row;
+    T.s[s].src = (const unsigned char*)ss[s].ptr;
+    T.s[s].dst = (unsigned char*)ds[s].ptr;
+    T.s[s].row_bytes = (u32)ss[s].row;
+    T.s[s].gran = (bits & 15) == 0 ? 16 : (bits & 7) == 0 ? 8 : 4;
+    T.s[s].kind = (u32)ss[s].kind;
+    if (bits & 3) return fail(ORL_E_INTERNAL, "copy_envs: section %zu is not made of 4-byte words", s);
+  }
+
+  HIPCHK(hipSetDevice(b->device));
+  if (!b->ev_copy_up) HIPCHK(hipEventCreateWithFlags(&b->ev_copy_up, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(b->ev_copy_up));  // (the last call's upload has left the staging buffer)
+  if (m > b->copy_cap) {
+    int64_t cap = b->copy_cap > 0 ? b->copy_cap : 1024;
+    while (cap < m) cap *= 2;
+    if (cap > b->P.B) cap = b->P.B;  // (destinations are distinct: m <= B)
+    long long *d = nullptr, *h = nullptr;
+    HIPCHK(hipMalloc((void**)&d, (size_t)cap * 2 * sizeof(long long) + 64));
+    b->allocs.push_back(d);  // (the smaller buffer stays with the batch: a copy queued earlier may still read it)
+    HIPCHK(hipHostMalloc((void**)&h, (size_t)cap * 2 * sizeof(long long), hipHostMallocPortable));
+    if (b->h_copy_idx) hipHostFree(b->h_copy_idx);
+    b->copy_idx = d;
+    b->h_copy_idx = h;
+    b->copy_cap = cap;
+  }
+  memcpy(b->h_copy_idx, cp.src.data(), (size_t)m * sizeof(long long));
+  memcpy(b->h_copy_idx + m, cp.dst.data(), (size_t)m * sizeof(long long));
+  HIPCHK(hipMemcpyAsync(b->copy_idx, b->h_copy_idx, (size_t)m * 2 * sizeof(long long), hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipEventRecord(b->ev_copy_up, b->stream));
+  if (!same) {  // the copy reads the source behind everything queued on the source's stream
+    if (!src->ev_copy) HIPCHK(hipEventCreateWithFlags(&src->ev_copy, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(src->ev_copy, src->stream));
+    HIPCHK(hipStreamWaitEvent(b->stream, src->ev_copy, 0));
+  }
+  slot_maps_change(b, b->stream);
+  hipLaunchKernelGGL(k_copy_envs, dim3((unsigned)m), dim3(ORL_COPY_THREADS), 0, b->stream, T, (int)ss.size(), (const long long*)b->copy_idx,
+                     (i64)m, keep_rng);
+  if (b->P.obs_dim) ORL_LAUNCH(obs, b, 0);
+  if (!same) {  // ... and later steps of the source cannot overtake the read
+    if (!b->ev_copy) HIPCHK(hipEventCreateWithFlags(&b->ev_copy, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(b->ev_copy, b->stream));
+    HIPCHK(hipStreamWaitEvent(src->stream, b->ev_copy, 0));
+  }
+  HIPCHK(hipGetLastError());
   return ORL_OK;
 }
 ORL_ABI_CATCH_INT

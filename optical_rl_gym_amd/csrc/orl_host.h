@@ -90,6 +90,14 @@ struct orl_batch {
   int mask_last = -1;              // layout of the last launch: what ORL_BUF_ACTION_MASK hands out (-1: none yet)
   unsigned char* qobs_buf = nullptr;  // MatrixObservationWithPaths (QoSConstrainedRA): [B][pitch] bytes, allocated by the first
                                     // orl_batch_matrix_paths_observation; what ORL_BUF_MATRIX_PATHS_OBS hands out
+  // orl_batch_copy_envs (as the destination): the pair indices [2][n] on the device and in page-locked memory, grown on demand
+  long long* copy_idx = nullptr;
+  long long* h_copy_idx = nullptr;
+  int64_t copy_cap = 0;
+  hipEvent_t ev_copy_up = nullptr;  // behind the last upload out of h_copy_idx: the next call waits for it before it refills the buffer
+  hipEvent_t ev_copy = nullptr;     // cross-batch copies: orders this batch's stream with the other's (as source: behind what it queued;
+                                    // as destination: behind the copy)
+  uint64_t topo_hash = 0;           // FNV-1a of the topology's sizes and path tables (hops, links, modulations): copy_envs compares it
 };
 
 // Anything but the row-cache-keeping forms of the persistent kernel is about to write slot maps: the row caches the persistent

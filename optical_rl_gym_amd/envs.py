@@ -923,6 +923,56 @@ class BatchedOpticalEnv:
                              "env's second stream to the state)" % (buf.size, need))
         self._ck(self.lib.orl_batch_set_state(self._h, buf.ctypes.data))
 
+    def state_layout(self):
+        """Bytes per env of every section of a get_state() snapshot, in snapshot order: section s occupies num_envs * layout[s]
+        bytes, env i at i * layout[s] inside it (include/orl.h, orl_batch_state_layout).  Enough to cut one env out of a snapshot."""
+        n = int(self.lib.orl_batch_state_layout(self._h, None, 0))
+        if n < 0:
+            self._ck(n)
+        rows = np.zeros(n, np.int64)
+        self._ck(min(int(self.lib.orl_batch_state_layout(self._h, rows.ctypes.data, n)), 0))
+        return [int(r) for r in rows]
+
+    def copy_envs(self, src, dst, source=None, keep_rng=False):
+        """Fork env states on the device: for every pair, env dst[p] of THIS batch becomes a copy of env src[p] of `source`
+        (default: this batch) — every per-env row a snapshot holds, byte for byte, so the copy continues exactly as its source
+        does under the same actions or policy.  `src`, `dst`: equally long 1-D integer arrays; a scalar `src` is broadcast to
+        len(dst), the fork of one env into many.  One source may feed many destinations.
+
+        keep_rng=True: the destination takes the source's network state, clock, counters, pending service and pending
+        releases but keeps its own random streams (and their positions, and whether it was reseeded): an honest lookahead
+        child, which has not seen its parent's future arrivals, or a population that does not collapse onto one future.
+
+        What does not travel: the traffic rates, which are configuration exactly as for set_state (`rates()` of both batches
+        is unchanged; follow up with set_load(mask=...) to fork across loads); the path column of set_paths and the actions /
+        reward / done / info / terminal-observation rows of the last step; the armed episode log; the info mode.  The env's
+        flag word travels with its record.  The observation of this batch is rebuilt afterwards.
+
+        Queued on this batch's stream (ordered with `source`'s stream both ways), without waiting for the device.  Refused by
+        the library with nothing changed: an index out of range, a destination listed twice, inside one batch a destination
+        that is also the source of another pair (src == dst pairs are no-ops; a permutation goes through a scratch batch),
+        batches on different devices or of different per-env layout (family, topology, spectrum, cores, j, event capacity,
+        bit-rate table, histograms), one batch reseeded and the other not (seed() the other first: an all-zero mask is
+        enough), a batch whose last run was abandoned.  ValueError for index arrays of the wrong shape or type."""
+        source = self if source is None else source
+        if not isinstance(source, BatchedOpticalEnv) or source.lib is not self.lib:
+            raise ValueError("copy_envs: source must be a batch of this library")
+        d = np.asarray(dst)
+        s = np.asarray(src)
+        for name, a in (("src", s), ("dst", d)):
+            if a.size and a.dtype.kind not in "iu":
+                raise ValueError("copy_envs: %s must hold integers, got dtype %s" % (name, a.dtype))
+        if d.ndim != 1:
+            raise ValueError("copy_envs: dst must be 1-D, got shape %r" % (d.shape,))
+        if s.ndim == 0:
+            s = np.full(d.shape, s)
+        if s.ndim != 1 or s.shape != d.shape:
+            raise ValueError("copy_envs: src and dst must be 1-D and equally long, got shapes %r and %r" % (s.shape, d.shape))
+        s = np.ascontiguousarray(s, np.int64)
+        d = np.ascontiguousarray(d, np.int64)
+        self._ck(self.lib.orl_batch_copy_envs(self._h, None if source is self else source._h, len(d), s.ctypes.data, d.ctypes.data,
+                                              1 if keep_rng else 0))
+
     def totals(self):
         p, a = C.c_int64(), C.c_int64()
         self._ck(self.lib.orl_batch_totals(self._h, C.byref(p), C.byref(a)))

@@ -345,6 +345,49 @@ class MultiDeviceBatch:
         self._map(lambda r: self.shards[r].matrix_observation_with_paths(out=out[self.bounds[r]:self.bounds[r + 1]]))
         return out
 
+    def copy_envs(self, src, dst, keep_rng=False):
+        """BatchedOpticalEnv.copy_envs with global env indices, inside this sharded batch.  The pairs are cut by the shards that own
+        them: a pair inside one shard is an in-place copy of that shard, a pair between two shards on one device a copy between
+        two batches.  Copies between GPUs are not supported: a pair whose shards sit on different devices raises ValueError
+        naming it, and every pair is checked — range and devices — before any shard queues anything.  (The
+        in-place rule of a single batch holds for the whole sharded batch: no env is a destination and the source of another pair.)"""
+        d = np.asarray(dst)
+        s = np.asarray(src)
+        if d.ndim != 1:
+            raise ValueError("copy_envs: dst must be 1-D, got shape %r" % (d.shape,))
+        if s.ndim == 0:
+            s = np.full(d.shape, s)
+        if s.ndim != 1 or s.shape != d.shape:
+            raise ValueError("copy_envs: src and dst must be 1-D and equally long, got shapes %r and %r" % (s.shape, d.shape))
+        for name, a in (("src", s), ("dst", d)):
+            if a.size and a.dtype.kind not in "iu":
+                raise ValueError("copy_envs: %s must hold integers, got dtype %s" % (name, a.dtype))
+        s, d = s.astype(np.int64), d.astype(np.int64)
+        for name, a in (("source", s), ("destination", d)):
+            bad = np.flatnonzero((a < 0) | (a >= self.num_envs))
+            if bad.size:
+                raise ValueError("copy_envs: pair %d: %s index %d outside [0, %d)" % (bad[0], name, a[bad[0]], self.num_envs))
+        if len(np.unique(d)) != len(d):
+            raise ValueError("copy_envs: a destination index occurs twice")
+        moved = s != d  # (src == dst pairs are no-ops, as in a single batch)
+        s, d = s[moved], d[moved]
+        both = np.intersect1d(s, d)
+        if both.size:  # (the rule of a single batch, for the whole sharded one: the shards' copies are not ordered with each other)
+            raise ValueError("copy_envs: env %d is the destination of one pair and the source of another; go through a scratch batch"
+                             % both[0])
+        rs = np.searchsorted(self.bounds, s, side="right") - 1
+        rd = np.searchsorted(self.bounds, d, side="right") - 1
+        dev = [getattr(sh, "device_id", 0) for sh in self.shards]
+        for p in range(len(d)):
+            if dev[rs[p]] != dev[rd[p]]:
+                raise ValueError("copy_envs: pair %d (%d -> %d) crosses devices (shard %d on device %d, shard %d on device %d): "
+                                 "copies between GPUs are not supported" % (p, s[p], d[p], rs[p], dev[rs[p]], rd[p], dev[rd[p]]))
+        for a in np.unique(rs):
+            for b in np.unique(rd[rs == a]):
+                sel = (rs == a) & (rd == b)
+                self.shards[b].copy_envs(s[sel] - self.bounds[a], d[sel] - self.bounds[b],
+                                         source=None if a == b else self.shards[a], keep_rng=keep_rng)
+
     def sync(self):
         self._map(lambda r: self.shards[r].sync())
 

@@ -288,7 +288,9 @@ class OpticalVecEnv:
         rates_only_info (opt-in; the reference's step() always fills every info entry, rmsa_env.py:228-264): when the info
         keywords are blocking rates only, the step kernel may skip the compactness entries and the two link means — then
         `info_array()` / `device_tensors()["info"]` hold NaN in those columns instead of stale values, and close() puts the
-        batch back into the full mode."""
+        batch back into the full mode.
+        Out of scope: `batch.copy_envs` under a VecEnv.  The host-side episode accumulators kept here (returns, lengths, the
+        episode log) do not follow a copy of env states on the device."""
         self.batch = batch
         self.num_envs = batch.num_envs
         self.obs_dtype = np.dtype(obs_dtype)

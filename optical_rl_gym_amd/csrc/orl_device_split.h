@@ -1227,6 +1227,9 @@ __device__ __forceinline__ void release_soon(const DevParams& P, EnvG& e, int la
       // insertion made the rebuilding wavefronts, which set this kernel's duration, compute-bound.  The exact times of
       // the chosen slots are re-read afterwards, and the horizon is a lower bound taken from the (NS+1)-th key (when
       // it does not lie beyond the clock, the loop below releases what the list holds and rebuilds again).
+      // The keys carry three absolute constants — the quantum, 128 time units behind the clock, 1 920 ahead of it — and
+      // the simulation has no time unit: what happens on the far side of each is in DESIGN section 2, "Time scales"
+      // (tests/timescale.py steps every route on both sides of all three).
       u32 kb[NS + 1];
 #pragma unroll
       for (int k = 0; k <= NS; k++) kb[k] = 0xffffffffu;
@@ -1252,15 +1255,25 @@ __device__ __forceinline__ void release_soon(const DevParams& P, EnvG& e, int la
         for (int k = 0; k < ORL_SCAN_BATCH; k++) {
           const double t = tt[k];
           const int i = base + 8 * k;
-          nd += (t <= e.now) ? 1 : 0;
+          const bool due_t = t <= e.now;
+          nd += due_t ? 1 : 0;
           const bool empty = (t == INF);
           top = empty ? top : i;  // i grows along the scan; slots beyond ev_hwm read as INF
           h1 = (empty && h0 != 0x7fffffff && h1 == 0x7fffffff) ? i : h1;
           h0 = (empty && h0 == 0x7fffffff) ? i : h0;
-          // time to release in 1/4096 units, offset by 2^19 so that overdue entries keep their order (a long
-          // inter-arrival gap leaves a dozen releases due at once), saturating at 2^23 - 1 (and for empty slots)
-          u32 q = (u32)__builtin_fmax(__builtin_fmin((t - e.now) * 4096.0 + 524288.0, 8388607.0), 0.0);
+          // time to release in 1/4096 units, offset by 2^19 so that overdue entries keep their order within 128 time units
+          // behind the clock (beyond that they share key 0 and lose it; NS + 1 of them in a lane make the horizon below -inf.
+          // They are due, so the chosen ones go into the list all the same and are released round by round, NS per lane and
+          // round, each round rebuilding - or by the serial path, when the step has more due releases than the sink takes).
+          // A pending release saturates at 2^23 - 2, about 1 920 time units ahead, ONE BELOW the key of an empty
+          // slot: it is a real entry that the horizon must stay in front of.  (While both read 2^23 - 1, a lane with
+          // fewer than NS + 1 nearer entries reported no horizon at all, and with holding times in the thousands — the
+          // reference's default is 10 800 — releases that were in nobody's list were found late, or never.)
+          u32 q = (u32)__builtin_fmax(__builtin_fmin((t - e.now) * 4096.0 + 524288.0, 8388606.0), 0.0);
           q = empty ? 8388607u : q;
+          // a due release sorts in front of every one that is not: t == now shares the quantum 2^19 with the releases of the
+          // next 1/4096 time unit, and when those fill the lane's NS places a due one among them was not chosen at all
+          q = (due_t && q > 524287u) ? 524287u : q;
           u32 x = (q << 8) | (u32)(ord + k);  // 8 ordinal bits: ev_cap <= 2048 (checked on the host)
 #pragma unroll
           for (int j = 0; j <= NS; j++) {  // sorted insertion: kb[] ascending
@@ -1280,12 +1293,19 @@ __device__ __forceinline__ void release_soon(const DevParams& P, EnvG& e, int la
         bt[k] = any ? e.ev_time[bi[k]] : INF;
       }
       // every slot this lane did not choose is no earlier than its (NS+1)-th key; two quanta lower covers the
-      // rounding of (t - now) * 4096 and of the sum below
+      // rounding of (t - now) * 4096 and of the sum below.  A saturated key bounds the horizon like any other (about
+      // now + 1 920: whatever it stands for is no earlier); only a lane with no (NS+1)-th entry at all has none
+      // (a chosen slot at or beyond the group's horizon stays out of the list, saturated or not, unless it is due: below)
       const u32 qn = kb[NS] >> 8;
       const double T_lane = (qn >= 8388607u) ? INF : (qn < 2u ? -INF : e.now + ((double)qn - 524290.0) * (1.0 / 4096.0));
       const double T = g8::g8_min(T_lane);
+      // A chosen slot that is due goes into the list even at or beyond the horizon: it is released in this very round.  The
+      // horizon lies up to three quanta below the (NS+1)-th entry, so where a lane holds NS + 1 releases within three quanta
+      // of the clock (mean times of a few quanta and less) it is not beyond the clock, and a release due between it and
+      // the clock was in no list; a round that had released from the list before stopped with that one still pending.
+      // Due releases have the lowest keys of their lane, so every round takes at least one per lane that has any.
 #pragma unroll
-      for (int k = 0; k < NS; k++) { st[k] = bt[k] < T ? bt[k] : INF; si[k] = bi[k]; }
+      for (int k = 0; k < NS; k++) { st[k] = (bt[k] < T || bt[k] <= e.now) ? bt[k] : INF; si[k] = bi[k]; }
       e.t_soon = T;
       dirty = (1 << NS) - 1;
       due_all = g8_sum(nd);
@@ -1316,7 +1336,9 @@ __device__ __forceinline__ void release_soon(const DevParams& P, EnvG& e, int la
     const int tot = g8_sum(ndl);
     if (tot == 0) {
       if (e.now < e.t_soon) break;
-      if (round > 0 || due_all >= 0) {  // nothing below the horizon is due although the clock passed it: equal times
+      // nothing is due (the rebuild puts every due release it chose into the list) although the clock passed the horizon:
+      // NS + 1 releases of one lane within three quanta ahead of the clock
+      if (round > 0 || due_all >= 0) {
         if (!sink.active) { ORL_DBG(8, 1); ORL_DBG(9, e.now < e.t_soon ? 0 : 1); ORL_DBG(10, due_all > 0 ? 1 : 0); sink.deferred = true; return; }
         break;
       }

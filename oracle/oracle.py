@@ -176,6 +176,7 @@ class OracleBatch:
         st = mt_states(seeds) if mt_state is None else mt_state
         self.h = self.lib.orc_create(C.byref(cfg), C.byref(tb), self.n, st.ctypes.data)
         self.C, self.E, self.S, self.k = cores, E, S, k
+        self.load, self.mean_service_holding_time = load, mht
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -189,6 +190,17 @@ class OracleBatch:
     def set_paths(self, paths):
         p = np.ascontiguousarray(np.asarray(paths).reshape(self.n), np.int32)
         self.lib.orc_set_paths(self.h, p.ctypes.data)
+
+    def set_load(self, load=None, mean_service_holding_time=None):
+        """set_load of every env (optical_network_env.py:76-94): a given value replaces the batch's, the mean inter-arrival time
+        follows from the two."""
+        if load is not None:
+            self.load = load
+        if mean_service_holding_time is not None:
+            self.mean_service_holding_time = mean_service_holding_time
+        miat = 1 / float(self.load / float(self.mean_service_holding_time))
+        self.lib.orc_set_rates.argtypes = [C.c_void_p, C.c_double, C.c_double]
+        self.lib.orc_set_rates(self.h, miat, float(self.mean_service_holding_time))
 
     def seed(self, seeds, mask=None):
         """env.seed(seed) of the selected envs (optical_network_env.py:205-210)."""

@@ -1168,6 +1168,12 @@ void orc_get_service(orc_batch* b, double* out /*[n][6]: at, ht, src, dst, bit_r
     o[0] = s->at; o[1] = s->ht; o[2] = s->src; o[3] = s->dst; o[4] = s->bit_rate; o[5] = s->id;
   }
 }
+/* set_load (optical_network_env.py:76-94): the two means of the services drawn from now on; the pending service and everything
+   else stay */
+void orc_set_rates(orc_batch* b, double mean_iat, double mean_ht) {
+  b->cfg.mean_iat = mean_iat;
+  b->cfg.mean_ht = mean_ht;
+}
 void orc_get_counters(orc_batch* b, int64_t* out /*[n][8]*/) {
   int64_t i;
   for (i = 0; i < b->n_envs; i++) {

@@ -330,3 +330,56 @@ def _exact_bits(name):
         ok = np.array_equal(got, exp)
         assert ok, "%s: step %d: %s differs (floats as bit patterns)\n got %r\n exp %r" % (name, t, what, got, exp)
     return check
+
+
+# ---- the set_load fixtures (tests/golden/s1_*.npz): shared by tests/test_set_load_gpu.py (device) and tests/test_timescale.py (oracle)
+S1 = {"RMSA": "s1_rmsa_set_load", "DeepRMSA": "s1_deeprmsa_set_load", "RWA": "s1_rwa_set_load", "RMCSA": "s1_rmcsa_set_load",
+      "QoSConstrainedRA": "s1_qos_set_load"}
+
+
+def _schedule(g):
+    return {int(k): v for k, v in json.loads(str(g["schedule"])).items()}
+
+
+def _replay_with_schedule(env, g, check, set_load=None):
+    """tests.helpers.replay / replay_q with env.set_load(**schedule[t]) before the action of step t is decided (where the
+    fixture's policy closure called the reference's set_load)."""
+    meta, sched = g["meta"], _schedule(g)
+    qos = meta["env"] == "QoSConstrainedRA"
+    set_load = set_load or (lambda **ch: env.set_load(**ch))
+    for t in range(meta["n_steps"]):
+        if g["reset_before"][t]:
+            env.reset(full=False)
+        check(t, "svc", env.services()[0], g["svc"][t])
+        if "obs" in g:
+            check(t, "obs", env.observation()[0], g["obs"][t])
+        if t in sched:
+            set_load(**sched[t])
+            check(t, "svc after set_load", env.services()[0], g["svc"][t])
+        a = env.policy(meta["policy"])
+        width = g["actions"].shape[1]
+        check(t, "action", np.asarray(a[0, :width], np.int64), g["actions"][t])
+        _, reward, done, info = env.step(a)
+        check(t, "reward", reward[0], g["reward"][t])
+        check(t, "done", int(done[0]), int(g["done"][t]))
+        check(t, "info", info[0, : g["info"].shape[1]], g["info"][t])
+        check(t, "n_active", env.n_active(0), int(g["n_active"][t]))
+        if qos:
+            check(t, "counters", env.counters()[0, :4], g["counters"][t][:4])
+            check(t, "spectrum", env.spectrum(0), g["spectrum"][t])
+        else:
+            check(t, "counters", env.counters()[0], g["counters"][t])
+            sl = env.slots(0)
+            sl = sl[0] if sl.shape[0] == 1 else sl
+            check(t, "crc", crc_slots(sl), int(g["crc"][t]))
+        if (t + 1) in meta["snapshot_steps"]:
+            ls = env.link_stats(0)
+            ref = g["snap%d_link_stats" % (t + 1)]
+            if qos:
+                check(t, "utilization", ls[0], ref[0])
+                check(t, "last_update", ls[3], ref[3])
+            else:
+                check(t, "snap_slots", np.packbits(sl, axis=-1, bitorder="little"), g["snap%d_slots" % (t + 1)])
+                check(t, "snap_link_stats", ls, ref)
+                check(t, "snap_net_stats", env.net_stats(0), g["snap%d_net_stats" % (t + 1)])
+    check(meta["n_steps"], "svc", env.services()[0], g["svc"][meta["n_steps"]])

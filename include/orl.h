@@ -189,7 +189,18 @@ int orl_batch_reseed(orl_batch* b, const int64_t* seeds, const uint8_t* env_mask
  * log of `capacity` episodes (0 = disarm); from then on every env that finishes an episode appends its
  * episode_services_accepted — the episode's reward sum for RMSA / RWA / RMCSA (reward 1 per accepted service), and
  * 2 * accepted - steps for DeepRMSA (reward +1 / -1) — before the auto (soft) reset.  Read it back with
- * orl_batch_get_episode_log: counts[n_envs], accepted[n_envs][capacity]. */
+ * orl_batch_get_episode_log: counts[n_envs], accepted[n_envs][capacity].
+ *
+ * A full log: counts[i] goes on counting every episode env i finishes, beyond `capacity`; row i holds the first `capacity`
+ * episodes in the order they finished (entries behind min(counts[i], capacity) are 0); an episode that finishes after the row is
+ * full is written nowhere — not over an earlier entry, not into another env's row.  So counts[i] > capacity says that
+ * counts[i] - capacity episodes were dropped.  The same holds for the reward sums of orl_batch_get_episode_rewards.
+ * Every route logs: device-resident runs (whatever the run plan) and host-driven steps through every step kernel.  A step without
+ * auto reset logs the episode when it returns done, once: an env stepped on without a reset never reports done again.
+ * Arming clears counts and rows, also when the log was armed before (with this or another capacity: the row stride is the
+ * armed capacity); the episode in progress keeps the accepted services it has — the kernels log the env's own
+ * episode_services_accepted — while the reward sums of QoSConstrainedRA start at 0.0 with the arming, so arm at an episode's start.
+ * Disarmed (capacity 0) nothing is logged and orl_batch_get_episode_log is refused (ORL_E_INVALID). */
 int orl_batch_episode_log(orl_batch* b, int32_t capacity);
 int orl_batch_get_episode_log(orl_batch* b, int32_t* counts, int32_t* accepted);
 /* QoSConstrainedRA (reward = the accepted service's class reward, qos_constrained_ra.py:131-136): the harness's episode_reward of

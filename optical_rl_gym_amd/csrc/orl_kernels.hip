@@ -1137,7 +1137,7 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
   sp::SvcBuf svb;
   svb.q = 0.0; svb.ht = 0.0; svb.pk = 0u; svb.cnt = 0;
   sp::StepCarry C;  // + the descriptor; DS: the episode step counter (SC_ESP; the replay keeps the record's copy), RMCSA: the core of
-                    // the last accepted provision (the high half of SC_ACC); RD: events logged in this launch; RW: steps handed over
+                    // the last accepted provision (the high half of SC_ACC while its update is pending, else unused: 0); RD: events logged in this launch; RW: steps handed over
   C.soon = SR ? &soon_c : nullptr;
   C.svc = SVC ? &svb : nullptr;
   u64 now0_w = 0ull;    // DS: the clock the launch starts at (logged for the replay)
@@ -1146,7 +1146,10 @@ __device__ __forceinline__ void persist_body(const DevParams& P, int pol, int ta
     C.desc = valid ? P.svc_desc[env] : 0ull;                                                                \
     if (DS && valid && step < target) {                                                                     \
       C.esp = (int)P.scal[env * ORL_SCAL_WORDS + SC_ESP];                                                   \
-      if (ENV == ENV_RMCSA) C.prev_core = (int)((P.scal[env * ORL_SCAL_WORDS + SC_ACC] >> 32) & 31ull);     \
+      if (ENV == ENV_RMCSA) {  /* (a record without a pending update holds the core of its last ACTION: the reject index C) */ \
+        const u64 acc_ = P.scal[env * ORL_SCAL_WORDS + SC_ACC];                                             \
+        C.prev_core = (acc_ & 2ull) ? (int)((acc_ >> 32) & 31ull) : 0;                                      \
+      }                                                                                                     \
       now0_w = P.scal[env * ORL_SCAL_WORDS + SC_NOW];                                                       \
     }                                                                                                       \
     if (SVC && valid && step < target) {                                                                    \

@@ -77,6 +77,17 @@ def derive_rates(load, mean_service_holding_time):
 
 
 
+def refuse_endless_episodes(steps_per_episode, episode_length):
+    """evaluate() plays until `done`: ValueError where an episode of the configuration can never end.  The soft reset in front of
+    every episode of the harness (utils.py:103-141) counts the pending service (rmsa_env.py:314, rmcsa_env.py:414), and `done` is
+    episode_services_processed == episode_length after the next one was counted: with episode_length=1 the counter stands at 1
+    when the episode starts and never equals it again — the reference harness would loop forever."""
+    if steps_per_episode < 1:
+        raise ValueError("evaluate: with episode_length=%r an episode of this env family never returns done (the soft reset that "
+                         "starts an episode already counts the pending service), so no number of steps finishes one; use "
+                         "episode_length >= %d" % (episode_length, episode_length - steps_per_episode + 1))
+
+
 class _PinnedBlock:
     """Owner of one page-locked host allocation (orl_host_alloc); numpy views keep it alive through their base chain."""
 
@@ -579,6 +590,7 @@ class BatchedOpticalEnv:
         accounting (reset -> loop until done -> sum of rewards): returns (episode_rewards [num_envs, n_eval_episodes],
         episode_lengths).  One device-resident run; the kernels log each finished episode."""
         n = int(n_eval_episodes)
+        refuse_endless_episodes(self.steps_per_episode(), self.episode_length)  # (before the batch is touched)
         self._ck(self.lib.orl_batch_reset(self._h, 0, None))  # the harness's reset() before the first episode (soft)
         self._ck(self.lib.orl_batch_episode_log(self._h, n))
         L = self.steps_per_episode()

@@ -282,9 +282,42 @@ def random_actions(seed, n, k, s, *, extra=()):
     return acts
 
 
+def edge_episode_lengths():
+    """G10: episode lengths at the edge.  RMSA, DeepRMSA and RMCSA count a service at creation and again in the soft reset
+    (rmsa_env.py:280, 314, 576): episode_length=2 gives one-step episodes, 3 two-step ones, and 1 never returns done.  RWA
+    counts at the decision (rwa_env.py:135-136, 160): episode_length=1 makes every step terminal.  (QoSConstrainedRA:
+    gen_golden_qos.py.)  `python gen_golden.py edges` records these alone and leaves every other fixture as it is."""
+    nsf = load_topology("nsfnet_chen")
+    for el in (1, 2, 3):
+        kw = dict(seed=21, allow_rejection=True, load=120, mean_service_holding_time=25, episode_length=el, num_spectrum_resources=64)
+        env = gym.make("RMSA-v0", topology=nsf, **kw)
+        run_trace("g10_rmsa_len%d_sapff" % el, env, policy=rmsa_env.shortest_available_path_first_fit, n_steps=48, info_keys=RMSA_INFO,
+                  snapshot_every=16, meta=dict(env="RMSA", topology="nsfnet_chen", kwargs=kw, policy="SAP_FF"))
+        kw = dict(seed=22, allow_rejection=True, mean_service_holding_time=7.5, mean_service_inter_arrival_time=1.0 / 12.0, j=2,
+                  episode_length=el, num_spectrum_resources=64)
+        env = gym.make("DeepRMSA-v0", topology=nsf, **kw)
+        run_trace("g10_deeprmsa_len%d_sap" % el, env, policy=deeprmsa_env.shortest_available_path_first_fit, n_steps=48,
+                  info_keys=RMSA_INFO, obs_fn=lambda e: e.observation(), snapshot_every=16,
+                  meta=dict(env="DeepRMSA", topology="nsfnet_chen", kwargs=kw, policy="SAP"))
+    for el in (1, 2):
+        kw = dict(seed=23, allow_rejection=True, load=450, mean_service_holding_time=25, episode_length=el, num_spectrum_resources=16)
+        env = gym.make("RWA-v0", topology=nsf, **kw)
+        run_trace("g10_rwa_len%d_sapff" % el, env, policy=rwa_env.shortest_available_path_first_fit, n_steps=48, info_keys=RWA_INFO,
+                  snapshot_every=16, vec_info_keys=("path_action_probability", "wavelength_action_probability"),
+                  meta=dict(env="RWA", topology="nsfnet_chen", kwargs=kw, policy="SAP_FF"))
+    kw = dict(seed=24, allow_rejection=True, load=250, mean_service_holding_time=25, episode_length=2, num_spectrum_resources=64,
+              num_spatial_resources=7, worst_xt=-84.7)
+    env = gym.make("RMCSA-v0", topology=load_topology("nsfnet_chen"), **kw)
+    run_trace("g10_rmcsa_len2_sapff", env, policy=rmcsa_env.shortest_available_path_best_modulation_first_core_first_fit, n_steps=48,
+              info_keys=RMCSA_INFO, snapshot_every=16, meta=dict(env="RMCSA", topology="nsfnet_chen", kwargs=kw, policy="SAP_BM_FC_FF"))
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     os.makedirs(DATA, exist_ok=True)
+    if sys.argv[1:] == ["edges"]:
+        edge_episode_lengths()
+        return
     nsf = load_topology("nsfnet_chen")
     ger = load_topology("germany50")
     flatten_topology(nsf, "nsfnet_chen_5-paths_6-modulations")
@@ -405,6 +438,7 @@ def main():
     run_trace("g6_rmcsa_random_actions", env, actions=random_actions(4321, 2000, 5, 100, extra=(6, 7)),
               n_steps=2000, info_keys=RMCSA_INFO, snapshot_every=500,
               meta=dict(env="RMCSA", topology="nsfnet_chen", kwargs=kw, policy="ACTIONS"))
+    edge_episode_lengths()
 
 
 if __name__ == "__main__":

@@ -383,3 +383,49 @@ def _replay_with_schedule(env, g, check, set_load=None):
                 check(t, "snap_link_stats", ls, ref)
                 check(t, "snap_net_stats", env.net_stats(0), g["snap%d_net_stats" % (t + 1)])
     check(meta["n_steps"], "svc", env.services()[0], g["svc"][meta["n_steps"]])
+
+
+# ---- full, masked and soft resets between runs (tests/test_gpu_parity.py in the library's own form, tests/test_run_plans_gpu.py in
+# every form of the persistent kernel with the batch in two halves)
+def resets_between_runs(dev, ora, policy, masks, chk, sample, after_run=None):
+    """reset(only_episode_counters=False) after stepping, for all envs and for a mask of envs, and masked soft resets
+    (rmsa_env.py:284-359, rwa_env.py:164-208, rmcsa_env.py:386-483): full masked reset (masks[0]) after a run, run, host steps, full
+    reset, run, soft masked reset (masks[1]), run — the batch keeps equal to the oracle.  Counters, pending service and pending
+    releases of every env; slot maps and statistics of the envs in `sample`.  after_run() is called after every device-resident run."""
+    n = dev.num_envs
+
+    def compare(tag):
+        chk(tag, "counters", dev.counters(), ora.counters())
+        chk(tag, "services", dev.services(), ora.services())
+        chk(tag, "active", dev.active(), np.array([ora.n_active(i) for i in range(n)]))
+        for e in sample:
+            chk(tag, "slots", dev.slots(e), ora.slots(e))
+            chk(tag, "link_stats", dev.link_stats(e), ora.link_stats(e))
+            chk(tag, "net_stats", dev.net_stats(e), ora.net_stats(e))
+        if dev.obs_dim:
+            chk(tag, "obs", dev.observation(), ora.observation())
+
+    def run(steps):
+        dev.run(policy, steps); ora.run(policy, steps)
+        if after_run is not None:
+            after_run(steps)
+
+    run(130)
+    dev.reset(full=True, mask=masks[0]); ora.reset(full=True, mask=masks[0])
+    compare(1)
+    run(90)
+    compare(2)
+    for t in range(40):  # host-driven steps after a masked full reset
+        a_o, a_d = ora.policy(policy), dev.policy(policy)
+        chk(t, "actions", a_d, a_o)
+        _, r_o, d_o, i_o = ora.step(a_o, auto_reset=True)
+        _, r_d, d_d, i_d = dev.step(a_d, auto_reset=True)
+        chk(t, "reward", r_d, r_o); chk(t, "done", d_d, d_o); chk(t, "info", i_d, i_o)
+    dev.reset(full=True); ora.reset(full=True)
+    compare(3)
+    run(70)
+    dev.reset(full=False, mask=masks[1]); ora.reset(full=False, mask=masks[1])
+    compare(4)
+    run(60)
+    compare(5)
+    assert not dev.flags().any()

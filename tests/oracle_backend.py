@@ -2,7 +2,7 @@
 `-m "not gpu"` suite.  Test infrastructure only."""
 import numpy as np
 
-from optical_rl_gym_amd.envs import RMSA_INFO_KEYS
+from optical_rl_gym_amd.envs import RMSA_INFO_KEYS, refuse_endless_episodes
 from optical_rl_gym_amd.topology import Topology
 from oracle.oracle import OracleBatch
 
@@ -40,6 +40,7 @@ class OracleBackend(OracleBatch):
         """Same contract as BatchedOpticalEnv.evaluate, by stepping the oracle."""
         n = int(n_eval_episodes)
         L = self.episode_length if self.ENV_TYPE == 2 else self.episode_length - 1
+        refuse_endless_episodes(L, self.episode_length)
         super().reset(full=False)
         rewards = np.zeros((self.n, n))
         for ep in range(n):

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import IMPL_ENV, IMPLS, _exact, _ran_pair_form, force_impl  # noqa: F401  (other test modules import them from here)
-from tests.helpers import golden_names, load_golden, replay, replay_h, replay_q, replay_w
+from tests.helpers import golden_names, load_golden, replay, replay_h, replay_q, replay_w, resets_between_runs
 
 pytestmark = pytest.mark.gpu
 
@@ -1182,41 +1182,9 @@ def test_full_and_masked_resets_match_oracle(gname, policy):
     seeds = [4000 + 3 * i for i in range(n)]
     ora = OracleBatch(meta["env"], meta["topology"], seeds, **kw)
     dev = _product(dict(meta, kwargs=dict(kw, seed=0)), num_envs=n, seeds=seeds)
-    chk = _exact(gname)
     rs = np.random.RandomState(11)
-
-    def compare(tag):
-        chk(tag, "counters", dev.counters(), ora.counters())
-        chk(tag, "services", dev.services(), ora.services())
-        chk(tag, "active", dev.active(), np.array([ora.n_active(i) for i in range(n)]))
-        for e in (0, 17, n - 1):
-            chk(tag, "slots", dev.slots(e), ora.slots(e))
-            chk(tag, "link_stats", dev.link_stats(e), ora.link_stats(e))
-            chk(tag, "net_stats", dev.net_stats(e), ora.net_stats(e))
-        if dev.obs_dim:
-            chk(tag, "obs", dev.observation(), ora.observation())
-
-    dev.run(policy, 130); ora.run(policy, 130)
-    mask = (rs.random_sample(n) < 0.4).astype(np.uint8)
-    dev.reset(full=True, mask=mask); ora.reset(full=True, mask=mask)
-    compare(1)
-    dev.run(policy, 90); ora.run(policy, 90)
-    compare(2)
-    for t in range(40):  # host-driven steps after a masked full reset
-        a_o, a_d = ora.policy(policy), dev.policy(policy)
-        chk(t, "actions", a_d, a_o)
-        _, r_o, d_o, i_o = ora.step(a_o, auto_reset=True)
-        _, r_d, d_d, i_d = dev.step(a_d, auto_reset=True)
-        chk(t, "reward", r_d, r_o); chk(t, "done", d_d, d_o); chk(t, "info", i_d, i_o)
-    dev.reset(full=True); ora.reset(full=True)
-    compare(3)
-    dev.run(policy, 70); ora.run(policy, 70)
-    mask = (rs.random_sample(n) < 0.5).astype(np.uint8)
-    dev.reset(full=False, mask=mask); ora.reset(full=False, mask=mask)
-    compare(4)
-    dev.run(policy, 60); ora.run(policy, 60)
-    compare(5)
-    assert not dev.flags().any()
+    masks = [(rs.random_sample(n) < 0.4).astype(np.uint8), (rs.random_sample(n) < 0.5).astype(np.uint8)]  # (in the order they are used)
+    resets_between_runs(dev, ora, policy, masks, _exact(gname), sample=(0, 17, n - 1))
     dev.close()
 
 

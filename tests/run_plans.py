@@ -96,6 +96,13 @@ PLANS = [("128", 1), ("128", 2), ("1", 2), ("L", 2), ("L-1", 2), ("L+1", 1), ("7
 FORMS = ["persist", "persist_global", "persist_lds", "persist_pair", "persist_rd"]
 PAIR_CONFIGS = ("rmsa", "deeprmsa")  # the two-wavefront form needs a specialisation build per configuration
 assert set(FORMS) <= set(IMPLS)
+# the forms a family is built in, where that is not all of them: RMCSA has neither the LDS-resident nor the rows-deferred form (asked
+# for, the library's own choice runs), and its "persist_pair" is the one-wavefront kernel, specialised
+FAMILY_FORMS = {"RMCSA": ("persist", "persist_global", "persist_pair")}
+
+
+def forms_of_family(fam):
+    return FAMILY_FORMS.get(fam, tuple(FORMS))
 
 
 def chunk_of(plan, L):

@@ -367,23 +367,41 @@ void orl_multi_destroy(orl_multi* m);
 
 /* Action masks of the pending service — what the next step() acts on, after any reset / step / policy_step / run / set_state,
  * auto resets included — for every env, computed on the device next to the slot maps (sb3-contrib's MaskablePPO reads them
- * through `action_masks()`; a torch agent fills the masked logits with -inf).  RMSA, DeepRMSA and RWA; RMCSA and
- * QoSConstrainedRA return ORL_E_INVALID.  Per env a row of `dim` bytes, 0 or 1; the last column is the reject action and equals
- * allow_rejection.  Layouts: */
+ * through `action_masks()`; a torch agent fills the masked logits with -inf).  RMSA, DeepRMSA and RWA take ORL_MASK_JOINT /
+ * ORL_MASK_PATH, RMCSA the two-stage pair ORL_MASK_PATH_MOD / ORL_MASK_CORE_SLOT; any other combination and QoSConstrainedRA
+ * return ORL_E_INVALID.  Per env a row of `dim` bytes, 0 or 1; the last column is the reject action and equals allow_rejection.
+ * Layouts: */
 #define ORL_MASK_JOINT 0 /* RMSA / RWA: dim = k*S + 1, column i < dim-1 = action (i / S, i % S) (path, first slot / wavelength);
                           * DeepRMSA: dim = k*j + 1, column i = action i.  1 iff stepping that action provisions the service:
                           * rmsa_env.py:163-200 with is_path_free :623-636; deeprmsa_env.py:48-58 with get_available_blocks
                           * rmsa_env.py:667-697; rwa_env.py:101-135.  A path index >= n_paths[src, dst] is 0 (IndexError there). */
 #define ORL_MASK_PATH 1  /* PathOnlyFirstFitAction (RMSA / RWA): dim = k + 1, column p = the wrapper's first fit finds a slot on
                           * path p — RMSA searches range(0, S - n) (rmsa_env.py:848-871), RWA every wavelength (rwa_env.py:518-533). */
+/* RMCSA: an action is (path p, modulation m, core c, first slot s), and stepping it provisions — prov(p, m, c, s) — iff, with
+ * n = n_slots[bit rate][m]: p < n_paths[src, dst], m < M, c < C, s + n <= S (s = S - n is valid), slots s .. s + n - 1 are free in
+ * core c on every hop, and length(p) < lmax_xt[m] and length(p) < lmax_snr[m][bit rate] (rmcsa_env.py:209-289 with is_path_free
+ * :767-794, get_number_slots :753-765, _crosstalk_is_acceptable :341-384).  A flat mask would have k*M*C*S columns; validity
+ * factorises exactly into the two rows a two-head or autoregressive policy masks its logits with: sampling stage 1, then stage
+ * 2 for the sampled pair, never yields a blocked action while a provisioning one exists. */
+#define ORL_MASK_PATH_MOD 2  /* RMCSA, stage 1: dim = k*M + 1, column p*M + m = 1 iff some (c, s) has prov(p, m, c, s). */
+#define ORL_MASK_CORE_SLOT 3 /* RMCSA, stage 2: dim = C*S + 1, column c*S + s = prov(p, m, c, s) for a pair (p, m) given per env:
+                              * columns 0 and 1 of the env's row of ORL_BUF_ACTIONS (where an agent on the GPU writes its stage-1
+                              * choice), or the `given` of orl_batch_action_mask_given.  A pair out of range (negative included)
+                              * or beyond reach has no provisioning column.  The mask never touches env state or flags. */
 /* Fallback: a row without a provisioning column gets, when allow_rejection == 0, every non-reject column set — every action of
  * the space then has the same effect (rejection) and a masked categorical never meets a row of -inf only.
  * orl_batch_action_mask_shape: *dim and the device pitch round_up(dim, 16) of ORL_BUF_ACTION_MASK's rows for `layout`.
  * orl_batch_action_mask: one launch on the batch's stream into ORL_BUF_ACTION_MASK (no synchronisation, graph-capturable: the
  * buffer is allocated by the first call, which should therefore come before a capture); with out != NULL ([n_envs][dim] bytes)
- * the rows are then copied out densely and the call synchronises. */
+ * the rows are then copied out densely and the call synchronises.
+ * orl_batch_action_mask_given: the same with the pairs of ORL_MASK_CORE_SLOT from the host — `given` [n_envs][2] int32 (path,
+ * modulation) goes through a page-locked buffer of the batch into a device buffer of the batch, asynchronously on the batch's
+ * stream (both allocated by the first such call); ORL_BUF_ACTIONS is not touched.  given == NULL: orl_batch_action_mask.  A `given`
+ * with another layout is ORL_E_INVALID.  A configuration whose rows exceed the kernel's LDS budget (none with k <= 8) is refused
+ * with ORL_E_INVALID before anything is queued. */
 int orl_batch_action_mask_shape(const orl_batch* b, int layout, int32_t* dim, int32_t* pitch);
 int orl_batch_action_mask(orl_batch* b, int layout, uint8_t* out);
+int orl_batch_action_mask_given(orl_batch* b, int layout, const int32_t* given /* host [n_envs][2], or NULL = ORL_BUF_ACTIONS */, uint8_t* out);
 
 /* MatrixObservationWithPaths (qos_constrained_ra.py:440-493) of the pending service of every env, built on the device from the
  * link counters: QoSConstrainedRA only (other families return ORL_E_INVALID).  Per env a row of dim = links * S * (k + 1) + 1

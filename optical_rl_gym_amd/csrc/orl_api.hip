@@ -695,6 +695,8 @@ extern "C" void orl_batch_destroy(orl_batch* b) try {
   if (b->h_tail) hipHostFree(b->h_tail);
   if (b->h_actions) hipHostFree(b->h_actions);
   if (b->h_copy_idx) hipHostFree(b->h_copy_idx);
+  if (b->h_mask_given) hipHostFree(b->h_mask_given);
+  if (b->ev_given_up) hipEventDestroy(b->ev_given_up);
   if (b->ev_copy_up) hipEventDestroy(b->ev_copy_up);
   if (b->ev_copy) hipEventDestroy(b->ev_copy);
   if (b->spec_handle) dlclose(b->spec_handle);
@@ -1144,8 +1146,9 @@ ORL_ABI_CATCH_INT
 static int64_t qos_obs_dim(const DevParams& P) { return (int64_t)P.E * P.S * (P.K + 1) + 1; }
 static int64_t qos_obs_pitch(const DevParams& P) { return (qos_obs_dim(P) + 15) / 16 * 16; }
 
-// action masks (orl_mask.h): row length of `layout` for this batch's family, 0 = not supported
+// action masks (orl_mask.h, orl_rmcsa_mask.h): row length of `layout` for this batch's family, 0 = not supported
 static int mask_dim(const DevParams& P, int layout) {
+  if (P.env_type == ENV_RMCSA) return layout == ORL_MASK_PATH_MOD ? P.K * P.M + 1 : (layout == ORL_MASK_CORE_SLOT ? P.C * P.S + 1 : 0);
   if (P.env_type != ENV_RMSA && P.env_type != ENV_DEEPRMSA && P.env_type != ENV_RWA) return 0;
   if (layout == ORL_MASK_JOINT) return P.K * (P.env_type == ENV_DEEPRMSA ? P.J : P.S) + 1;
   if (layout == ORL_MASK_PATH && P.env_type != ENV_DEEPRMSA) return P.K + 1;
@@ -1203,9 +1206,12 @@ ORL_ABI_CATCH_INT
 
 static int mask_check(const orl_batch* b, int layout) {
   const int t = b->P.env_type;
-  if (t == ENV_RMCSA || t == ENV_QOS)
-    return fail(ORL_E_INVALID, "action masks are not available for %s (RMSA, DeepRMSA and RWA only)", t == ENV_RMCSA ? "RMCSA" : "QoSConstrainedRA");
-  if (layout != ORL_MASK_JOINT && layout != ORL_MASK_PATH) return fail(ORL_E_INVALID, "unknown action-mask layout %d", layout);
+  if (t == ENV_QOS) return fail(ORL_E_INVALID, "action masks are not available for QoSConstrainedRA (RMSA, DeepRMSA, RWA and RMCSA only)");
+  if (layout < ORL_MASK_JOINT || layout > ORL_MASK_CORE_SLOT) return fail(ORL_E_INVALID, "unknown action-mask layout %d", layout);
+  const bool two_stage = layout == ORL_MASK_PATH_MOD || layout == ORL_MASK_CORE_SLOT;
+  if (t == ENV_RMCSA && !two_stage)
+    return fail(ORL_E_INVALID, "the joint and path action masks are not available for RMCSA: use ORL_MASK_PATH_MOD and ORL_MASK_CORE_SLOT");
+  if (t != ENV_RMCSA && two_stage) return fail(ORL_E_INVALID, "ORL_MASK_PATH_MOD and ORL_MASK_CORE_SLOT are defined for RMCSA only");
   if (!mask_dim(b->P, layout)) return fail(ORL_E_INVALID, "DeepRMSA has no path-only action space: use ORL_MASK_JOINT");
   return ORL_OK;  // (DeepRMSA: a path's blocks are bits of one u64, and batch_create_impl admits j <= 8)
 }
@@ -1219,19 +1225,52 @@ extern "C" int orl_batch_action_mask_shape(const orl_batch* b, int layout, int32
 }
 ORL_ABI_CATCH_INT
 
-extern "C" int orl_batch_action_mask(orl_batch* b, int layout, uint8_t* out) try {
+// ORL_MASK_CORE_SLOT: the caller's (path, modulation) pairs through the batch's page-locked buffer into its device buffer [B][2],
+// queued on the batch's stream; the actions buffer is not touched
+static int upload_mask_given(orl_batch* b, const int32_t* given) {
+  const size_t bytes = (size_t)b->P.B * 2 * sizeof(int32_t);
+  if (!b->mask_given) {
+    HIPCHK(hipMalloc((void**)&b->mask_given, bytes));
+    b->allocs.push_back(b->mask_given);
+    HIPCHK(hipHostMalloc((void**)&b->h_mask_given, bytes, hipHostMallocPortable));
+    HIPCHK(hipEventCreateWithFlags(&b->ev_given_up, hipEventDisableTiming));
+  } else {
+    HIPCHK(hipEventSynchronize(b->ev_given_up));  // (the last call's upload has left the staging buffer)
+  }
+  memcpy(b->h_mask_given, given, bytes);
+  HIPCHK(hipMemcpyAsync(b->mask_given, b->h_mask_given, bytes, hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipEventRecord(b->ev_given_up, b->stream));
+  return ORL_OK;
+}
+
+extern "C" int orl_batch_action_mask_given(orl_batch* b, int layout, const int32_t* given, uint8_t* out) try {
   if (!b) return fail(ORL_E_INVALID, "null argument");
   if (int rc = mask_check(b, layout)) return rc;
+  if (given && layout != ORL_MASK_CORE_SLOT) return fail(ORL_E_INVALID, "`given` belongs to ORL_MASK_CORE_SLOT only");
   HIPCHK(hipSetDevice(b->device));
   const int dim = mask_dim(b->P, layout), pitch = (dim + 15) / 16 * 16;
   const i64 B = b->P.B;
+  const bool rmcsa = b->P.env_type == ENV_RMCSA;
+  if (rmcsa && ORL_LAUNCH(rmcsa_mask, b, layout, nullptr, pitch, nullptr, 0))  // (out == nullptr: the check alone, before anything is allocated or queued)
+    return fail(ORL_E_INVALID, "RMCSA action masks of k = %d paths, %d modulations, %d cores x %d slots exceed the kernel's LDS budget", b->P.K,
+                b->P.M, b->P.C, b->P.S);
   unsigned char*& buf = b->mask_buf[layout];  // one buffer per layout: a device view of one layout's rows never sees the other's
   if (!buf) {
     HIPCHK(hipMalloc((void**)&buf, (size_t)(B * (int64_t)pitch)));
     b->allocs.push_back(buf);
   }
-  if (ORL_LAUNCH(action_mask, b, layout, buf, pitch))
+  if (rmcsa) {
+    const int* src = b->P.actions;  // columns 0 and 1 of ORL_BUF_ACTIONS: where an agent on the GPU writes its stage-1 choice
+    int stride = 4;
+    if (given) {
+      if (int rc = upload_mask_given(b, given)) return rc;
+      src = b->mask_given;
+      stride = 2;
+    }
+    ORL_LAUNCH(rmcsa_mask, b, layout, buf, pitch, src, stride);
+  } else if (ORL_LAUNCH(action_mask, b, layout, buf, pitch)) {
     return fail(ORL_E_INVALID, "action masks of k = %d paths x %d columns exceed the kernel's LDS budget", b->P.K, dim - 1);
+  }
   HIPCHK(hipGetLastError());
   b->mask_last = layout;
   if (out) {
@@ -1241,6 +1280,8 @@ extern "C" int orl_batch_action_mask(orl_batch* b, int layout, uint8_t* out) try
   return ORL_OK;
 }
 ORL_ABI_CATCH_INT
+
+extern "C" int orl_batch_action_mask(orl_batch* b, int layout, uint8_t* out) { return orl_batch_action_mask_given(b, layout, nullptr, out); }
 
 static int qos_obs_check(const orl_batch* b) {
   if (b->P.env_type != ENV_QOS) return fail(ORL_E_INVALID, "MatrixObservationWithPaths is defined for QoSConstrainedRA only");

@@ -85,8 +85,11 @@ struct orl_batch {
   int* ep_buf = nullptr;           // episode log buffer (orl_batch_episode_log): [B][ep_alloc] ints, armed with stride P.ep_cap <= ep_alloc
   int ep_alloc = 0;
   double* ep_rew_buf = nullptr;    // QoSConstrainedRA: the float64 reward sums beside it, same shape
-  unsigned char* mask_buf[2] = {nullptr, nullptr};  // action masks per layout (ORL_MASK_JOINT / _PATH): [B][pitch] bytes, allocated by
-                                                   // the first orl_batch_action_mask of that layout (a view of one stays that layout's)
+  unsigned char* mask_buf[4] = {nullptr, nullptr, nullptr, nullptr};  // action masks per layout (ORL_MASK_*): [B][pitch] bytes, allocated
+                                   // by the first orl_batch_action_mask of that layout (a view of one stays that layout's)
+  int32_t* mask_given = nullptr;   // ORL_MASK_CORE_SLOT with a host `given`: the (path, modulation) pairs [B][2] on the device and in
+  int32_t* h_mask_given = nullptr; // page-locked memory, allocated on first use
+  hipEvent_t ev_given_up = nullptr;  // behind the last upload out of h_mask_given: the next call waits for it before it refills the buffer
   int mask_last = -1;              // layout of the last launch: what ORL_BUF_ACTION_MASK hands out (-1: none yet)
   unsigned char* qobs_buf = nullptr;  // MatrixObservationWithPaths (QoSConstrainedRA): [B][pitch] bytes, allocated by the first
                                     // orl_batch_matrix_paths_observation; what ORL_BUF_MATRIX_PATHS_OBS hands out
@@ -128,6 +131,8 @@ template <int W> void policy(orl_batch* b, int pol);                       // st
 template <int W> void step64(orl_batch* b, int auto_reset, int want_info, int fused_policy);  // one wavefront per env
 template <int W> void obs(orl_batch* b, int with_terminal);                // DeepRMSA observation
 template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, int pitch);  // k_action_mask -> out [B][pitch]
+// k_rmcsa_mask -> out [B][pitch]; given: device (path, modulation) of env e at given[e * gstride + 0 / 1]; -1: refused (nothing launched)
+template <int W> int rmcsa_mask(orl_batch* b, int layout, unsigned char* out, int pitch, const int* given, int gstride);
 // k_persist in the form `ch` (the run's choice for the whole batch; use_spec: made for the attached specialisation library) over the
 // env range of view VP up to step `target` of this run, then k_rel_tail, on stream st
 template <int W> void persist(orl_batch* b, const orl::DevParams& VP, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,

@@ -10,6 +10,7 @@
 //               (k_persist does that itself at the start of the owning wavefront's next launch)
 //   k_obs8/k_obs DeepRMSA observation of the pending service
 //   k_action_mask action masks of the pending service (orl_mask.h)                      8 lanes per env, lane = path
+//   k_rmcsa_mask RMCSA's path-modulation and core-slot masks (orl_rmcsa_mask.h)         8 lanes per env, lane = (path, core) / core
 // Launchers (orl_launch::*<W>) are explicitly instantiated at the end; orl_api.hip dispatches on the batch's W.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -2045,6 +2046,7 @@ __global__ void __launch_bounds__(256) k_obs8(DevParams P, int with_terminal) {
 
 #ifndef ORL_SPEC_ONLY
 #include "orl_mask.h"  // k_action_mask: action masks of the pending service (RMSA, DeepRMSA, RWA)
+#include "orl_rmcsa_mask.h"  // k_rmcsa_mask: the two-stage masks of RMCSA (path-modulation, core-slot)
 #endif
 
 // ---- QoSConstrainedRA for an agent in the loop: 8 lanes per env (round 5) --------------------------------------------------------
@@ -2249,6 +2251,21 @@ template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, i
   return 0;
 }
 
+// k_rmcsa_mask (orl_rmcsa_mask.h) into `out` ([B][pitch] bytes on the device); `given`: device int32, the (path, modulation) of env e
+// at given[e * gstride + 0 / 1] (ORL_MASK_CORE_SLOT).  -1, and no launch, when the LDS rows of one wavefront's 8 envs exceed 48 KiB
+// or a path's M modulations do not fit its 32-bit word; out == nullptr: that check alone
+template <int W> int rmcsa_mask(orl_batch* b, int layout, unsigned char* out, int pitch, const int* given, int gstride) {
+  const DevParams& VP = b->P;
+  const int waves = rmcsa_mask_waves(layout, W, VP.K, VP.C);
+  if (!waves || VP.M > 32) return -1;
+  if (!out) return 0;
+  const size_t lds = (size_t)waves * 8 * rmcsa_mask_env_words(layout, W, VP.K, VP.C) * sizeof(u32);
+  const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
+  hipLaunchKernelGGL((k_rmcsa_mask<W>), dim3(grid), dim3(64 * waves), lds, b->stream, VP, out, layout, pitch, given, gstride);
+  ORL_TK(b, "k_rmcsa_mask");
+  return 0;
+}
+
 // The persistent kernel in the form `ch` — what persist_choose (orl_persist_form.h) took for the whole batch when the run began:
 // a run in two halves launches the same kernel on both views — over the env range of view VP0.
 template <int W> void persist(orl_batch* b, const DevParams& VP0, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,
@@ -2400,6 +2417,7 @@ template void policy<ORL_W>(orl_batch*, int);
 template void step64<ORL_W>(orl_batch*, int, int, int);
 template void obs<ORL_W>(orl_batch*, int);
 template int action_mask<ORL_W>(orl_batch*, int, unsigned char*, int);
+template int rmcsa_mask<ORL_W>(orl_batch*, int, unsigned char*, int, const int*, int);
 template void persist<ORL_W>(orl_batch*, const DevParams&, const PersistChoice&, bool, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);
 template void step2<ORL_W>(orl_batch*, int);
 template void agent_step<ORL_W>(orl_batch*, int, int);

@@ -693,7 +693,7 @@ class BatchedOpticalEnv:
         return la, lh
 
     # ---- action masks (include/orl.h, orl_batch_action_mask) -------------------------------------------
-    MASK_LAYOUTS = {"joint": 0, "path": 1}
+    MASK_LAYOUTS = {"joint": 0, "path": 1, "path_modulation": 2, "core_slot": 3}
 
     def action_mask_shape(self, layout="joint"):
         """(dim, pitch) of the rows of `layout`: dim columns per env, rows pitch bytes apart in the device buffer."""
@@ -701,22 +701,32 @@ class BatchedOpticalEnv:
         self._ck(self.lib.orl_batch_action_mask_shape(self._h, self.MASK_LAYOUTS[layout], C.byref(d), C.byref(p)))
         return d.value, p.value
 
-    def action_mask(self, layout="joint", fetch=True):
+    def action_mask(self, layout="joint", fetch=True, given=None):
         """Action mask of the pending service of every env, computed on the device: bool [num_envs, dim].  "joint": RMSA / RWA
-        column p * S + s = action (p, s), DeepRMSA column i = action i; "path": PathOnlyFirstFitAction's Discrete(k + 1).  The
+        column p * S + s = action (p, s), DeepRMSA column i = action i; "path": PathOnlyFirstFitAction's Discrete(k + 1).  RMCSA has
+        the two stages of its (path, modulation, core, slot) action instead: "path_modulation", column p * M + m = some (core,
+        slot) provisions under that pair, and "core_slot", column c * S + s = (c, s) provisions under the env's pair — `given`,
+        an int array [num_envs, 2] of (path, modulation), or with given=None columns 0 and 1 of device_array("actions"), where an
+        agent on the GPU writes its stage-1 choice; a pair out of range or beyond reach has no provisioning column.  The
         last column is the reject action (= allow_rejection); a row without a provisioning action and allow_rejection=False is
         all ones but for it (every action rejects then).  fetch=False only queues the launch on the batch's stream — read the
         rows in place with device_array("action_mask") / device_tensor("action_mask")."""
         lay = self.MASK_LAYOUTS[layout]
-        if not fetch:
-            self._ck(self.lib.orl_batch_action_mask(self._h, lay, None))
-            self._mask_layout = layout
-            return None
-        dim, _pitch = self.action_mask_shape(layout)
-        out = np.empty((self.num_envs, dim), np.uint8)
-        self._ck(self.lib.orl_batch_action_mask(self._h, lay, out.ctypes.data))
+        g = None
+        if given is not None:
+            if layout != "core_slot":
+                raise ValueError("given (path, modulation) pairs belong to the \"core_slot\" layout, not %r" % (layout,))
+            g = np.asarray(given)
+            if g.shape != (self.num_envs, 2) or g.dtype.kind not in "iu":
+                raise ValueError("given must be an int array of shape %r, got %s %r" % ((self.num_envs, 2), g.dtype, g.shape))
+            g = np.ascontiguousarray(g, np.int32)
+        out = None
+        if fetch:
+            dim, _pitch = self.action_mask_shape(layout)
+            out = np.empty((self.num_envs, dim), np.uint8)
+        self._ck(self.lib.orl_batch_action_mask_given(self._h, lay, None if g is None else g.ctypes.data, None if out is None else out.ctypes.data))
         self._mask_layout = layout
-        return out.view(np.bool_)
+        return None if out is None else out.view(np.bool_)
 
     # ---- MatrixObservationWithPaths (include/orl.h, orl_batch_matrix_paths_observation): QoSConstrainedRA only ---------------
     def matrix_paths_obs_shape(self):

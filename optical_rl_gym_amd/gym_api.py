@@ -435,6 +435,15 @@ class RMCSAEnv(_SingleEnv):
         avail = self._slots()
         return not np.any(avail[core][self._links(path), initial_slot:initial_slot + number_slots] == 0)
 
+    def action_mask(self, layout="path_modulation", given=None):
+        """The env's row of the batch's two-stage masks (BatchedOpticalEnv.action_mask), computed on the device: "path_modulation",
+        bool [k * M + 1], then "core_slot", bool [C * S + 1], for the pair `given` = (path, modulation)."""
+        if given is not None:
+            if np.shape(given) != (2,):
+                raise ValueError("given must be a (path, modulation) pair, got shape %r" % (np.shape(given),))
+            given = np.asarray(given).reshape(1, 2)
+        return self.batch.action_mask(layout, given=given)[0]
+
     def _episode_hist(self, which):  # re-zeroed at every reset and never incremented (rmcsa_env.py:154-180, 391-407)
         return np.zeros((self.k_paths + 1, len(self.topo.modulations) + 1, self.num_spatial_resources + 1,
                          self.num_spectrum_resources + 1), dtype=int)

@@ -330,8 +330,15 @@ class MultiDeviceBatch:
     def matrix_observation(self):
         return self._cat(self._map(lambda r: self.shards[r].matrix_observation()))
 
-    def action_mask(self, layout="joint", fetch=True):
-        out = self._map(lambda r: self.shards[r].action_mask(layout, fetch=fetch))
+    def action_mask(self, layout="joint", fetch=True, given=None):
+        """BatchedOpticalEnv.action_mask of every shard; `given` ([num_envs, 2], "core_slot") is cut by the shards' bounds."""
+        if given is None:  # (shards may be any objects with the batch interface: the argument is passed only where it is used)
+            out = self._map(lambda r: self.shards[r].action_mask(layout, fetch=fetch))
+        else:
+            given = np.asarray(given)
+            if given.shape != (self.num_envs, 2):
+                raise ValueError("given must be an int array of shape %r, got %r" % ((self.num_envs, 2), given.shape))
+            out = self._map(lambda r: self.shards[r].action_mask(layout, fetch=fetch, given=self._cut(given, r)))
         return self._cat(out) if fetch else None
 
     def matrix_paths_obs_shape(self):

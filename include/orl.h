@@ -309,6 +309,9 @@ int orl_host_free(void* p);
                                * pointer taken after a JOINT call keeps showing JOINT rows; n_elements = 0 before any call */
 #define ORL_BUF_MATRIX_PATHS_OBS 8 /* u8 [n_envs][pitch]: rows of the last orl_batch_matrix_paths_observation (pitch of
                                     * orl_batch_matrix_paths_obs_shape); allocated by the first call, n_elements = 0 before it */
+#define ORL_BUF_PATH_FEATURES 9  /* f32 [n_envs][pitch]: rows of the last orl_batch_path_features (pitch, in floats, of
+                                  * orl_batch_path_features_shape for that call's j); each j has a buffer of its own, allocated by
+                                  * its first call; n_elements = 0 before any call */
 int orl_batch_device_buffer(orl_batch* b, int which, void** device_ptr, int64_t* n_elements);
 /* The HIP stream (hipStream_t) the batch queues its launches on.  An agent on the same GPU that queues ITS kernels on this
  * stream too (torch: `torch.cuda.ExternalStream(ptr)`) needs no synchronisation between its network and orl_batch_step: the
@@ -417,6 +420,31 @@ int orl_batch_action_mask_given(orl_batch* b, int layout, const int32_t* given /
  * out densely and the call synchronises. */
 int orl_batch_matrix_paths_obs_shape(const orl_batch* b, int32_t* dim, int32_t* pitch);
 int orl_batch_matrix_paths_observation(orl_batch* b, uint8_t* out);
+
+/* Path features of the pending service of every env — the feature table of DeepRMSAEnv.observation (deeprmsa_env.py:60-121) as a
+ * float32 device observation for every slot-map family: RMSA, DeepRMSA, RWA and RMCSA (QoSConstrainedRA, which has no slot maps,
+ * returns ORL_E_INVALID).  `j` in [1, 8] is the number of free blocks listed per row, a parameter of the call (independent of a
+ * DeepRMSA batch's own j).  Per env a row of dim = 1 + 2 n_nodes + R (2 j + 3) floats, R = k (RMCSA: R = k * cores, row p * cores
+ * + c, path-major as rmcsa_env.py:889-906):
+ *   column 0 = bit_rate / 100 (RWA: 0.0); column 1 + min(src, dst) = 1; column 1 + n_nodes + max(src, dst) = 1; other header
+ *   columns 0; then per row r (path p, core c) a block of 2 j + 3 values, all -1.0 when p >= n_paths[src, dst], else with m = the
+ *   slots free on every hop of p in core c and n = the slots the service needs (RMSA / DeepRMSA: get_number_slots under the path's
+ *   best modulation; RWA: 1; RMCSA: under the path's best modulation — the one SAP_BM_FC_FF uses — for modulation == -1, under
+ *   modulation m for every path for modulation == m in [0, M)):
+ *     [2 b], [2 b + 1]  for b < min(j, maximal free runs of >= n slots), in slot order: 2 (start - 0.5 S) / S, (length - 8) / 8;
+ *                       the block's other columns below 2 j stay -1.0
+ *     [2 j] = (n - 5.5) / 3.5;  [2 j + 1] = 2 (popcount(m) - 0.5 S) / S;
+ *     [2 j + 2] = (popcount(m) / runs(m) - 4) / 4 when m has a free run, else -1.0
+ * Every value is the reference's float64 expression rounded to float32 once: on a DeepRMSA batch with its own j the row is the
+ * float32 cast of its observation, bit for bit.  A modulation other than -1 outside RMCSA, a modulation outside [-1, M) and a j
+ * outside [1, 8] return ORL_E_INVALID before anything is queued.
+ * orl_batch_path_features_shape: *dim, *rows = R and the device pitch IN FLOATS, round_up(dim, 4), of ORL_BUF_PATH_FEATURES' rows.
+ * orl_batch_path_features: one launch on the batch's stream into ORL_BUF_PATH_FEATURES (no synchronisation, graph-capturable:
+ * the buffer of a j is allocated by the first call with that j, which should therefore come before a capture); with out != NULL
+ * ([n_envs][dim] floats) the rows are then copied out densely and the call synchronises.  The pending service and the slot maps
+ * are read as the last step or reset left them; nothing of the env is written. */
+int orl_batch_path_features_shape(const orl_batch* b, int j, int32_t* dim, int32_t* rows, int32_t* pitch);
+int orl_batch_path_features(orl_batch* b, int j, int modulation, float* out /* host [n_envs][dim], or NULL */);
 
 /* Snapshot / restore of the complete simulation state of the batch (slot maps, pending releases, RNG, statistics,
  * counters).  The reference has no equivalent (no checkpointing); used for long PPO runs.  The per-env

@@ -1171,6 +1171,10 @@ extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_pt
       *device_ptr = b->mask_buf[b->mask_last];
       *n_elements = B * ((mask_dim(b->P, b->mask_last) + 15) / 16 * 16);
       break;
+    case ORL_BUF_PATH_FEATURES:
+      *device_ptr = b->pf_last ? b->pf_buf[b->pf_last] : nullptr;
+      *n_elements = b->pf_last ? B * path_obs_pitch(path_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, b->pf_last)) : 0;
+      break;
     case ORL_BUF_MATRIX_PATHS_OBS:
       *device_ptr = b->qobs_buf;
       *n_elements = b->qobs_buf ? B * qos_obs_pitch(b->P) : 0;
@@ -1282,6 +1286,47 @@ extern "C" int orl_batch_action_mask_given(orl_batch* b, int layout, const int32
 ORL_ABI_CATCH_INT
 
 extern "C" int orl_batch_action_mask(orl_batch* b, int layout, uint8_t* out) { return orl_batch_action_mask_given(b, layout, nullptr, out); }
+
+// path features (orl_path_obs.h)
+static int path_features_check(const orl_batch* b, int j, int modulation) {
+  if (b->P.env_type == ENV_QOS) return fail(ORL_E_INVALID, "path features are not available for QoSConstrainedRA, which has no slot maps (RMSA, DeepRMSA, RWA and RMCSA only)");
+  if (j < 1 || j > 8) return fail(ORL_E_INVALID, "path features list j = 1 .. 8 free blocks per row, got j = %d", j);
+  if (modulation != -1 && b->P.env_type != ENV_RMCSA) return fail(ORL_E_INVALID, "a modulation for the path features is defined for RMCSA only (pass -1)");
+  if (modulation < -1 || modulation >= b->P.M) return fail(ORL_E_INVALID, "modulation %d outside -1 (each path's best) .. %d", modulation, b->P.M - 1);
+  return ORL_OK;
+}
+
+extern "C" int orl_batch_path_features_shape(const orl_batch* b, int j, int32_t* dim, int32_t* rows, int32_t* pitch) try {
+  if (!b || !dim || !rows || !pitch) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = path_features_check(b, j, -1)) return rc;
+  *dim = path_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, j);
+  *rows = path_obs_rows(b->P.env_type, b->P.K, b->P.C);
+  *pitch = path_obs_pitch(*dim);
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+extern "C" int orl_batch_path_features(orl_batch* b, int j, int modulation, float* out) try {
+  if (!b) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = path_features_check(b, j, modulation)) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  const int dim = path_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, j), pitch = path_obs_pitch(dim);
+  const i64 B = b->P.B;
+  float*& buf = b->pf_buf[j];  // one buffer per j: a device view of one j's rows never sees another's
+  if (!buf) {
+    HIPCHK(hipMalloc((void**)&buf, (size_t)(B * (int64_t)pitch) * sizeof(float)));
+    b->allocs.push_back(buf);
+  }
+  ORL_LAUNCH(path_features, b, buf, j, modulation);
+  HIPCHK(hipGetLastError());
+  b->pf_last = j;
+  if (out) {
+    HIPCHK(hipMemcpy2DAsync(out, (size_t)dim * sizeof(float), buf, (size_t)pitch * sizeof(float), (size_t)dim * sizeof(float), (size_t)B, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+  }
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
 
 static int qos_obs_check(const orl_batch* b) {
   if (b->P.env_type != ENV_QOS) return fail(ORL_E_INVALID, "MatrixObservationWithPaths is defined for QoSConstrainedRA only");

@@ -91,6 +91,9 @@ struct orl_batch {
   int32_t* h_mask_given = nullptr; // page-locked memory, allocated on first use
   hipEvent_t ev_given_up = nullptr;  // behind the last upload out of h_mask_given: the next call waits for it before it refills the buffer
   int mask_last = -1;              // layout of the last launch: what ORL_BUF_ACTION_MASK hands out (-1: none yet)
+  float* pf_buf[9] = {};           // path features per block count j (1 .. 8): [B][pitch] floats, allocated by the first
+                                   // orl_batch_path_features of that j (a view of one stays that j's)
+  int pf_last = 0;                 // j of the last launch: what ORL_BUF_PATH_FEATURES hands out (0: none yet)
   unsigned char* qobs_buf = nullptr;  // MatrixObservationWithPaths (QoSConstrainedRA): [B][pitch] bytes, allocated by the first
                                     // orl_batch_matrix_paths_observation; what ORL_BUF_MATRIX_PATHS_OBS hands out
   // orl_batch_copy_envs (as the destination): the pair indices [2][n] on the device and in page-locked memory, grown on demand
@@ -113,6 +116,11 @@ static inline void slot_maps_change(orl_batch* b, hipStream_t st) {
   }
 }
 
+// path features (orl_path_obs.h, orl_batch_path_features): block rows per env, row length for j blocks per row, device pitch in floats
+static inline int path_obs_rows(int env_type, int K, int C) { return env_type == orl::ENV_RMCSA ? K * C : K; }
+static inline int path_obs_dim(int env_type, int N, int K, int C, int j) { return 1 + 2 * N + path_obs_rows(env_type, K, C) * (2 * j + 3); }
+static inline int path_obs_pitch(int dim) { return (dim + 3) / 4 * 4; }
+
 #define ORL_TK(B_, NAME)                                                                 \
   do {                                                                                   \
     if ((B_)->tk) {                                                                      \
@@ -133,6 +141,7 @@ template <int W> void obs(orl_batch* b, int with_terminal);                // De
 template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, int pitch);  // k_action_mask -> out [B][pitch]
 // k_rmcsa_mask -> out [B][pitch]; given: device (path, modulation) of env e at given[e * gstride + 0 / 1]; -1: refused (nothing launched)
 template <int W> int rmcsa_mask(orl_batch* b, int layout, unsigned char* out, int pitch, const int* given, int gstride);
+template <int W> void path_features(orl_batch* b, float* out, int j, int mod);  // k_path_features -> out [B][round_up(dim, 4)] floats
 // k_persist in the form `ch` (the run's choice for the whole batch; use_spec: made for the attached specialisation library) over the
 // env range of view VP up to step `target` of this run, then k_rel_tail, on stream st
 template <int W> void persist(orl_batch* b, const orl::DevParams& VP, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,

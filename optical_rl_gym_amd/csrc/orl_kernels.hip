@@ -11,6 +11,7 @@
 //   k_obs8/k_obs DeepRMSA observation of the pending service
 //   k_action_mask action masks of the pending service (orl_mask.h)                      8 lanes per env, lane = path
 //   k_rmcsa_mask RMCSA's path-modulation and core-slot masks (orl_rmcsa_mask.h)         8 lanes per env, lane = (path, core) / core
+//   k_path_features path-feature observation of the pending service (orl_path_obs.h)    8 lanes per env, rows striped over them
 // Launchers (orl_launch::*<W>) are explicitly instantiated at the end; orl_api.hip dispatches on the batch's W.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -2047,6 +2048,7 @@ __global__ void __launch_bounds__(256) k_obs8(DevParams P, int with_terminal) {
 #ifndef ORL_SPEC_ONLY
 #include "orl_mask.h"  // k_action_mask: action masks of the pending service (RMSA, DeepRMSA, RWA)
 #include "orl_rmcsa_mask.h"  // k_rmcsa_mask: the two-stage masks of RMCSA (path-modulation, core-slot)
+#include "orl_path_obs.h"  // k_path_features: the path-feature observation of the pending service (every slot-map family)
 #endif
 
 // ---- QoSConstrainedRA for an agent in the loop: 8 lanes per env (round 5) --------------------------------------------------------
@@ -2266,6 +2268,19 @@ template <int W> int rmcsa_mask(orl_batch* b, int layout, unsigned char* out, in
   return 0;
 }
 
+// k_path_features (orl_path_obs.h) into `out` ([B][pitch] floats on the device): j blocks per row, RMCSA under modulation `mod`
+// (-1: each path's best).  The wavefront's rows are staged in LDS where 8 of them fit 48 KiB, else every lane stores its own blocks
+// (-DORL_PATH_OBS_STAGE=0: always — the build the two forms were measured against each other with).
+template <int W> void path_features(orl_batch* b, float* out, int j, int mod) {
+  const DevParams& VP = b->P;
+  const int dim = path_obs_dim(VP.env_type, VP.N, VP.K, VP.C, j), pitch = path_obs_pitch(dim);
+  const int fit = ORL_PATH_OBS_STAGE ? path_obs_waves(pitch) : 0, waves = fit ? fit : 4;
+  const size_t lds = fit ? (size_t)waves * 8 * pitch * sizeof(float) : 0;
+  const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
+  hipLaunchKernelGGL((k_path_features<W>), dim3(grid), dim3(64 * waves), lds, b->stream, VP, out, j, mod, dim, pitch, fit ? 1 : 0);
+  ORL_TK(b, "k_path_features");
+}
+
 // The persistent kernel in the form `ch` — what persist_choose (orl_persist_form.h) took for the whole batch when the run began:
 // a run in two halves launches the same kernel on both views — over the env range of view VP0.
 template <int W> void persist(orl_batch* b, const DevParams& VP0, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,
@@ -2418,6 +2433,7 @@ template void step64<ORL_W>(orl_batch*, int, int, int);
 template void obs<ORL_W>(orl_batch*, int);
 template int action_mask<ORL_W>(orl_batch*, int, unsigned char*, int);
 template int rmcsa_mask<ORL_W>(orl_batch*, int, unsigned char*, int, const int*, int);
+template void path_features<ORL_W>(orl_batch*, float*, int, int);
 template void persist<ORL_W>(orl_batch*, const DevParams&, const PersistChoice&, bool, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);
 template void step2<ORL_W>(orl_batch*, int);
 template void agent_step<ORL_W>(orl_batch*, int, int);

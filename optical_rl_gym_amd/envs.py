@@ -752,10 +752,42 @@ class BatchedOpticalEnv:
         self._ck(self.lib.orl_batch_matrix_paths_observation(self._h, out.ctypes.data))
         return out
 
+    # ---- path features (include/orl.h, orl_batch_path_features): RMSA, DeepRMSA, RWA and RMCSA --------------------------------
+    def path_features_shape(self, j=1):
+        """(dim, rows, pitch) of the path-feature rows for `j` blocks per row: dim = 1 + 2 N + rows * (2 j + 3) float32 columns per
+        env, rows = k (RMCSA: k * cores), rows of the device buffer pitch FLOATS apart."""
+        d, r, p = C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self.lib.orl_batch_path_features_shape(self._h, int(j), C.byref(d), C.byref(r), C.byref(p)))
+        return d.value, r.value, p.value
+
+    def path_features(self, j=1, modulation=None, fetch=True, out=None):
+        """Path features of every env's pending service, computed on the device: float32 [num_envs, dim] — the feature table of
+        DeepRMSAEnv.observation (deeprmsa_env.py:60-121) for every slot-map family.  Column 0 = bit_rate / 100 (RWA: 0), then the
+        one-hots of min(src, dst) and max(src, dst), then per candidate path (RMCSA: per path and core, row p * cores + c) a
+        block of 2 j + 3 values: start and length of the first j free blocks that fit the service, the slots it needs, the free
+        slots and the mean free-run length, normalised as the reference does; -1.0 where a value does not exist.  `j` in [1, 8]
+        is independent of a DeepRMSA batch's own j.  `modulation` (RMCSA only): None = each path's best modulation, as SAP_BM_FC_FF;
+        m in [0, M) = that modulation for every path.  `out` (a C-contiguous float32 [num_envs, dim] array) receives the rows
+        instead of a fresh array.  fetch=False only queues the launch on the batch's stream — read the rows in place with
+        device_array("path_features") / device_tensor("path_features")."""
+        j, mod = int(j), -1 if modulation is None else int(modulation)
+        if not fetch:
+            self._ck(self.lib.orl_batch_path_features(self._h, j, mod, None))
+            self._pf_j = j
+            return None
+        dim, _rows, _pitch = self.path_features_shape(j)
+        if out is None:
+            out = np.empty((self.num_envs, dim), np.float32)
+        elif out.shape != (self.num_envs, dim) or out.dtype != np.float32 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous float32 array of shape %r" % ((self.num_envs, dim),))
+        self._ck(self.lib.orl_batch_path_features(self._h, j, mod, out.ctypes.data))
+        self._pf_j = j
+        return out
+
     # ---- zero-copy device views (an agent on the same GPU: no PCIe in the loop) -------------------------
     _BUFFERS = {"actions": (0, "<i4", 4), "reward": (1, "<f8", 0), "done": (2, "|u1", 0), "info": (3, "<f8", -1),
                 "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0), "action_mask": (7, "|b1", -3),
-                "matrix_paths_obs": (8, "|u1", -4)}
+                "matrix_paths_obs": (8, "|u1", -4), "path_features": (9, "<f4", -5)}
 
     def device_array(self, name):
         """The batch's device-resident I/O array `name` as an object with `__cuda_array_interface__` (what
@@ -778,6 +810,11 @@ class BatchedOpticalEnv:
                                     "queues it) first")
             cols, pitch = self.matrix_paths_obs_shape()
             strides = (pitch, 1)
+        elif cols == -5:  # the rows of the last path_features(), [num_envs, dim] at the device pitch; each j has a buffer of its own
+            if n.value == 0 or not ptr.value:
+                raise _lib.OrlError("no path features yet: call path_features() (fetch=False only queues it) first")
+            cols, _rows, pitch = self.path_features_shape(self._pf_j)
+            strides = (4 * pitch, 4)
         cols = {-1: self.n_info, -2: self.obs_dim}.get(cols, cols)
         if n.value == 0 or not ptr.value:
             raise _lib.OrlError("this env family has no '%s' array" % name)

@@ -329,6 +329,11 @@ class _SingleEnv:
 
         return sb3_action_masks(self.batch, self.batch.action_mask("joint"), self.action_space)[0]
 
+    def path_features(self, j=1, modulation=None):
+        """The env's row of the batch's path features (BatchedOpticalEnv.path_features), computed on the device: float32
+        [1 + 2 N + rows * (2 j + 3)]."""
+        return self.batch.path_features(j, modulation)[0]
+
     def policy_action(self, policy):
         """Action of the on-device heuristic `policy` for the pending service, in the reference's tuple form."""
         a = self.batch.policy(policy)[0]

@@ -341,6 +341,18 @@ class MultiDeviceBatch:
             out = self._map(lambda r: self.shards[r].action_mask(layout, fetch=fetch, given=self._cut(given, r)))
         return self._cat(out) if fetch else None
 
+    def path_features_shape(self, j=1):
+        return self.shards[0].path_features_shape(j)
+
+    def path_features(self, j=1, modulation=None, fetch=True, out=None):
+        """BatchedOpticalEnv.path_features of every shard, rows in env order; with `out` ([num_envs, dim] float32, C-contiguous)
+        every shard writes its own rows."""
+        if out is None or not fetch:
+            parts = self._map(lambda r: self.shards[r].path_features(j, modulation, fetch=fetch))
+            return self._cat(parts) if fetch else None
+        self._map(lambda r: self.shards[r].path_features(j, modulation, out=out[self.bounds[r]:self.bounds[r + 1]]))
+        return out
+
     def matrix_paths_obs_shape(self):
         return self.shards[0].matrix_paths_obs_shape()
 

@@ -130,6 +130,7 @@ __global__ void k_matrix_obs(DevParams P, unsigned char* out) {
   }
 }
 
+#include "orl_view.h"     // what the views of the pending service share (the kernels of orl_kernels.hip; here: 16 bits -> 16 bytes)
 #include "orl_qos_obs.h"  // k_qos_matrix_obs: MatrixObservationWithPaths of QoSConstrainedRA (qos_constrained_ra.py:440-493)
 
 #include "orl_copy.h"  // k_copy_envs: the rows of env src[p] of one batch into env dst[p] of another (orl_batch_copy_envs)
@@ -1142,9 +1143,35 @@ extern "C" int orl_host_free(void* p) try {
 }
 ORL_ABI_CATCH_INT
 
+// ---- the views of the pending service (action masks, path features, MatrixObservationWithPaths): what their entry points share ----
+// device pitch of a view's row of `dim` bytes: rows are written as 16-byte stores
+static int64_t byte_row_pitch(int64_t dim) { return (dim + 15) / 16 * 16; }
+
+// A view's device buffer, allocated by the first call that needs it (which therefore comes before a graph capture).  A failed
+// allocation leaves the batch as it was: the slot null, nothing recorded, no error left for a later call to find.
+template <typename T> static int view_buffer(orl_batch* b, T*& slot, size_t bytes, const char* what) {
+  if (slot) return ORL_OK;
+  void* p = nullptr;
+  const hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ORL_E_HIP, "%s: allocating %zu bytes failed: %s", what, bytes, hipGetErrorString(e));
+  }
+  slot = (T*)p;
+  b->allocs.push_back(p);
+  return ORL_OK;
+}
+
+// a view's rows — [B][dim] elements of `elem` bytes at a device pitch of `pitch` elements — densely into the host's `out`; waits
+static int view_rows_to_host(orl_batch* b, const void* buf, size_t elem, int64_t dim, int64_t pitch, void* out) {
+  HIPCHK(hipMemcpy2DAsync(out, (size_t)dim * elem, buf, (size_t)pitch * elem, (size_t)dim * elem, (size_t)b->P.B, hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return ORL_OK;
+}
+
 // MatrixObservationWithPaths (orl_qos_obs.h): row length and device pitch, in 64 bits
 static int64_t qos_obs_dim(const DevParams& P) { return (int64_t)P.E * P.S * (P.K + 1) + 1; }
-static int64_t qos_obs_pitch(const DevParams& P) { return (qos_obs_dim(P) + 15) / 16 * 16; }
+static int64_t qos_obs_pitch(const DevParams& P) { return byte_row_pitch(qos_obs_dim(P)); }
 
 // action masks (orl_mask.h, orl_rmcsa_mask.h): row length of `layout` for this batch's family, 0 = not supported
 static int mask_dim(const DevParams& P, int layout) {
@@ -1169,7 +1196,7 @@ extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_pt
     case ORL_BUF_ACTION_MASK:
       if (b->mask_last < 0) { *device_ptr = nullptr; *n_elements = 0; break; }
       *device_ptr = b->mask_buf[b->mask_last];
-      *n_elements = B * ((mask_dim(b->P, b->mask_last) + 15) / 16 * 16);
+      *n_elements = B * byte_row_pitch(mask_dim(b->P, b->mask_last));
       break;
     case ORL_BUF_PATH_FEATURES:
       *device_ptr = b->pf_last ? b->pf_buf[b->pf_last] : nullptr;
@@ -1224,7 +1251,7 @@ extern "C" int orl_batch_action_mask_shape(const orl_batch* b, int layout, int32
   if (!b || !dim || !pitch) return fail(ORL_E_INVALID, "null argument");
   if (int rc = mask_check(b, layout)) return rc;
   *dim = mask_dim(b->P, layout);
-  *pitch = (*dim + 15) / 16 * 16;
+  *pitch = (int32_t)byte_row_pitch(*dim);
   return ORL_OK;
 }
 ORL_ABI_CATCH_INT
@@ -1252,17 +1279,13 @@ extern "C" int orl_batch_action_mask_given(orl_batch* b, int layout, const int32
   if (int rc = mask_check(b, layout)) return rc;
   if (given && layout != ORL_MASK_CORE_SLOT) return fail(ORL_E_INVALID, "`given` belongs to ORL_MASK_CORE_SLOT only");
   HIPCHK(hipSetDevice(b->device));
-  const int dim = mask_dim(b->P, layout), pitch = (dim + 15) / 16 * 16;
-  const i64 B = b->P.B;
+  const int dim = mask_dim(b->P, layout), pitch = (int)byte_row_pitch(dim);
   const bool rmcsa = b->P.env_type == ENV_RMCSA;
   if (rmcsa && ORL_LAUNCH(rmcsa_mask, b, layout, nullptr, pitch, nullptr, 0))  // (out == nullptr: the check alone, before anything is allocated or queued)
     return fail(ORL_E_INVALID, "RMCSA action masks of k = %d paths, %d modulations, %d cores x %d slots exceed the kernel's LDS budget", b->P.K,
                 b->P.M, b->P.C, b->P.S);
   unsigned char*& buf = b->mask_buf[layout];  // one buffer per layout: a device view of one layout's rows never sees the other's
-  if (!buf) {
-    HIPCHK(hipMalloc((void**)&buf, (size_t)(B * (int64_t)pitch)));
-    b->allocs.push_back(buf);
-  }
+  if (int rc = view_buffer(b, buf, (size_t)(b->P.B * (int64_t)pitch), "action mask")) return rc;
   if (rmcsa) {
     const int* src = b->P.actions;  // columns 0 and 1 of ORL_BUF_ACTIONS: where an agent on the GPU writes its stage-1 choice
     int stride = 4;
@@ -1277,11 +1300,7 @@ extern "C" int orl_batch_action_mask_given(orl_batch* b, int layout, const int32
   }
   HIPCHK(hipGetLastError());
   b->mask_last = layout;
-  if (out) {
-    HIPCHK(hipMemcpy2DAsync(out, (size_t)dim, buf, (size_t)pitch, (size_t)dim, (size_t)B, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-  }
-  return ORL_OK;
+  return out ? view_rows_to_host(b, buf, 1, dim, pitch, out) : ORL_OK;
 }
 ORL_ABI_CATCH_INT
 
@@ -1311,20 +1330,12 @@ extern "C" int orl_batch_path_features(orl_batch* b, int j, int modulation, floa
   if (int rc = path_features_check(b, j, modulation)) return rc;
   HIPCHK(hipSetDevice(b->device));
   const int dim = path_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, j), pitch = path_obs_pitch(dim);
-  const i64 B = b->P.B;
   float*& buf = b->pf_buf[j];  // one buffer per j: a device view of one j's rows never sees another's
-  if (!buf) {
-    HIPCHK(hipMalloc((void**)&buf, (size_t)(B * (int64_t)pitch) * sizeof(float)));
-    b->allocs.push_back(buf);
-  }
+  if (int rc = view_buffer(b, buf, (size_t)(b->P.B * (int64_t)pitch) * sizeof(float), "path features")) return rc;
   ORL_LAUNCH(path_features, b, buf, j, modulation);
   HIPCHK(hipGetLastError());
   b->pf_last = j;
-  if (out) {
-    HIPCHK(hipMemcpy2DAsync(out, (size_t)dim * sizeof(float), buf, (size_t)pitch * sizeof(float), (size_t)dim * sizeof(float), (size_t)B, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-  }
-  return ORL_OK;
+  return out ? view_rows_to_host(b, buf, sizeof(float), dim, pitch, out) : ORL_OK;
 }
 ORL_ABI_CATCH_INT
 
@@ -1349,27 +1360,13 @@ extern "C" int orl_batch_matrix_paths_observation(orl_batch* b, uint8_t* out) tr
   if (int rc = qos_obs_check(b)) return rc;
   HIPCHK(hipSetDevice(b->device));
   const int64_t B = b->P.B, dim = qos_obs_dim(b->P), pitch = qos_obs_pitch(b->P);
-  if (!b->qobs_buf) {  // (the first call allocates: it comes before a graph capture)
-    const size_t bytes = (size_t)(B * pitch);
-    unsigned char* p = nullptr;
-    const hipError_t e = hipMalloc((void**)&p, bytes);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();  // (a failed allocation leaves the batch as it was)
-      return fail(ORL_E_HIP, "MatrixObservationWithPaths: allocating %zu bytes failed: %s", bytes, hipGetErrorString(e));
-    }
-    b->qobs_buf = p;
-    b->allocs.push_back(p);
-  }
+  if (int rc = view_buffer(b, b->qobs_buf, (size_t)(B * pitch), "MatrixObservationWithPaths")) return rc;
   const unsigned grid = (unsigned)((B + ORL_QOBS_WAVES - 1) / ORL_QOBS_WAVES);
   const size_t lds = (size_t)ORL_QOBS_WAVES * qos_obs_wave_lds(b->P.E, b->P.K);
   hipLaunchKernelGGL(k_qos_matrix_obs, dim3(grid), dim3(256), lds, b->stream, b->P, b->qobs_buf, (int)pitch);
   ORL_TK(b, "k_qos_matrix_obs");
   HIPCHK(hipGetLastError());
-  if (out) {
-    HIPCHK(hipMemcpy2DAsync(out, (size_t)dim, b->qobs_buf, (size_t)pitch, (size_t)dim, (size_t)B, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-  }
-  return ORL_OK;
+  return out ? view_rows_to_host(b, b->qobs_buf, 1, dim, pitch, out) : ORL_OK;
 }
 ORL_ABI_CATCH_INT
 

@@ -12,6 +12,7 @@
 //   k_action_mask action masks of the pending service (orl_mask.h)                      8 lanes per env, lane = path
 //   k_rmcsa_mask RMCSA's path-modulation and core-slot masks (orl_rmcsa_mask.h)         8 lanes per env, lane = (path, core) / core
 //   k_path_features path-feature observation of the pending service (orl_path_obs.h)    8 lanes per env, rows striped over them
+//               [what these three views share — and k_qos_matrix_obs of orl_api.hip with them — lives in orl_view.h]
 // Launchers (orl_launch::*<W>) are explicitly instantiated at the end; orl_api.hip dispatches on the batch's W.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -2046,6 +2047,7 @@ __global__ void __launch_bounds__(256) k_obs8(DevParams P, int with_terminal) {
 }
 
 #ifndef ORL_SPEC_ONLY
+#include "orl_view.h"  // what the three views below share: the opening, the pending service, bit rows -> byte rows, the LDS budget
 #include "orl_mask.h"  // k_action_mask: action masks of the pending service (RMSA, DeepRMSA, RWA)
 #include "orl_rmcsa_mask.h"  // k_rmcsa_mask: the two-stage masks of RMCSA (path-modulation, core-slot)
 #include "orl_path_obs.h"  // k_path_features: the path-feature observation of the pending service (every slot-map family)
@@ -2242,13 +2244,14 @@ template <int W> void obs(orl_batch* b, int with_terminal) {
   ORL_TK(b, "k_obs");
 }
 
-// k_action_mask (orl_mask.h) into `out` ([B][pitch] bytes on the device); -1 when the LDS rows of 32 envs exceed 48 KiB
+// k_action_mask (orl_mask.h) into `out` ([B][pitch] bytes on the device); -1 when the LDS rows of 4 wavefronts (32 envs) exceed 48 KiB
 template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, int pitch) {
   const DevParams& VP = b->P;
-  const size_t lds = (size_t)ORL_MASK_ENVS_PER_BLOCK * mask_env_words(layout, VP.env_type, W, VP.K) * sizeof(u32);
-  if (lds > 48 * 1024) return -1;
-  const unsigned grid = (unsigned)((VP.B + ORL_MASK_ENVS_PER_BLOCK - 1) / ORL_MASK_ENVS_PER_BLOCK);
-  hipLaunchKernelGGL((k_action_mask<W>), dim3(grid), dim3(256), lds, b->stream, VP, out, layout, pitch);
+  const size_t wave = (size_t)8 * mask_env_words(layout, VP.env_type, W, VP.K) * sizeof(u32);
+  const int waves = 4;
+  if (view_waves(wave) < waves) return -1;
+  const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
+  hipLaunchKernelGGL((k_action_mask<W>), dim3(grid), dim3(64 * waves), waves * wave, b->stream, VP, out, layout, pitch);
   ORL_TK(b, "k_action_mask");
   return 0;
 }
@@ -2258,12 +2261,12 @@ template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, i
 // or a path's M modulations do not fit its 32-bit word; out == nullptr: that check alone
 template <int W> int rmcsa_mask(orl_batch* b, int layout, unsigned char* out, int pitch, const int* given, int gstride) {
   const DevParams& VP = b->P;
-  const int waves = rmcsa_mask_waves(layout, W, VP.K, VP.C);
+  const size_t wave = (size_t)8 * rmcsa_mask_env_words(layout, W, VP.K, VP.C) * sizeof(u32);
+  const int waves = view_waves(wave);
   if (!waves || VP.M > 32) return -1;
   if (!out) return 0;
-  const size_t lds = (size_t)waves * 8 * rmcsa_mask_env_words(layout, W, VP.K, VP.C) * sizeof(u32);
   const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
-  hipLaunchKernelGGL((k_rmcsa_mask<W>), dim3(grid), dim3(64 * waves), lds, b->stream, VP, out, layout, pitch, given, gstride);
+  hipLaunchKernelGGL((k_rmcsa_mask<W>), dim3(grid), dim3(64 * waves), waves * wave, b->stream, VP, out, layout, pitch, given, gstride);
   ORL_TK(b, "k_rmcsa_mask");
   return 0;
 }
@@ -2274,8 +2277,9 @@ template <int W> int rmcsa_mask(orl_batch* b, int layout, unsigned char* out, in
 template <int W> void path_features(orl_batch* b, float* out, int j, int mod) {
   const DevParams& VP = b->P;
   const int dim = path_obs_dim(VP.env_type, VP.N, VP.K, VP.C, j), pitch = path_obs_pitch(dim);
-  const int fit = ORL_PATH_OBS_STAGE ? path_obs_waves(pitch) : 0, waves = fit ? fit : 4;
-  const size_t lds = fit ? (size_t)waves * 8 * pitch * sizeof(float) : 0;
+  const size_t wave = (size_t)8 * pitch * sizeof(float);
+  const int fit = ORL_PATH_OBS_STAGE ? view_waves(wave) : 0, waves = fit ? fit : 4;
+  const size_t lds = fit ? waves * wave : 0;
   const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
   hipLaunchKernelGGL((k_path_features<W>), dim3(grid), dim3(64 * waves), lds, b->stream, VP, out, j, mod, dim, pitch, fit ? 1 : 0);
   ORL_TK(b, "k_path_features");

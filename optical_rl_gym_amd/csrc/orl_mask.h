@@ -1,4 +1,6 @@
-// orl_mask.h — action masks of the pending service (include/orl.h, orl_batch_action_mask); included by orl_kernels.hip.
+// orl_mask.h — action masks of the pending service (include/orl.h, orl_batch_action_mask); included by orl_kernels.hip behind
+// orl_view.h, which holds what this view shares with the others: the kernel's opening (view_lanes), the decode of the pending service
+// (view_pending), the rows' way from LDS to memory (view_store_rows) and the LDS budget rule (view_waves).
 //
 // Per env, one row of `dim` bytes (0/1) at a device pitch of round_up(dim, 16); consecutive envs are contiguous.
 //   ORL_MASK_JOINT  RMSA / RWA: column p * S + s = action (path p, first slot / wavelength s); DeepRMSA: column p * j + b = action
@@ -13,11 +15,10 @@
 //
 // Layout of the work: 8 lanes per env, lane = path (p = gl, gl + 8, ... for k > 8), 8 envs per wavefront, as k_obs8.  Each lane
 // ANDs its path's link rows straight from global memory and leaves the path's columns as a bit row in LDS; then the wavefront
-// streams its 8 envs' output rows (8 * pitch contiguous bytes) as 16-byte stores: a 16-column chunk is a 16-bit field of the
-// env's bitstring, expanded to bytes in registers.  No atomics, no host synchronisation: graph-capturable.
+// streams its 8 envs' output rows (8 * pitch contiguous bytes) as 16-byte stores (view_store_rows: a 16-column chunk is a 16-bit
+// field of the env's bitstring, expanded to bytes in registers).  4 wavefronts per workgroup: the launcher refuses the shapes whose
+// rows do not allow them.  No atomics, no host synchronisation: graph-capturable.
 #pragma once
-
-#define ORL_MASK_ENVS_PER_BLOCK 32  // 4 wavefronts of 8 envs
 
 // u32 words of LDS one env's bit rows take: k rows of `rw` words, a pad word (read past the last row's end, masked off) and
 // the env's "has a provisioning column" flag.  rw: a whole slot row (joint RMSA / RWA), else one u64 (j <= 64 blocks, 1 bit).
@@ -26,33 +27,25 @@ __host__ __device__ inline int mask_row_words(int layout, int env_type, int W) {
 }
 __host__ __device__ inline int mask_env_words(int layout, int env_type, int W, int K) { return K * mask_row_words(layout, env_type, W) + 2; }
 
-// 4 bits -> 4 bytes of 0/1 (bit i lands at bit 8 i; the four partial products do not overlap)
-__device__ __forceinline__ u32 mask_nibble_bytes(u32 x) { return (x * 0x00204081u) & 0x01010101u; }
-
 template <int W>
 __global__ void __launch_bounds__(256) k_action_mask(DevParams P, unsigned char* out, int layout, int pitch) {
-  const int lane = lane_id(), gl = lane & 7, wv = (int)(threadIdx.x >> 6);
-  const i64 env0 = (i64)blockIdx.x * ORL_MASK_ENVS_PER_BLOCK + wv * 8;  // the wavefront's first env
-  const i64 env = env0 + (lane >> 3);
+  const ViewLanes v = view_lanes();
+  const int lane = v.lane, gl = v.gl;
   const int K = P.K, S = P.S, J = P.J;
   const bool deep = P.env_type == ENV_DEEPRMSA, rwa = P.env_type == ENV_RWA, path_layout = layout == ORL_MASK_PATH;
   const int rw = mask_row_words(layout, P.env_type, W), ew = K * rw + 2;
   const int cpp = path_layout ? 1 : (deep ? J : S);  // columns per path
-  u32* lds = (u32*)orl_lds_raw + (size_t)wv * 8 * ew;
+  u32* lds = (u32*)orl_lds_raw + (size_t)v.wv * 8 * ew;
   u32* mine = lds + (lane >> 3) * ew;
   int any = 0;
-  if (env < P.B) {
-    const u64* rec = P.scal + env * ORL_SCAL_WORDS;
-    const u64 sd = rec[SC_SRC_DST], br = rec[SC_BR_IDX];
-    const int src = (int)(u32)sd, dst = (int)(sd >> 32), br_idx = (int)(br >> 32);
-    const int np = P.n_paths[src * P.N + dst];
-    const u64* bm = P.bitmap + env * P.bm_words;
+  if (v.env < P.B) {
+    const PendingSvc sv = view_pending(P, v.env);
     for (int p = gl; p < K; p += 8) {
       Row<W> r = row_mask_lo<W>(0);
-      if (p < np) {
-        const int pidx = (src * P.N + dst) * K + p;
-        const Row<W> m = path_and_rec<W>(path_rec_load(P, pidx), bm, P.E, S, 0);
-        const int n = rwa ? 1 : (int)P.nslots_path[(size_t)pidx * P.n_br + br_idx];
+      if (p < sv.np) {
+        const int pidx = sv.pb + p;
+        const Row<W> m = path_and_rec<W>(path_rec_load(P, pidx), sv.bm, P.E, S, 0);
+        const int n = rwa ? 1 : (int)P.nslots_path[(size_t)pidx * P.n_br + sv.br_idx];
         r = row_runs_ge<W>(m, n);  // bit s: slots s .. s + n - 1 free on every hop (bits >= S are 0: s + n <= S)
         if (deep) {
           const int nb = row_popc<W>(row_and<W>(row_starts<W>(m), r));  // maximal free runs of >= n slots
@@ -71,36 +64,5 @@ __global__ void __launch_bounds__(256) k_action_mask(DevParams P, unsigned char*
   any = g8_max(any);
   if (gl == 0) { mine[K * rw] = 0u; mine[K * rw + 1] = (u32)any; }
   wave_fence();
-  // the wavefront's 8 output rows, 16 columns (bytes) per lane and store
-  const int ncols = K * cpp, nch = pitch >> 4;
-  const int allow = P.allow_rejection != 0;
-  for (int g = lane; g < 8 * nch; g += 64) {
-    const int el = g / nch, c = g - el * nch;
-    const i64 e = env0 + el;
-    if (e >= P.B) break;
-    const u32* rows = lds + el * ew;
-    const int c0 = 16 * c, c1 = c0 + 16 < ncols ? c0 + 16 : ncols;
-    u32 bits = 0u;
-    if (!allow && !rows[K * rw + 1]) {
-      bits = c1 > c0 ? (1u << (c1 - c0)) - 1u : 0u;  // fallback
-    } else {
-      for (int col = c0; col < c1;) {
-        const int p = col / cpp, s = col - p * cpp;
-        const int take = cpp - s < c1 - col ? cpp - s : c1 - col;  // <= 16
-        const u32* rp = rows + p * rw + (s >> 5);
-        const int off = s & 31;
-        u32 v = rp[0] >> off;
-        if (off) v |= rp[1] << (32 - off);
-        bits |= (v & ((1u << take) - 1u)) << (col - c0);
-        col += take;
-      }
-    }
-    if (allow && ncols >= c0 && ncols < c0 + 16) bits |= 1u << (ncols - c0);  // reject column
-    uint4 o;
-    o.x = mask_nibble_bytes(bits & 15u);
-    o.y = mask_nibble_bytes((bits >> 4) & 15u);
-    o.z = mask_nibble_bytes((bits >> 8) & 15u);
-    o.w = mask_nibble_bytes((bits >> 12) & 15u);
-    *(uint4*)(out + e * pitch + c0) = o;
-  }
+  view_store_rows(lds, K, rw, cpp, ew, K * rw, P.allow_rejection, v.env0, P.B, out, pitch);
 }

@@ -1,5 +1,6 @@
 // orl_path_obs.h — the path-feature observation of the pending service (include/orl.h, orl_batch_path_features); included by
-// orl_kernels.hip.
+// orl_kernels.hip behind orl_view.h (the kernel's opening, the decode of the pending service and the LDS budget rule are shared
+// with the other views and live there).
 //
 // Per env one row of dim = 1 + 2 N + R (2 j + 3) float32 values at a device pitch of round_up(dim, 4) floats; consecutive envs are
 // contiguous.  The row is DeepRMSAEnv.observation (deeprmsa_env.py:60-121) with a block count j of the call's own, for every
@@ -18,7 +19,7 @@
 // Layout of the work, as k_action_mask and k_obs8: 8 lanes per env, 8 envs per wavefront; the rows r = gl, gl + 8, ... are striped
 // over the env's lanes, each of which ANDs its path's link rows straight from global memory.  Where the rows go:
 //   staged  the wavefront's 8 rows (8 pitch floats, contiguous in the output too) are assembled in LDS and streamed as 16-byte
-//           stores; 1 / 2 / 4 wavefronts per workgroup, what 48 KiB of LDS allow (path_obs_waves)
+//           stores; 1 / 2 / 4 wavefronts per workgroup, what 48 KiB of LDS allow (view_waves)
 //   direct  every lane stores its own blocks, one float per store — the shapes whose 8 rows do not fit (RMCSA with 31 cores and
 //           j = 8: 11.8 kB per env); -DORL_PATH_OBS_STAGE=0 builds it for every shape (the A/B of DESIGN 4.5)
 // No atomics, no host synchronisation: graph-capturable.
@@ -29,13 +30,6 @@
 #endif
 
 // (path_obs_rows / path_obs_dim / path_obs_pitch: orl_host.h, shared with the API unit)
-// wavefronts (of 8 envs) per workgroup of the staged form: the most of 4, 2, 1 whose rows fit 48 KiB of LDS; 0: not even one does
-inline int path_obs_waves(int pitch) {
-  const size_t wave = (size_t)8 * pitch * sizeof(float);
-  for (int w = 4; w >= 1; w >>= 1)
-    if (w * wave <= 48 * 1024) return w;
-  return 0;
-}
 
 // one row's block: the 2 j + 3 values of the free-slot row m for a service of n slots
 template <int W>
@@ -64,18 +58,16 @@ __device__ __forceinline__ void path_obs_block(const Row<W>& m, int n, int S, in
 // the env's row into o (LDS or global): header and pad by the group's lanes, then the blocks r = gl, gl + 8, ...
 template <int W>
 __device__ __forceinline__ void path_obs_env(const DevParams& P, i64 env, int gl, int J, int mod, int dim, int pitch, float* o) {
-  const u64* rec = P.scal + env * ORL_SCAL_WORDS;
-  const u64 sd = rec[SC_SRC_DST], br = rec[SC_BR_IDX];
-  const int src = (int)(u32)sd, dst = (int)(sd >> 32), br_idx = (int)(br >> 32);
+  const PendingSvc sv = view_pending(P, env);
+  const int src = sv.src, dst = sv.dst, br_idx = sv.br_idx, np = sv.np, pb = sv.pb;
+  const u64* bm = sv.bm;
   const int N = P.N, K = P.K, S = P.S, WD = 2 * J + 3;
   const bool rwa = P.env_type == ENV_RWA, rmcsa = P.env_type == ENV_RMCSA;
   const int C = rmcsa ? P.C : 1, R = K * C;
   const int mn = src < dst ? src : dst, mx = src < dst ? dst : src;
-  const float rate = rwa ? 0.0f : (float)((double)(int)(u32)br / 100);
+  const float rate = rwa ? 0.0f : (float)((double)(int)(u32)sv.br / 100);
   for (int i = gl; i < 1 + 2 * N; i += 8) o[i] = (i == 0) ? rate : ((i == 1 + mn || i == 1 + N + mx) ? 1.0f : 0.0f);
   for (int i = dim + gl; i < pitch; i += 8) o[i] = 0.0f;
-  const int np = P.n_paths[src * N + dst], pb = (src * N + dst) * K;
-  const u64* bm = P.bitmap + env * P.bm_words;
   for (int r = gl; r < R; r += 8) {
     const int p = r / C, core = r - p * C;
     float* blk = o + 1 + 2 * N + r * WD;
@@ -92,14 +84,14 @@ __device__ __forceinline__ void path_obs_env(const DevParams& P, i64 env, int gl
 
 template <int W>
 __global__ void __launch_bounds__(256) k_path_features(DevParams P, float* out, int J, int mod, int dim, int pitch, int staged) {
-  const int lane = lane_id(), gl = lane & 7, wv = (int)(threadIdx.x >> 6), waves = (int)(blockDim.x >> 6);
-  const i64 env0 = ((i64)blockIdx.x * waves + wv) * 8;  // the wavefront's first env
-  const i64 env = env0 + (lane >> 3);
+  const ViewLanes v = view_lanes();
+  const int lane = v.lane, gl = v.gl;
+  const i64 env0 = v.env0, env = v.env;
   if (!staged) {
     if (env < P.B) path_obs_env<W>(P, env, gl, J, mod, dim, pitch, out + env * pitch);
     return;
   }
-  float* lds = (float*)orl_lds_raw + (size_t)wv * 8 * pitch;
+  float* lds = (float*)orl_lds_raw + (size_t)v.wv * 8 * pitch;
   if (env < P.B) path_obs_env<W>(P, env, gl, J, mod, dim, pitch, lds + (lane >> 3) * pitch);
   wave_fence();
   // the wavefront's rows are one contiguous range of the output: 4 floats per lane and store

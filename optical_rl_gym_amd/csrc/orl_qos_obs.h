@@ -1,5 +1,5 @@
 // orl_qos_obs.h — MatrixObservationWithPaths (qos_constrained_ra.py:440-493) of the pending service of every QoSConstrainedRA
-// env (include/orl.h, orl_batch_matrix_paths_observation); included by orl_api.hip.
+// env (include/orl.h, orl_batch_matrix_paths_observation); included by orl_api.hip behind orl_view.h.
 //
 // Per env a row of dim = E * S * (k + 1) + 1 bytes at a device pitch of round_up(dim, 16): the reference's [E, (k + 1) S] matrix
 // flattened link-major, then the service class.  Every block b of S columns of link l is a prefix run of ones of length
@@ -15,16 +15,14 @@
 // LDS as u16, in row order: "segment" g = l (k + 1) + b covers columns [g S, (g + 1) S).  Phase 2: lane c writes the 16-byte
 // chunks c, c + 64, ... of the row; a chunk starts in segment g at offset o (one division per lane, then stepped by 1 024
 // columns without dividing) and walks its segments, each adding a run of ones to a 16-bit field expanded to bytes in
-// registers.  Only 16-byte stores, no atomics, no host synchronisation: graph-capturable.
+// registers (view_bits16_bytes of orl_view.h, shared with the action masks; the phase-2 walk, the class byte and the guard against a
+// pair outside the topology are this view's own).  Only 16-byte stores, no atomics, no host synchronisation: graph-capturable.
 #pragma once
 
 #define ORL_QOBS_WAVES 4  // wavefronts (envs) per workgroup
 
 // LDS bytes of one wavefront: E (k + 1) u16 run lengths, padded to 16 bytes
 __host__ __device__ inline int qos_obs_wave_lds(int E, int K) { return (E * (K + 1) * 2 + 15) / 16 * 16; }
-
-// 4 bits -> 4 bytes of 0/1 (bit i lands at bit 8 i; the four partial products do not overlap)
-__device__ __forceinline__ u32 qobs_nibble_bytes(u32 x) { return (x * 0x00204081u) & 0x01010101u; }
 
 __global__ void __launch_bounds__(256) k_qos_matrix_obs(DevParams P, unsigned char* out, int pitch) {
   const int lane = lane_id();
@@ -80,11 +78,7 @@ __global__ void __launch_bounds__(256) k_qos_matrix_obs(DevParams P, unsigned ch
       bits |= ((1u << ones) - 1u) << i;
       i += take;
     }
-    uint4 v;
-    v.x = qobs_nibble_bytes(bits & 15u);
-    v.y = qobs_nibble_bytes((bits >> 4) & 15u);
-    v.z = qobs_nibble_bytes((bits >> 8) & 15u);
-    v.w = qobs_nibble_bytes((bits >> 12) & 15u);
+    uint4 v = view_bits16_bytes(bits);
     const int j = ncols - c0;  // the class column (dim - 1); the pad columns behind it stay 0
     if (j >= 0 && j < 16) {
       const u32 cb = ((u32)cls & 255u) << (8 * (j & 3));

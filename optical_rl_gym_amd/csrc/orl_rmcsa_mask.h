@@ -1,5 +1,6 @@
 // orl_rmcsa_mask.h — the two-stage action masks of RMCSA's pending service (include/orl.h, ORL_MASK_PATH_MOD / ORL_MASK_CORE_SLOT);
-// included by orl_kernels.hip.
+// included by orl_kernels.hip behind orl_view.h (the kernel's opening, the decode of the pending service, the rows' way from LDS
+// to memory and the LDS budget rule are shared with the other views and live there).
 //
 // An RMCSA action is (path p, modulation m, core c, first slot s).  With n = nslots[br_idx][m], stepping it provisions iff
 // (rmcsa_env.py:209-289 with is_path_free :767-794, get_number_slots :753-765, _crosstalk_is_acceptable :341-384)
@@ -13,15 +14,15 @@
 // Nothing of the env is written.
 //
 // Layout of the work, as k_action_mask: 8 lanes per env, 8 envs per wavefront, 1 / 2 / 4 wavefronts per workgroup (what the LDS
-// rows allow: rmcsa_mask_waves).
+// rows allow: view_waves).
 //   PATH_MOD   "a run of >= n free slots exists" is monotone in n, so one number per (path, core) serves every modulation: the
 //              longest free run of the AND of the path's link rows in that core.  Lanes walk the (path, core) pairs path-major as
 //              the RMCSA branch of policy_g and leave the runs in LDS; pairs of a path that no modulation reaches at this bit rate
 //              load nothing.  Then lane = path: the largest run over the cores against nslots of each modulation within reach, M
 //              bits into the path's word.
 //   CORE_SLOT  lane = core: row_runs_ge of the given path's AND-row in that core, for the given modulation's n.
-// Then the wavefront streams its 8 envs' rows as 16-byte stores (the tail of k_action_mask: a 16-column chunk is a 16-bit field
-// of the env's bit rows, expanded to bytes in registers).  No atomics, no host synchronisation: graph-capturable.
+// Then the wavefront streams its 8 envs' rows as 16-byte stores (view_store_rows of orl_view.h: a 16-column chunk is a 16-bit
+// field of the env's bit rows, expanded to bytes in registers).  No atomics, no host synchronisation: graph-capturable.
 #pragma once
 
 // u32 words of LDS per env: `rows` bit rows of `rw` words, a pad word, the "has a provisioning column" flag; PATH_MOD: the k C
@@ -31,14 +32,6 @@ __host__ __device__ inline int rmcsa_mask_row_words(int layout, int W) { return 
 __host__ __device__ inline int rmcsa_mask_env_words(int layout, int W, int K, int C) {
   return rmcsa_mask_rows(layout, K, C) * rmcsa_mask_row_words(layout, W) + 2 + (layout == ORL_MASK_PATH_MOD ? K * C : 0);
 }
-// wavefronts (of 8 envs) per workgroup: the most of 4, 2, 1 whose rows fit 48 KiB of LDS; 0: not even one does
-inline int rmcsa_mask_waves(int layout, int W, int K, int C) {
-  const size_t wave = (size_t)8 * rmcsa_mask_env_words(layout, W, K, C) * sizeof(u32);
-  for (int w = 4; w >= 1; w >>= 1)
-    if (w * wave <= 48 * 1024) return w;
-  return 0;
-}
-
 // is modulation m within both reach limits for a path of length len at bit-rate index br_idx?
 __device__ __forceinline__ bool rmcsa_reach(const DevParams& P, double len, int m, int br_idx) {
   return len < P.lmax_xt[m] && len < P.lmax_snr[m * P.n_br + br_idx];
@@ -46,22 +39,19 @@ __device__ __forceinline__ bool rmcsa_reach(const DevParams& P, double len, int 
 
 template <int W>
 __global__ void __launch_bounds__(256) k_rmcsa_mask(DevParams P, unsigned char* out, int layout, int pitch, const int* given, int gstride) {
-  const int lane = lane_id(), gl = lane & 7, wv = (int)(threadIdx.x >> 6), waves = (int)(blockDim.x >> 6);
-  const i64 env0 = ((i64)blockIdx.x * waves + wv) * 8;  // the wavefront's first env
-  const i64 env = env0 + (lane >> 3);
+  const ViewLanes v = view_lanes();
+  const int lane = v.lane, gl = v.gl;
   const int K = P.K, S = P.S, M = P.M, C = P.C;
   const bool pm = layout == ORL_MASK_PATH_MOD;
   const int nrows = rmcsa_mask_rows(layout, K, C), rw = rmcsa_mask_row_words(layout, W), ew = rmcsa_mask_env_words(layout, W, K, C);
   const int cpp = pm ? M : S;  // columns per bit row
-  u32* lds = (u32*)orl_lds_raw + (size_t)wv * 8 * ew;
+  u32* lds = (u32*)orl_lds_raw + (size_t)v.wv * 8 * ew;
   u32* mine = lds + (lane >> 3) * ew;
   int any = 0;
-  if (env < P.B) {
-    const u64* rec = P.scal + env * ORL_SCAL_WORDS;
-    const u64 sd = rec[SC_SRC_DST], br = rec[SC_BR_IDX];
-    const int src = (int)(u32)sd, dst = (int)(sd >> 32), br_idx = (int)(br >> 32);
-    const int np = P.n_paths[src * P.N + dst], pb = (src * P.N + dst) * K;
-    const u64* bm = P.bitmap + env * P.bm_words;
+  if (v.env < P.B) {
+    const PendingSvc sv = view_pending(P, v.env);
+    const int br_idx = sv.br_idx, np = sv.np, pb = sv.pb;
+    const u64* bm = sv.bm;
     const unsigned char* nsl = P.nslots + br_idx * M;
     if (pm) {
       u32* runs = mine + nrows * rw + 2;  // [np][C] longest free runs
@@ -88,7 +78,7 @@ __global__ void __launch_bounds__(256) k_rmcsa_mask(DevParams P, unsigned char* 
         mine[p] = bits;
       }
     } else {
-      const int p = given[env * gstride], m = given[env * gstride + 1];
+      const int p = given[v.env * gstride], m = given[v.env * gstride + 1];
       const bool ok = p >= 0 && p < np && m >= 0 && m < M && rmcsa_reach(P, P.path_length[pb + p], m, br_idx);
       const PathRec prec = path_rec_load(P, pb + (ok ? p : 0));
       const int n = ok ? (int)nsl[m] : 1;
@@ -103,36 +93,5 @@ __global__ void __launch_bounds__(256) k_rmcsa_mask(DevParams P, unsigned char* 
   any = g8_max(any);
   if (gl == 0) { mine[nrows * rw] = 0u; mine[nrows * rw + 1] = (u32)any; }
   wave_fence();
-  // the wavefront's 8 output rows, 16 columns (bytes) per lane and store
-  const int ncols = nrows * cpp, nch = pitch >> 4;
-  const int allow = P.allow_rejection != 0;
-  for (int g = lane; g < 8 * nch; g += 64) {
-    const int el = g / nch, ch = g - el * nch;
-    const i64 e = env0 + el;
-    if (e >= P.B) break;
-    const u32* rows = lds + el * ew;
-    const int c0 = 16 * ch, c1 = c0 + 16 < ncols ? c0 + 16 : ncols;
-    u32 bits = 0u;
-    if (!allow && !rows[nrows * rw + 1]) {
-      bits = c1 > c0 ? (1u << (c1 - c0)) - 1u : 0u;  // fallback
-    } else {
-      for (int col = c0; col < c1;) {
-        const int r = col / cpp, s = col - r * cpp;
-        const int take = cpp - s < c1 - col ? cpp - s : c1 - col;  // <= 16
-        const u32* rp = rows + r * rw + (s >> 5);
-        const int off = s & 31;
-        u32 v = rp[0] >> off;
-        if (off) v |= rp[1] << (32 - off);
-        bits |= (v & ((1u << take) - 1u)) << (col - c0);
-        col += take;
-      }
-    }
-    if (allow && ncols >= c0 && ncols < c0 + 16) bits |= 1u << (ncols - c0);  // reject column
-    uint4 o;
-    o.x = mask_nibble_bytes(bits & 15u);
-    o.y = mask_nibble_bytes((bits >> 4) & 15u);
-    o.z = mask_nibble_bytes((bits >> 8) & 15u);
-    o.w = mask_nibble_bytes((bits >> 12) & 15u);
-    *(uint4*)(out + e * pitch + c0) = o;
-  }
+  view_store_rows(lds, nrows, rw, cpp, ew, nrows * rw, P.allow_rejection, v.env0, P.B, out, pitch);
 }

@@ -692,6 +692,21 @@ class BatchedOpticalEnv:
         self._ck(self.lib.orl_batch_get_rates(self._h, la.ctypes.data, lh.ctypes.data))
         return la, lh
 
+    # ---- the views of the pending service: action masks, MatrixObservationWithPaths, path features ---------------------------
+    def _view_rows(self, call, dim, dtype, fetch, out=None):
+        """The rows of one view: `call(host pointer or None)` queues the launch and, given a pointer, fetches [num_envs, dim()] items
+        of `dtype` into it.  fetch=False only queues (returns None); otherwise the rows land in `out` or in a fresh array."""
+        if not fetch:
+            call(None)
+            return None
+        shape = (self.num_envs, dim())
+        if out is None:
+            out = np.empty(shape, dtype)
+        elif out.shape != shape or out.dtype != dtype or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous %s array of shape %r" % (np.dtype(dtype).name, shape))
+        call(out.ctypes.data)
+        return out
+
     # ---- action masks (include/orl.h, orl_batch_action_mask) -------------------------------------------
     MASK_LAYOUTS = {"joint": 0, "path": 1, "path_modulation": 2, "core_slot": 3}
 
@@ -720,11 +735,9 @@ class BatchedOpticalEnv:
             if g.shape != (self.num_envs, 2) or g.dtype.kind not in "iu":
                 raise ValueError("given must be an int array of shape %r, got %s %r" % ((self.num_envs, 2), g.dtype, g.shape))
             g = np.ascontiguousarray(g, np.int32)
-        out = None
-        if fetch:
-            dim, _pitch = self.action_mask_shape(layout)
-            out = np.empty((self.num_envs, dim), np.uint8)
-        self._ck(self.lib.orl_batch_action_mask_given(self._h, lay, None if g is None else g.ctypes.data, None if out is None else out.ctypes.data))
+        gp = None if g is None else g.ctypes.data
+        out = self._view_rows(lambda p: self._ck(self.lib.orl_batch_action_mask_given(self._h, lay, gp, p)),
+                              lambda: self.action_mask_shape(layout)[0], np.uint8, fetch)
         self._mask_layout = layout
         return None if out is None else out.view(np.bool_)
 
@@ -741,16 +754,8 @@ class BatchedOpticalEnv:
         with the service on that path; the service class in the last column.  `out` (a C-contiguous uint8 [num_envs, dim]
         array) receives the rows instead of a fresh array.  fetch=False only queues the launch on the batch's stream — read
         the rows in place with device_array("matrix_paths_obs") / device_tensor("matrix_paths_obs")."""
-        if not fetch:
-            self._ck(self.lib.orl_batch_matrix_paths_observation(self._h, None))
-            return None
-        dim, _pitch = self.matrix_paths_obs_shape()
-        if out is None:
-            out = np.empty((self.num_envs, dim), np.uint8)
-        elif out.shape != (self.num_envs, dim) or out.dtype != np.uint8 or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous uint8 array of shape %r" % ((self.num_envs, dim),))
-        self._ck(self.lib.orl_batch_matrix_paths_observation(self._h, out.ctypes.data))
-        return out
+        return self._view_rows(lambda p: self._ck(self.lib.orl_batch_matrix_paths_observation(self._h, p)),
+                               lambda: self.matrix_paths_obs_shape()[0], np.uint8, fetch, out)
 
     # ---- path features (include/orl.h, orl_batch_path_features): RMSA, DeepRMSA, RWA and RMCSA --------------------------------
     def path_features_shape(self, j=1):
@@ -771,23 +776,25 @@ class BatchedOpticalEnv:
         instead of a fresh array.  fetch=False only queues the launch on the batch's stream — read the rows in place with
         device_array("path_features") / device_tensor("path_features")."""
         j, mod = int(j), -1 if modulation is None else int(modulation)
-        if not fetch:
-            self._ck(self.lib.orl_batch_path_features(self._h, j, mod, None))
-            self._pf_j = j
-            return None
-        dim, _rows, _pitch = self.path_features_shape(j)
-        if out is None:
-            out = np.empty((self.num_envs, dim), np.float32)
-        elif out.shape != (self.num_envs, dim) or out.dtype != np.float32 or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous float32 array of shape %r" % ((self.num_envs, dim),))
-        self._ck(self.lib.orl_batch_path_features(self._h, j, mod, out.ctypes.data))
+        out = self._view_rows(lambda p: self._ck(self.lib.orl_batch_path_features(self._h, j, mod, p)),
+                              lambda: self.path_features_shape(j)[0], np.float32, fetch, out)
         self._pf_j = j
         return out
 
     # ---- zero-copy device views (an agent on the same GPU: no PCIe in the loop) -------------------------
     _BUFFERS = {"actions": (0, "<i4", 4), "reward": (1, "<f8", 0), "done": (2, "|u1", 0), "info": (3, "<f8", -1),
-                "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0), "action_mask": (7, "|b1", -3),
-                "matrix_paths_obs": (8, "|u1", -4), "path_features": (9, "<f4", -5)}
+                "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0), "action_mask": (7, "|b1", None),
+                "matrix_paths_obs": (8, "|u1", None), "path_features": (9, "<f4", None)}
+    # The views of the pending service: [num_envs, dim] rows of the last call at the device pitch.  name -> (the message while no
+    # call has been made, (dim, pitch in items) of those rows, item size).  Every mask layout and every j of the path features has
+    # a buffer of its own: a view taken after a "joint" call keeps showing the joint rows (as the last "joint" call left them)
+    # after "path" calls.
+    _VIEWS = {"action_mask": ("no action mask yet: call action_mask() (fetch=False only queues it) first",
+                              lambda self: self.action_mask_shape(getattr(self, "_mask_layout", "joint")), 1),
+              "matrix_paths_obs": ("no MatrixObservationWithPaths yet: call matrix_observation_with_paths() (fetch=False only "
+                                   "queues it) first", lambda self: self.matrix_paths_obs_shape(), 1),
+              "path_features": ("no path features yet: call path_features() (fetch=False only queues it) first",
+                                lambda self: self.path_features_shape(self._pf_j)[::2], 4)}
 
     def device_array(self, name):
         """The batch's device-resident I/O array `name` as an object with `__cuda_array_interface__` (what
@@ -797,24 +804,12 @@ class BatchedOpticalEnv:
         ptr, n = C.c_void_p(), C.c_int64()
         self._ck(self.lib.orl_batch_device_buffer(self._h, which, C.byref(ptr), C.byref(n)))
         strides = None
-        if cols == -3:
-            # the rows of the last action_mask(), [num_envs, dim] at the device pitch.  Each layout has a buffer of its own: a view
-            # taken after a "joint" call keeps showing the joint rows (as the last "joint" call left them) after "path" calls
+        if name in self._VIEWS:
+            not_yet, shape_of, item = self._VIEWS[name]
             if n.value == 0 or not ptr.value:
-                raise _lib.OrlError("no action mask yet: call action_mask() (fetch=False only queues it) first")
-            cols, pitch = self.action_mask_shape(getattr(self, "_mask_layout", "joint"))
-            strides = (pitch, 1)
-        elif cols == -4:  # the rows of the last matrix_observation_with_paths(), [num_envs, dim] at the device pitch
-            if n.value == 0 or not ptr.value:
-                raise _lib.OrlError("no MatrixObservationWithPaths yet: call matrix_observation_with_paths() (fetch=False only "
-                                    "queues it) first")
-            cols, pitch = self.matrix_paths_obs_shape()
-            strides = (pitch, 1)
-        elif cols == -5:  # the rows of the last path_features(), [num_envs, dim] at the device pitch; each j has a buffer of its own
-            if n.value == 0 or not ptr.value:
-                raise _lib.OrlError("no path features yet: call path_features() (fetch=False only queues it) first")
-            cols, _rows, pitch = self.path_features_shape(self._pf_j)
-            strides = (4 * pitch, 4)
+                raise _lib.OrlError(not_yet)
+            cols, pitch = shape_of(self)
+            strides = (item * pitch, item)
         cols = {-1: self.n_info, -2: self.obs_dim}.get(cols, cols)
         if n.value == 0 or not ptr.value:
             raise _lib.OrlError("this env family has no '%s' array" % name)

@@ -330,16 +330,23 @@ class MultiDeviceBatch:
     def matrix_observation(self):
         return self._cat(self._map(lambda r: self.shards[r].matrix_observation()))
 
+    def _view_rows(self, call, fetch, out=None):
+        """One view of every shard — `call(r, **kw)` is shard r's method: the rows in env order, with `out` ([num_envs, dim],
+        C-contiguous) every shard writing its own slice of it; fetch=False only queues."""
+        if out is None or not fetch:
+            parts = self._map(lambda r: call(r, fetch=fetch))
+            return self._cat(parts) if fetch else None
+        self._map(lambda r: call(r, out=out[self.bounds[r]:self.bounds[r + 1]]))
+        return out
+
     def action_mask(self, layout="joint", fetch=True, given=None):
         """BatchedOpticalEnv.action_mask of every shard; `given` ([num_envs, 2], "core_slot") is cut by the shards' bounds."""
         if given is None:  # (shards may be any objects with the batch interface: the argument is passed only where it is used)
-            out = self._map(lambda r: self.shards[r].action_mask(layout, fetch=fetch))
-        else:
-            given = np.asarray(given)
-            if given.shape != (self.num_envs, 2):
-                raise ValueError("given must be an int array of shape %r, got %r" % ((self.num_envs, 2), given.shape))
-            out = self._map(lambda r: self.shards[r].action_mask(layout, fetch=fetch, given=self._cut(given, r)))
-        return self._cat(out) if fetch else None
+            return self._view_rows(lambda r, **kw: self.shards[r].action_mask(layout, **kw), fetch)
+        given = np.asarray(given)
+        if given.shape != (self.num_envs, 2):
+            raise ValueError("given must be an int array of shape %r, got %r" % ((self.num_envs, 2), given.shape))
+        return self._view_rows(lambda r, **kw: self.shards[r].action_mask(layout, given=self._cut(given, r), **kw), fetch)
 
     def path_features_shape(self, j=1):
         return self.shards[0].path_features_shape(j)
@@ -347,22 +354,14 @@ class MultiDeviceBatch:
     def path_features(self, j=1, modulation=None, fetch=True, out=None):
         """BatchedOpticalEnv.path_features of every shard, rows in env order; with `out` ([num_envs, dim] float32, C-contiguous)
         every shard writes its own rows."""
-        if out is None or not fetch:
-            parts = self._map(lambda r: self.shards[r].path_features(j, modulation, fetch=fetch))
-            return self._cat(parts) if fetch else None
-        self._map(lambda r: self.shards[r].path_features(j, modulation, out=out[self.bounds[r]:self.bounds[r + 1]]))
-        return out
+        return self._view_rows(lambda r, **kw: self.shards[r].path_features(j, modulation, **kw), fetch, out)
 
     def matrix_paths_obs_shape(self):
         return self.shards[0].matrix_paths_obs_shape()
 
     def matrix_observation_with_paths(self, fetch=True, out=None):
         """The shards' rows in env order; with `out` ([num_envs, dim] uint8, C-contiguous) every shard writes its own rows."""
-        if out is None or not fetch:
-            parts = self._map(lambda r: self.shards[r].matrix_observation_with_paths(fetch=fetch))
-            return self._cat(parts) if fetch else None
-        self._map(lambda r: self.shards[r].matrix_observation_with_paths(out=out[self.bounds[r]:self.bounds[r + 1]]))
-        return out
+        return self._view_rows(lambda r, **kw: self.shards[r].matrix_observation_with_paths(**kw), fetch, out)
 
     def copy_envs(self, src, dst, keep_rng=False):
         """BatchedOpticalEnv.copy_envs with global env indices, inside this sharded batch.  The pairs are cut by the shards that own

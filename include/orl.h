@@ -446,6 +446,34 @@ int orl_batch_matrix_paths_observation(orl_batch* b, uint8_t* out);
 int orl_batch_path_features_shape(const orl_batch* b, int j, int32_t* dim, int32_t* rows, int32_t* pitch);
 int orl_batch_path_features(orl_batch* b, int j, int modulation, float* out /* host [n_envs][dim], or NULL */);
 
+/* First-fit completion of a partial RMCSA action: the agent fixes a prefix of (path p, modulation m, core c, first slot s) — nothing,
+ * the path, the pair or the triple — and the device fills in the rest under prov(p, m, c, s), the predicate of ORL_MASK_PATH_MOD /
+ * ORL_MASK_CORE_SLOT above, unchanged.  For an env whose first g = n_given action columns are given:
+ *   g = 3 (p, m, c): the lowest s with prov(p, m, c, s);
+ *   g = 2 (p, m):    the lowest column c * S + s of the env's ORL_MASK_CORE_SLOT row for that pair — cores in order, then slots;
+ *   g = 1 (p):       m*(p), then as g = 2; m*(p) = the modulation that needs the fewest slots at the service's bit rate among those
+ *                    within both reach limits for p (ties: the lowest index); none within reach: no completion.  "Enough free
+ *                    slots exist" is monotone in n, so this completion provisions iff any column p * M + . of the env's
+ *                    ORL_MASK_PATH_MOD row is set (without the fallback): that row is the mask of a one-head path-only agent too;
+ *   g = 0:           the first path, in order, whose g = 1 completion exists — a reach-aware k-shortest-path first fit.
+ * A given column out of range — negative, p >= n_paths[src, dst], m >= M, c >= C — or a pair beyond reach has no completion.  "No
+ * completion" is the reject action (k, M, C, S), which RMCSA's heuristic (policy id 1, SAP_BM_FC_FF) returns too; it is inside actions_output under
+ * either allow_rejection.  Two deliberate differences from SAP_BM_FC_FF and the reference's range(0, S - n)
+ * (rmcsa_env.py:889-906): s = S - n is tried, and an action the reach check of step() would refuse is never returned (the
+ * heuristic takes each path's best modulation by length alone).
+ * The completion reads the pending service and the slot maps as the last step or reset left them and writes only the env's row of
+ * ORL_BUF_ACTIONS, all four columns (a valid prefix comes back as given); env state, flags and snapshot bytes do not change.
+ * orl_batch_complete_actions: one launch on the batch's stream.  given == NULL: the prefix is columns 0 .. n_given - 1 of
+ * ORL_BUF_ACTIONS, where an agent on the GPU writes its choice; with actions_out == NULL as well the call does not synchronise,
+ * allocates nothing and is graph-capturable.  A host `given` [n_envs][n_given] int32 goes through a page-locked buffer of the batch
+ * into a device buffer of the batch (both allocated by the first such call, and not those of orl_batch_action_mask_given),
+ * asynchronously on the batch's stream; ORL_BUF_ACTIONS is then written by the kernel only.  With actions_out != NULL the rows are
+ * copied out and the call synchronises.  ORL_E_INVALID, before anything is queued: a family other than RMCSA (the single-core
+ * families have ORL_POLICY_PATH_FF), n_given outside 0 .. 3, given != NULL with n_given == 0. */
+int orl_batch_complete_actions(orl_batch* b, int n_given,
+                               const int32_t* given /* host [n_envs][n_given], or NULL = columns 0..n_given-1 of ORL_BUF_ACTIONS */,
+                               int32_t* actions_out /* host [n_envs][4], or NULL */);
+
 /* Snapshot / restore of the complete simulation state of the batch (slot maps, pending releases, RNG, statistics,
  * counters).  The reference has no equivalent (no checkpointing); used for long PPO runs.  The per-env
  * rates (orl_batch_set_rates) are configuration and not part of it. */

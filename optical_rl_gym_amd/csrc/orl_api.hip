@@ -698,6 +698,8 @@ extern "C" void orl_batch_destroy(orl_batch* b) try {
   if (b->h_copy_idx) hipHostFree(b->h_copy_idx);
   if (b->h_mask_given) hipHostFree(b->h_mask_given);
   if (b->ev_given_up) hipEventDestroy(b->ev_given_up);
+  if (b->h_complete_given) hipHostFree(b->h_complete_given);
+  if (b->ev_complete_up) hipEventDestroy(b->ev_complete_up);
   if (b->ev_copy_up) hipEventDestroy(b->ev_copy_up);
   if (b->ev_copy) hipEventDestroy(b->ev_copy);
   if (b->spec_handle) dlclose(b->spec_handle);
@@ -1305,6 +1307,41 @@ extern "C" int orl_batch_action_mask_given(orl_batch* b, int layout, const int32
 ORL_ABI_CATCH_INT
 
 extern "C" int orl_batch_action_mask(orl_batch* b, int layout, uint8_t* out) { return orl_batch_action_mask_given(b, layout, nullptr, out); }
+
+// first-fit completion of partial RMCSA actions (orl_rmcsa_complete.h)
+extern "C" int orl_batch_complete_actions(orl_batch* b, int n_given, const int32_t* given, int32_t* actions_out) try {
+  if (!b) return fail(ORL_E_INVALID, "null argument");
+  if (b->P.env_type != ENV_RMCSA)
+    return fail(ORL_E_INVALID, "action completion is defined for RMCSA only (the single-core families have ORL_POLICY_PATH_FF)");
+  if (n_given < 0 || n_given > 3) return fail(ORL_E_INVALID, "n_given = %d outside 0 .. 3 (nothing, path, + modulation, + core)", n_given);
+  if (given && n_given == 0) return fail(ORL_E_INVALID, "`given` with n_given == 0: there is no column to read");
+  HIPCHK(hipSetDevice(b->device));
+  const int* src = b->P.actions;  // columns 0 .. n_given - 1 of ORL_BUF_ACTIONS: where an agent on the GPU writes its choice
+  int stride = 4;
+  if (given) {
+    const size_t cap = (size_t)b->P.B * 3 * sizeof(int32_t), bytes = (size_t)b->P.B * n_given * sizeof(int32_t);
+    if (!b->complete_given) {
+      if (int rc = view_buffer(b, b->complete_given, cap, "action completion")) return rc;
+      HIPCHK(hipHostMalloc((void**)&b->h_complete_given, cap, hipHostMallocPortable));
+      HIPCHK(hipEventCreateWithFlags(&b->ev_complete_up, hipEventDisableTiming));
+    } else {
+      HIPCHK(hipEventSynchronize(b->ev_complete_up));  // (the last call's upload has left the staging buffer)
+    }
+    memcpy(b->h_complete_given, given, bytes);
+    HIPCHK(hipMemcpyAsync(b->complete_given, b->h_complete_given, bytes, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipEventRecord(b->ev_complete_up, b->stream));
+    src = b->complete_given;
+    stride = n_given;
+  }
+  ORL_LAUNCH(rmcsa_complete, b, n_given, src, stride);
+  HIPCHK(hipGetLastError());
+  if (actions_out) {
+    HIPCHK(hipMemcpyAsync(actions_out, b->P.actions, (size_t)b->P.B * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+  }
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
 
 // path features (orl_path_obs.h)
 static int path_features_check(const orl_batch* b, int j, int modulation) {

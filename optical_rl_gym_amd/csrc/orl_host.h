@@ -90,6 +90,9 @@ struct orl_batch {
   int32_t* mask_given = nullptr;   // ORL_MASK_CORE_SLOT with a host `given`: the (path, modulation) pairs [B][2] on the device and in
   int32_t* h_mask_given = nullptr; // page-locked memory, allocated on first use
   hipEvent_t ev_given_up = nullptr;  // behind the last upload out of h_mask_given: the next call waits for it before it refills the buffer
+  int32_t* complete_given = nullptr;    // orl_batch_complete_actions with a host `given`: the prefixes [B][n_given <= 3] on the device and in
+  int32_t* h_complete_given = nullptr;  // page-locked memory (both [B][3]), allocated on first use — not the masks' pair: either call may
+  hipEvent_t ev_complete_up = nullptr;  // refill its staging buffer without waiting for the other's upload; behind the last upload out of it
   int mask_last = -1;              // layout of the last launch: what ORL_BUF_ACTION_MASK hands out (-1: none yet)
   float* pf_buf[9] = {};           // path features per block count j (1 .. 8): [B][pitch] floats, allocated by the first
                                    // orl_batch_path_features of that j (a view of one stays that j's)
@@ -141,6 +144,8 @@ template <int W> void obs(orl_batch* b, int with_terminal);                // De
 template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, int pitch);  // k_action_mask -> out [B][pitch]
 // k_rmcsa_mask -> out [B][pitch]; given: device (path, modulation) of env e at given[e * gstride + 0 / 1]; -1: refused (nothing launched)
 template <int W> int rmcsa_mask(orl_batch* b, int layout, unsigned char* out, int pitch, const int* given, int gstride);
+// k_rmcsa_complete: the first n_given action columns of env e at given[e * gstride ...] (device) completed first-fit into P.actions
+template <int W> void rmcsa_complete(orl_batch* b, int n_given, const int* given, int gstride);
 template <int W> void path_features(orl_batch* b, float* out, int j, int mod);  // k_path_features -> out [B][round_up(dim, 4)] floats
 // k_persist in the form `ch` (the run's choice for the whole batch; use_spec: made for the attached specialisation library) over the
 // env range of view VP up to step `target` of this run, then k_rel_tail, on stream st

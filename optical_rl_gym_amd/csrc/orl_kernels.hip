@@ -11,6 +11,7 @@
 //   k_obs8/k_obs DeepRMSA observation of the pending service
 //   k_action_mask action masks of the pending service (orl_mask.h)                      8 lanes per env, lane = path
 //   k_rmcsa_mask RMCSA's path-modulation and core-slot masks (orl_rmcsa_mask.h)         8 lanes per env, lane = (path, core) / core
+//   k_rmcsa_complete first-fit completion of a partial RMCSA action (orl_rmcsa_complete.h)  8 lanes per env, lane = (path, core)
 //   k_path_features path-feature observation of the pending service (orl_path_obs.h)    8 lanes per env, rows striped over them
 //               [what these three views share — and k_qos_matrix_obs of orl_api.hip with them — lives in orl_view.h]
 // Launchers (orl_launch::*<W>) are explicitly instantiated at the end; orl_api.hip dispatches on the batch's W.
@@ -2050,6 +2051,7 @@ __global__ void __launch_bounds__(256) k_obs8(DevParams P, int with_terminal) {
 #include "orl_view.h"  // what the three views below share: the opening, the pending service, bit rows -> byte rows, the LDS budget
 #include "orl_mask.h"  // k_action_mask: action masks of the pending service (RMSA, DeepRMSA, RWA)
 #include "orl_rmcsa_mask.h"  // k_rmcsa_mask: the two-stage masks of RMCSA (path-modulation, core-slot)
+#include "orl_rmcsa_complete.h"  // k_rmcsa_complete: a partial RMCSA action completed first-fit under the masks' rule
 #include "orl_path_obs.h"  // k_path_features: the path-feature observation of the pending service (every slot-map family)
 #endif
 
@@ -2271,6 +2273,16 @@ template <int W> int rmcsa_mask(orl_batch* b, int layout, unsigned char* out, in
   return 0;
 }
 
+// k_rmcsa_complete (orl_rmcsa_complete.h): the first n_given columns of env e at given[e * gstride ...] (device int32) completed into
+// its row of P.actions
+template <int W> void rmcsa_complete(orl_batch* b, int n_given, const int* given, int gstride) {
+  const DevParams& VP = b->P;
+  const int waves = 4;
+  const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
+  hipLaunchKernelGGL((k_rmcsa_complete<W>), dim3(grid), dim3(64 * waves), 0, b->stream, VP, n_given, given, gstride);
+  ORL_TK(b, "k_rmcsa_complete");
+}
+
 // k_path_features (orl_path_obs.h) into `out` ([B][pitch] floats on the device): j blocks per row, RMCSA under modulation `mod`
 // (-1: each path's best).  The wavefront's rows are staged in LDS where 8 of them fit 48 KiB, else every lane stores its own blocks
 // (-DORL_PATH_OBS_STAGE=0: always — the build the two forms were measured against each other with).
@@ -2437,6 +2449,7 @@ template void step64<ORL_W>(orl_batch*, int, int, int);
 template void obs<ORL_W>(orl_batch*, int);
 template int action_mask<ORL_W>(orl_batch*, int, unsigned char*, int);
 template int rmcsa_mask<ORL_W>(orl_batch*, int, unsigned char*, int, const int*, int);
+template void rmcsa_complete<ORL_W>(orl_batch*, int, const int*, int);
 template void path_features<ORL_W>(orl_batch*, float*, int, int);
 template void persist<ORL_W>(orl_batch*, const DevParams&, const PersistChoice&, bool, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);
 template void step2<ORL_W>(orl_batch*, int);

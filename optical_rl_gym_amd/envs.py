@@ -101,6 +101,33 @@ class _PinnedBlock:
             pass
 
 
+class _RawDeviceArray:  # what torch.as_tensor consumes
+    def __init__(self, cai):
+        self.__cuda_array_interface__ = cai
+
+
+class _DeviceArray:
+    """Device-resident array of a batch: `__cuda_array_interface__` (torch.as_tensor, CuPy) and DLPack (`torch.from_dlpack`,
+    `cupy.from_dlpack`, jax): no copy either way; the batch owns the memory.  A plain object without a reference cycle: it, and the
+    batch it keeps alive, go when the last reference does, not whenever the cycle collector next runs — a batch's page-locked
+    buffers are given back with it (hipHostFree), which must not fall into somebody's stream capture."""
+
+    def __init__(self, cai, device_id, owner):
+        self.__cuda_array_interface__ = cai
+        self._device_id = device_id
+        self._owner = owner  # keeps the batch alive
+
+    def __dlpack_device__(self):
+        return (10, self._device_id)  # kDLROCM
+
+    def __dlpack__(self, stream=None, **kw):
+        import torch
+
+        t = torch.as_tensor(_RawDeviceArray(self.__cuda_array_interface__), device="cuda:%d" % self._device_id)
+        t._orl_owner = self._owner
+        return t.__dlpack__() if stream is None else t.__dlpack__(stream=stream)
+
+
 class BatchedOpticalEnv:
     """Common machinery; use one of the four family classes below."""
 
@@ -741,6 +768,40 @@ class BatchedOpticalEnv:
         self._mask_layout = layout
         return None if out is None else out.view(np.bool_)
 
+    # ---- first-fit completion of partial RMCSA actions (include/orl.h, orl_batch_complete_actions) ------------------------------
+    @staticmethod
+    def completion_prefix(given, n_given, num_envs):
+        """(int32 [num_envs, g] or None, g) from the arguments of complete_actions(); ValueError for a bad shape or dtype."""
+        if given is None:
+            if n_given is None:
+                raise ValueError("n_given is required with given=None (the prefix is read from the actions buffer)")
+            return None, int(n_given)
+        g = np.asarray(given)
+        if g.ndim == 1:
+            g = g[:, None]
+        if g.ndim != 2 or g.shape[0] != num_envs or not 1 <= g.shape[1] <= 3 or g.dtype.kind not in "iu":
+            raise ValueError("given must be an int array of shape (%d, 1 .. 3) or (%d,), got %s %r" % (num_envs, num_envs, g.dtype, g.shape))
+        n = g.shape[1] if n_given is None else int(n_given)
+        if n != g.shape[1] and 1 <= n <= 3:  # (an n_given outside 1 .. 3 is the library's to refuse, with or without `given`)
+            raise ValueError("n_given = %d, but given has %d columns" % (n, g.shape[1]))
+        return np.ascontiguousarray(g, np.int32), n
+
+    def complete_actions(self, given=None, n_given=None, fetch=True):
+        """RMCSA: complete a prefix of every env's (path, modulation, core, first slot) action first-fit on the device, under the
+        rule of the two-stage masks: int32 [num_envs, 4], left in device_array("actions") for the next step(None).  `given`: an int
+        array [num_envs, g], g = 1 (the path; a 1-D array too), 2 (+ modulation) or 3 (+ core); given=None with n_given = 0 .. 3
+        reads the prefix from columns 0 .. n_given - 1 of device_array("actions"), where an agent on the GPU writes it (n_given=0: a
+        reach-aware first fit over all paths).  g = 2 yields the lowest set column of the pair's "core_slot" row; g = 1 takes the
+        modulation within reach that needs the fewest slots, and provisions iff any of the path's M columns of the
+        "path_modulation" row is set.  No completion (a column out of range, a pair beyond reach, no room) is the reject action
+        (k, M, C, S).  Env state and flags are not touched.  fetch=False only queues the launch on the batch's stream (returns
+        None; graph-capturable with given=None)."""
+        g, n = self.completion_prefix(given, n_given, self.num_envs)
+        out = self._act if fetch else None
+        self._keep_given = g  # (alive until the call returns: the library copies it before it does)
+        self._ck(self.lib.orl_batch_complete_actions(self._h, n, None if g is None else g.ctypes.data, None if out is None else out.ctypes.data))
+        return None if out is None else out.copy()
+
     # ---- MatrixObservationWithPaths (include/orl.h, orl_batch_matrix_paths_observation): QoSConstrainedRA only ---------------
     def matrix_paths_obs_shape(self):
         """(dim, pitch): dim = links * S * (k + 1) + 1 columns per env, rows pitch bytes apart in the device buffer."""
@@ -816,28 +877,7 @@ class BatchedOpticalEnv:
         shape = (self.num_envs, cols) if cols else (self.num_envs,)
 
         cai = {"shape": shape, "typestr": typestr, "data": (int(ptr.value), False), "version": 2, "strides": strides}
-        device_id, owner = self.device_id, self
-
-        class _Raw:  # what torch.as_tensor consumes
-            __cuda_array_interface__ = cai
-
-        class _DeviceArray:
-            """Device-resident array of the batch: `__cuda_array_interface__` (torch.as_tensor, CuPy) and DLPack
-            (`torch.from_dlpack`, `cupy.from_dlpack`, jax): no copy either way; the batch owns the memory."""
-            __cuda_array_interface__ = cai
-            _owner = owner  # keeps the batch alive
-
-            def __dlpack_device__(self):
-                return (10, device_id)  # kDLROCM
-
-            def __dlpack__(self, stream=None, **kw):
-                import torch
-
-                t = torch.as_tensor(_Raw(), device="cuda:%d" % device_id)
-                t._orl_owner = owner
-                return t.__dlpack__() if stream is None else t.__dlpack__(stream=stream)
-
-        return _DeviceArray()
+        return _DeviceArray(cai, self.device_id, self)
 
     def device_tensor(self, name):
         """`device_array(name)` wrapped as a torch tensor on this batch's GPU (no copy)."""

@@ -449,6 +449,16 @@ class RMCSAEnv(_SingleEnv):
             given = np.asarray(given).reshape(1, 2)
         return self.batch.action_mask(layout, given=given)[0]
 
+    def complete_action(self, prefix=()):
+        """The action (path, modulation, core, first slot) that completes `prefix` — (), (path,), (path, modulation) or (path,
+        modulation, core) — first-fit on the device (BatchedOpticalEnv.complete_actions); the reject action (k, M, C, S) when
+        there is none."""
+        prefix = tuple(int(v) for v in prefix)
+        if len(prefix) > 3:
+            raise ValueError("prefix holds at most (path, modulation, core), got %r" % (prefix,))
+        given = np.asarray(prefix, np.int32).reshape(1, len(prefix)) if prefix else None
+        return tuple(int(v) for v in self.batch.complete_actions(given=given, n_given=len(prefix))[0])
+
     def _episode_hist(self, which):  # re-zeroed at every reset and never incremented (rmcsa_env.py:154-180, 391-407)
         return np.zeros((self.k_paths + 1, len(self.topo.modulations) + 1, self.num_spatial_resources + 1,
                          self.num_spectrum_resources + 1), dtype=int)

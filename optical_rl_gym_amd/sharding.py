@@ -348,6 +348,14 @@ class MultiDeviceBatch:
             raise ValueError("given must be an int array of shape %r, got %r" % ((self.num_envs, 2), given.shape))
         return self._view_rows(lambda r, **kw: self.shards[r].action_mask(layout, given=self._cut(given, r), **kw), fetch)
 
+    def complete_actions(self, given=None, n_given=None, fetch=True):
+        """BatchedOpticalEnv.complete_actions of every shard; `given` ([num_envs, g] or [num_envs]) is cut by the shards' bounds."""
+        from .envs import BatchedOpticalEnv
+
+        g, n = BatchedOpticalEnv.completion_prefix(given, n_given, self.num_envs)
+        out = self._map(lambda r: self.shards[r].complete_actions(given=self._cut(g, r), n_given=n, fetch=fetch))
+        return self._cat(out) if fetch else None
+
     def path_features_shape(self, j=1):
         return self.shards[0].path_features_shape(j)
 

@@ -280,7 +280,7 @@ class OpticalVecEnv:
 
     def __init__(self, batch, info_keywords=("episode_service_blocking_rate", "episode_bit_rate_blocking_rate"),
                  obs_dtype=np.float64, observation="default", max_logged_episodes=1 << 20, monitor_spill_path=None,
-                 rates_only_info=False, path_features_j=1):
+                 rates_only_info=False, path_features_j=1, action_completion=None):
         """observation: "default" (DeepRMSA: its 1-D vector; other families: None, as their Dict observation holds live
         objects), "matrix" (SimpleMatrixObservation built on the device: uint8 [2N + C*E*S]) or "matrix_paths"
         (QoSConstrainedRA only: MatrixObservationWithPaths built on the device, uint8 [E*S*(k+1) + 1]) or "path_features" (RMSA,
@@ -290,6 +290,10 @@ class OpticalVecEnv:
         keywords are blocking rates only, the step kernel may skip the compactness entries and the two link means — then
         `info_array()` / `device_tensors()["info"]` hold NaN in those columns instead of stale values, and close() puts the
         batch back into the full mode.
+        action_completion (RMCSA only): None — the family's MultiDiscrete (path, modulation, core, slot) space — or "path" /
+        "path_modulation": a one-head agent chooses the path (Discrete(k + 1)) or the pair (Discrete(k * M + 1), action p * M + m),
+        the last action being reject, and the device completes the action first-fit (batch.complete_actions) before it steps it;
+        `action_masks()` is then the batch's "path_modulation" row, for "path" reduced with any() over each path's M columns.
         Out of scope: `batch.copy_envs` under a VecEnv.  The host-side episode accumulators kept here (returns, lengths, the
         episode log) do not follow a copy of env states on the device."""
         self.batch = batch
@@ -297,6 +301,15 @@ class OpticalVecEnv:
         self.obs_dtype = np.dtype(obs_dtype)
         self.observation_mode = observation
         self.observation_space, self.action_space = make_spaces(batch, obs_dtype)
+        self.action_completion = action_completion
+        if action_completion is not None:
+            if action_completion not in ("path", "path_modulation"):
+                raise ValueError("action_completion must be None, \"path\" or \"path_modulation\", got %r" % (action_completion,))
+            if getattr(batch, "ENV_TYPE", None) != 3 or not hasattr(batch, "complete_actions"):
+                raise ValueError("action_completion is defined for RMCSA batches only (the single-core families have PATH_FF)")
+            self._n_mod = len(batch.modulation_formats)
+            cols = batch.k_paths * (self._n_mod if action_completion == "path_modulation" else 1)
+            self.action_space = _space_module().Discrete(cols + 1)
         if observation == "matrix":
             t = batch.topology
             dim = 2 * t.n_nodes + batch.num_spatial_resources * t.n_links * batch.num_spectrum_resources
@@ -349,11 +362,25 @@ class OpticalVecEnv:
         back into page-locked arrays — and returns: what the caller does until step_wait() overlaps the device's work."""
         self._actions = np.asarray(actions)
         self._queued = False
+        if self.action_completion is not None:  # the prefix completed on the device; the step then takes the device-resident actions
+            self.batch.complete_actions(given=self._completion_prefix(self._actions), fetch=False)
+            self._actions = None
         if self._async:
             direct = self._direct()
             self.batch.step_async(self._actions, auto_reset=True, obs_out=self._next_obs_buffer() if direct else None,
                                   fetch_info=not self._sparse_info)
             self._queued = True
+
+    def _completion_prefix(self, actions):
+        """The integers of the one-head action space as the given columns of complete_actions(): [n, 1] paths or [n, 2] (path,
+        modulation) pairs; the reject action becomes path k, which has no completion."""
+        a = np.asarray(actions).reshape(self.num_envs).astype(np.int64)
+        k = self.batch.k_paths
+        if self.action_completion == "path":
+            return np.minimum(a, k).astype(np.int32)[:, None]
+        M = self._n_mod
+        rej = a >= k * M
+        return np.stack([np.where(rej, k, a // M), np.where(rej, 0, a % M)], axis=1).astype(np.int32)
 
     def _next_obs_buffer(self):
         """Observations go straight into one of THREE page-locked arrays of the requested dtype, used in turn: the array a
@@ -538,6 +565,12 @@ class OpticalVecEnv:
     def action_masks(self):
         """Action masks of every env's pending service in the form of `action_space` (sb3_action_masks), bool [num_envs, n]:
         what sb3-contrib's MaskablePPO reads (`np.stack(venv.env_method("action_masks"))`).  Computed on the device."""
+        if self.action_completion is not None:
+            pm = self.batch.action_mask("path_modulation")
+            if self.action_completion == "path_modulation":
+                return pm
+            body = pm[:, :-1].reshape(self.num_envs, self.batch.k_paths, self._n_mod).any(axis=2)
+            return np.concatenate([body, pm[:, -1:]], axis=1)
         return sb3_action_masks(self.batch, self.batch.action_mask("joint"), self.action_space)
 
     def _env_action_masks(self, i):

@@ -312,6 +312,8 @@ int orl_host_free(void* p);
 #define ORL_BUF_PATH_FEATURES 9  /* f32 [n_envs][pitch]: rows of the last orl_batch_path_features (pitch, in floats, of
                                   * orl_batch_path_features_shape for that call's j); each j has a buffer of its own, allocated by
                                   * its first call; n_elements = 0 before any call */
+#define ORL_BUF_LINK_FEATURES 10  /* f32 [n_envs][pitch]: rows of the last orl_batch_link_features (pitch, in floats, of
+                                  * orl_batch_link_features_shape); allocated by the first call, n_elements = 0 before it */
 int orl_batch_device_buffer(orl_batch* b, int which, void** device_ptr, int64_t* n_elements);
 /* The HIP stream (hipStream_t) the batch queues its launches on.  An agent on the same GPU that queues ITS kernels on this
  * stream too (torch: `torch.cuda.ExternalStream(ptr)`) needs no synchronisation between its network and orl_batch_step: the
@@ -445,6 +447,33 @@ int orl_batch_matrix_paths_observation(orl_batch* b, uint8_t* out);
  * are read as the last step or reset left them; nothing of the env is written. */
 int orl_batch_path_features_shape(const orl_batch* b, int j, int32_t* dim, int32_t* rows, int32_t* pitch);
 int orl_batch_path_features(orl_batch* b, int j, int modulation, float* out /* host [n_envs][dim], or NULL */);
+
+/* Link features of the pending service of every env — the state per LINK, for agents that are graph networks over the topology,
+ * where the path features above describe it per candidate path: RMSA, DeepRMSA, RWA and RMCSA (QoSConstrainedRA, which has no slot
+ * maps, returns ORL_E_INVALID).  Per env a row of dim = 1 + 2 n_nodes + R F floats: the header of the path features (column 0 =
+ * bit_rate / 100, RWA: 0.0; column 1 + min(src, dst) = 1; column 1 + n_nodes + max(src, dst) = 1; other header columns 0), then
+ * R = cores * links blocks of F = 10 + k values, block r = c * links + l — the order of the slot maps, [cores][links] of
+ * orl_batch_get_slots; cores = 1 outside RMCSA; l is the link index of the topology's path_links and of orl_batch_get_link_stats.
+ * With a = the free-slot row of core c and link l, S its slots and f = the number of free slots:
+ *   [0] f / S;  [1] maximal free runs / S;  [2] longest free run / S (0 when there is none);
+ *   [3] first free slot / S;  [4] (last free slot + 1) / S;  both -1.0 when f == 0;
+ *   [5] cur_external_fragmentation and [6] cur_link_compactness of the row as it stands (rmsa_env.py:492-528 = rmcsa_env.py:635-672):
+ *       what _update_link_stats would feed into the link's running averages now — 0.0 for a row without a free slot; max_empty = 0
+ *       for a single free run and for exactly two free runs at the two ends of the row; compactness 1.0 with fewer than two used
+ *       runs.  RWA, whose reference keeps no such statistics, gets the same functions of the row;
+ *   [7], [8], [9] the link's running utilization, external_fragmentation and compactness (orl_batch_get_link_stats columns 0 .. 2)
+ *       cast to float32, the same three values for every core of a link (RWA: [8] and [9] are whatever the record holds);
+ *   [10 + p] 1.0 when link l is on candidate path p of the pending (src, dst) and p < n_paths[src, dst], else 0.0; the same for
+ *       every core.
+ * Every value is computed in float64 and rounded to float32 once.
+ * orl_batch_link_features_shape: *dim, *rows = R, *width = F and the device pitch IN FLOATS, round_up(dim, 4), of
+ * ORL_BUF_LINK_FEATURES' rows; the pad columns are 0.
+ * orl_batch_link_features: one launch on the batch's stream into ORL_BUF_LINK_FEATURES (no synchronisation, graph-capturable: the
+ * buffer is allocated by the first call, which should therefore come before a capture); with out != NULL ([n_envs][dim] floats)
+ * the rows are then copied out densely and the call synchronises.  The pending service, the slot maps and the link statistics are
+ * read as the last step or reset left them; nothing of the env is written. */
+int orl_batch_link_features_shape(const orl_batch* b, int32_t* dim, int32_t* rows, int32_t* width, int32_t* pitch);
+int orl_batch_link_features(orl_batch* b, float* out /* host [n_envs][dim], or NULL = only queue the launch */);
 
 /* First-fit completion of a partial RMCSA action: the agent fixes a prefix of (path p, modulation m, core c, first slot s) — nothing,
  * the path, the pair or the triple — and the device fills in the rest under prov(p, m, c, s), the predicate of ORL_MASK_PATH_MOD /

@@ -91,6 +91,8 @@ EXPORTS = {
     "orl_batch_complete_actions": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "orl_batch_path_features_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "orl_batch_path_features": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "orl_batch_link_features_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "orl_batch_link_features": (C.c_int, [C.c_void_p, C.c_void_p]),
     "orl_batch_matrix_paths_obs_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "orl_batch_matrix_paths_observation": (C.c_int, [C.c_void_p, C.c_void_p]),
     "orl_batch_debug_serial_count": (C.c_int64, [C.c_void_p]),

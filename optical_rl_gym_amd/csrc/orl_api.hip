@@ -1204,6 +1204,10 @@ extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_pt
       *device_ptr = b->pf_last ? b->pf_buf[b->pf_last] : nullptr;
       *n_elements = b->pf_last ? B * path_obs_pitch(path_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, b->pf_last)) : 0;
       break;
+    case ORL_BUF_LINK_FEATURES:
+      *device_ptr = b->lf_buf;
+      *n_elements = b->lf_buf ? B * path_obs_pitch(link_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, b->P.E)) : 0;
+      break;
     case ORL_BUF_MATRIX_PATHS_OBS:
       *device_ptr = b->qobs_buf;
       *n_elements = b->qobs_buf ? B * qos_obs_pitch(b->P) : 0;
@@ -1373,6 +1377,35 @@ extern "C" int orl_batch_path_features(orl_batch* b, int j, int modulation, floa
   HIPCHK(hipGetLastError());
   b->pf_last = j;
   return out ? view_rows_to_host(b, buf, sizeof(float), dim, pitch, out) : ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+// link features (orl_link_obs.h)
+static int link_features_check(const orl_batch* b) {
+  if (b->P.env_type == ENV_QOS) return fail(ORL_E_INVALID, "link features are not available for QoSConstrainedRA, which has no slot maps (RMSA, DeepRMSA, RWA and RMCSA only)");
+  return ORL_OK;
+}
+
+extern "C" int orl_batch_link_features_shape(const orl_batch* b, int32_t* dim, int32_t* rows, int32_t* width, int32_t* pitch) try {
+  if (!b || !dim || !rows || !width || !pitch) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = link_features_check(b)) return rc;
+  *dim = link_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, b->P.E);
+  *rows = link_obs_rows(b->P.env_type, b->P.C, b->P.E);
+  *width = link_obs_width(b->P.K);
+  *pitch = path_obs_pitch(*dim);
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+extern "C" int orl_batch_link_features(orl_batch* b, float* out) try {
+  if (!b) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = link_features_check(b)) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  const int dim = link_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, b->P.E), pitch = path_obs_pitch(dim);
+  if (int rc = view_buffer(b, b->lf_buf, (size_t)(b->P.B * (int64_t)pitch) * sizeof(float), "link features")) return rc;
+  ORL_LAUNCH(link_features, b, b->lf_buf);
+  HIPCHK(hipGetLastError());
+  return out ? view_rows_to_host(b, b->lf_buf, sizeof(float), dim, pitch, out) : ORL_OK;
 }
 ORL_ABI_CATCH_INT
 

@@ -97,6 +97,8 @@ struct orl_batch {
   float* pf_buf[9] = {};           // path features per block count j (1 .. 8): [B][pitch] floats, allocated by the first
                                    // orl_batch_path_features of that j (a view of one stays that j's)
   int pf_last = 0;                 // j of the last launch: what ORL_BUF_PATH_FEATURES hands out (0: none yet)
+  float* lf_buf = nullptr;         // link features: [B][pitch] floats, allocated by the first orl_batch_link_features; what
+                                   // ORL_BUF_LINK_FEATURES hands out
   unsigned char* qobs_buf = nullptr;  // MatrixObservationWithPaths (QoSConstrainedRA): [B][pitch] bytes, allocated by the first
                                     // orl_batch_matrix_paths_observation; what ORL_BUF_MATRIX_PATHS_OBS hands out
   // orl_batch_copy_envs (as the destination): the pair indices [2][n] on the device and in page-locked memory, grown on demand
@@ -123,6 +125,10 @@ static inline void slot_maps_change(orl_batch* b, hipStream_t st) {
 static inline int path_obs_rows(int env_type, int K, int C) { return env_type == orl::ENV_RMCSA ? K * C : K; }
 static inline int path_obs_dim(int env_type, int N, int K, int C, int j) { return 1 + 2 * N + path_obs_rows(env_type, K, C) * (2 * j + 3); }
 static inline int path_obs_pitch(int dim) { return (dim + 3) / 4 * 4; }
+// link features (orl_link_obs.h, orl_batch_link_features): slot rows per env, values per row, row length; the pitch is path_obs_pitch's
+static inline int link_obs_rows(int env_type, int C, int E) { return (env_type == orl::ENV_RMCSA ? C : 1) * E; }
+static inline int link_obs_width(int K) { return 10 + K; }
+static inline int link_obs_dim(int env_type, int N, int K, int C, int E) { return 1 + 2 * N + link_obs_rows(env_type, C, E) * link_obs_width(K); }
 
 #define ORL_TK(B_, NAME)                                                                 \
   do {                                                                                   \
@@ -147,6 +153,7 @@ template <int W> int rmcsa_mask(orl_batch* b, int layout, unsigned char* out, in
 // k_rmcsa_complete: the first n_given action columns of env e at given[e * gstride ...] (device) completed first-fit into P.actions
 template <int W> void rmcsa_complete(orl_batch* b, int n_given, const int* given, int gstride);
 template <int W> void path_features(orl_batch* b, float* out, int j, int mod);  // k_path_features -> out [B][round_up(dim, 4)] floats
+template <int W> void link_features(orl_batch* b, float* out);             // k_link_features -> out [B][round_up(dim, 4)] floats
 // k_persist in the form `ch` (the run's choice for the whole batch; use_spec: made for the attached specialisation library) over the
 // env range of view VP up to step `target` of this run, then k_rel_tail, on stream st
 template <int W> void persist(orl_batch* b, const orl::DevParams& VP, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,

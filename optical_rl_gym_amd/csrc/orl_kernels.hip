@@ -13,6 +13,7 @@
 //   k_rmcsa_mask RMCSA's path-modulation and core-slot masks (orl_rmcsa_mask.h)         8 lanes per env, lane = (path, core) / core
 //   k_rmcsa_complete first-fit completion of a partial RMCSA action (orl_rmcsa_complete.h)  8 lanes per env, lane = (path, core)
 //   k_path_features path-feature observation of the pending service (orl_path_obs.h)    8 lanes per env, rows striped over them
+//   k_link_features per-link feature observation of the pending service (orl_link_obs.h)  8 lanes per env, slot rows striped over them
 //               [what these three views share — and k_qos_matrix_obs of orl_api.hip with them — lives in orl_view.h]
 // Launchers (orl_launch::*<W>) are explicitly instantiated at the end; orl_api.hip dispatches on the batch's W.
 #include <hip/hip_runtime.h>
@@ -2053,6 +2054,7 @@ __global__ void __launch_bounds__(256) k_obs8(DevParams P, int with_terminal) {
 #include "orl_rmcsa_mask.h"  // k_rmcsa_mask: the two-stage masks of RMCSA (path-modulation, core-slot)
 #include "orl_rmcsa_complete.h"  // k_rmcsa_complete: a partial RMCSA action completed first-fit under the masks' rule
 #include "orl_path_obs.h"  // k_path_features: the path-feature observation of the pending service (every slot-map family)
+#include "orl_link_obs.h"  // k_link_features: the per-link feature observation of the pending service (every slot-map family)
 #endif
 
 // ---- QoSConstrainedRA for an agent in the loop: 8 lanes per env (round 5) --------------------------------------------------------
@@ -2297,6 +2299,23 @@ template <int W> void path_features(orl_batch* b, float* out, int j, int mod) {
   ORL_TK(b, "k_path_features");
 }
 
+// k_link_features (orl_link_obs.h) into `out` ([B][pitch] floats on the device).  The wavefront's rows are staged whole in LDS where
+// 8 of them, beside the 8 envs' link sets, fit 48 KiB; else in rounds of `chunk` slot rows per env, the most (a multiple of 8) that
+// 4, 2 or 1 wavefronts' staging fits.
+template <int W> void link_features(orl_batch* b, float* out) {
+  const DevParams& VP = b->P;
+  const int dim = link_obs_dim(VP.env_type, VP.N, VP.K, VP.C, VP.E), pitch = path_obs_pitch(dim), F = link_obs_width(VP.K);
+  int waves = view_waves(link_obs_wave_lds(VP.K, pitch)), chunk = 0;
+  if (!waves) {
+    waves = view_waves(link_obs_wave_lds(VP.K, 8 * F));  // (k = 64: 8 blocks of 74 floats for 8 envs + their link sets = 27 kB, one wavefront)
+    chunk = (int)((48 * 1024 / waves - link_obs_wave_lds(VP.K, 0)) / (8 * F * sizeof(float))) / 8 * 8;
+  }
+  const size_t lds = waves * link_obs_wave_lds(VP.K, chunk ? chunk * F : pitch);
+  const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
+  hipLaunchKernelGGL((k_link_features<W>), dim3(grid), dim3(64 * waves), lds, b->stream, VP, out, dim, pitch, chunk);
+  ORL_TK(b, "k_link_features");
+}
+
 // The persistent kernel in the form `ch` — what persist_choose (orl_persist_form.h) took for the whole batch when the run began:
 // a run in two halves launches the same kernel on both views — over the env range of view VP0.
 template <int W> void persist(orl_batch* b, const DevParams& VP0, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,
@@ -2451,6 +2470,7 @@ template int action_mask<ORL_W>(orl_batch*, int, unsigned char*, int);
 template int rmcsa_mask<ORL_W>(orl_batch*, int, unsigned char*, int, const int*, int);
 template void rmcsa_complete<ORL_W>(orl_batch*, int, const int*, int);
 template void path_features<ORL_W>(orl_batch*, float*, int, int);
+template void link_features<ORL_W>(orl_batch*, float*);
 template void persist<ORL_W>(orl_batch*, const DevParams&, const PersistChoice&, bool, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);
 template void step2<ORL_W>(orl_batch*, int);
 template void agent_step<ORL_W>(orl_batch*, int, int);

@@ -59,15 +59,12 @@ __device__ __forceinline__ void path_obs_block(const Row<W>& m, int n, int S, in
 template <int W>
 __device__ __forceinline__ void path_obs_env(const DevParams& P, i64 env, int gl, int J, int mod, int dim, int pitch, float* o) {
   const PendingSvc sv = view_pending(P, env);
-  const int src = sv.src, dst = sv.dst, br_idx = sv.br_idx, np = sv.np, pb = sv.pb;
+  const int br_idx = sv.br_idx, np = sv.np, pb = sv.pb;
   const u64* bm = sv.bm;
   const int N = P.N, K = P.K, S = P.S, WD = 2 * J + 3;
   const bool rwa = P.env_type == ENV_RWA, rmcsa = P.env_type == ENV_RMCSA;
   const int C = rmcsa ? P.C : 1, R = K * C;
-  const int mn = src < dst ? src : dst, mx = src < dst ? dst : src;
-  const float rate = rwa ? 0.0f : (float)((double)(int)(u32)sv.br / 100);
-  for (int i = gl; i < 1 + 2 * N; i += 8) o[i] = (i == 0) ? rate : ((i == 1 + mn || i == 1 + N + mx) ? 1.0f : 0.0f);
-  for (int i = dim + gl; i < pitch; i += 8) o[i] = 0.0f;
+  view_obs_header(sv, N, rwa, gl, dim, pitch, o);
   for (int r = gl; r < R; r += 8) {
     const int p = r / C, core = r - p * C;
     float* blk = o + 1 + 2 * N + r * WD;

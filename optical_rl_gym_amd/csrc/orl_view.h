@@ -1,9 +1,10 @@
 // orl_view.h — what the per-step device views of the pending service share (orl_mask.h, orl_rmcsa_mask.h, orl_path_obs.h,
-// orl_qos_obs.h); included by orl_kernels.hip and orl_api.hip, after orl_device.h.
+// orl_link_obs.h, orl_qos_obs.h); included by orl_kernels.hip and orl_api.hip, after orl_device.h.
 //
 //   view_bits16_bytes  a 16-bit field -> 16 bytes of 0/1, one 16-byte store's worth (every byte view)
 //   view_lanes         the opening of an 8-lanes-per-env kernel: 8 envs per wavefront, blockDim / 64 wavefronts per workgroup
 //   view_pending       the pending service of an env, decoded from its scalar record
+//   view_obs_header    the float32 header of the feature rows (orl_path_obs.h, orl_link_obs.h) and their pad columns
 //   view_store_rows    a wavefront's 8 envs' bit rows in LDS -> their output rows of 0/1 bytes, as 16-byte stores
 //   view_waves         wavefronts per workgroup that 48 KiB of LDS allow (host)
 // (orl_device.h has no decode of the scalar record short of the whole Env; k_policy reads the svc_desc word instead.)
@@ -45,6 +46,15 @@ __device__ __forceinline__ PendingSvc view_pending(const DevParams& P, i64 env) 
   s.pb = (s.src * P.N + s.dst) * P.K;
   s.bm = P.bitmap + env * P.bm_words;
   return s;
+}
+
+// The header of a feature row o (LDS or global) of dim columns at a pitch of `pitch`, by the env group's 8 lanes: bit_rate / 100 (RWA:
+// 0), the one-hots of min(src, dst) and max(src, dst) over N nodes each (deeprmsa_env.py:62-68); the pad columns dim .. pitch - 1 = 0
+__device__ __forceinline__ void view_obs_header(const PendingSvc& sv, int N, bool rwa, int gl, int dim, int pitch, float* o) {
+  const int mn = sv.src < sv.dst ? sv.src : sv.dst, mx = sv.src < sv.dst ? sv.dst : sv.src;
+  const float rate = rwa ? 0.0f : (float)((double)(int)(u32)sv.br / 100);
+  for (int i = gl; i < 1 + 2 * N; i += 8) o[i] = (i == 0) ? rate : ((i == 1 + mn || i == 1 + N + mx) ? 1.0f : 0.0f);
+  for (int i = dim + gl; i < pitch; i += 8) o[i] = 0.0f;
 }
 
 // The wavefront's 8 output rows (envs env0 .. env0 + 7, those < B) from its LDS image: env el's words at lds + el * ew hold nrows

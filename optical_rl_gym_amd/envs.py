@@ -842,10 +842,33 @@ class BatchedOpticalEnv:
         self._pf_j = j
         return out
 
+    # ---- link features (include/orl.h, orl_batch_link_features): RMSA, DeepRMSA, RWA and RMCSA --------------------------------
+    def link_features_shape(self):
+        """(dim, rows, width, pitch) of the link-feature rows: dim = 1 + 2 N + rows * width float32 columns per env, rows = links
+        (RMCSA: cores * links, block c * links + l), width = 10 + k, rows of the device buffer pitch FLOATS apart."""
+        d, r, w, p = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self.lib.orl_batch_link_features_shape(self._h, C.byref(d), C.byref(r), C.byref(w), C.byref(p)))
+        return d.value, r.value, w.value, p.value
+
+    def link_features(self, fetch=True, out=None):
+        """The state per link for every env's pending service, computed on the device: float32 [num_envs, dim] — what a graph
+        network over the topology reads.  The header of path_features (bit_rate / 100, RWA: 0; one-hots of min(src, dst) and
+        max(src, dst)), then per slot row, in the order of the slot maps (link l of topology.path_links and link_stats_all();
+        RMCSA: block c * links + l), a block of 10 + k values: free slots / S, free runs / S, longest free run / S, first free slot
+        / S and (last free slot + 1) / S (-1.0 for a row without a free slot), the external fragmentation and the compactness of
+        the row as it stands (the reference's _update_link_stats expressions), the link's running utilization, external
+        fragmentation and compactness (link_stats_all() columns 0 .. 2), and per candidate path p of the pending pair 1.0 where
+        the link is on it.  `out` (a C-contiguous float32 [num_envs, dim] array) receives the rows instead of a fresh array.
+        fetch=False only queues the launch on the batch's stream — read the rows in place with device_array("link_features") /
+        device_tensor("link_features")."""
+        return self._view_rows(lambda p: self._ck(self.lib.orl_batch_link_features(self._h, p)),
+                               lambda: self.link_features_shape()[0], np.float32, fetch, out)
+
     # ---- zero-copy device views (an agent on the same GPU: no PCIe in the loop) -------------------------
     _BUFFERS = {"actions": (0, "<i4", 4), "reward": (1, "<f8", 0), "done": (2, "|u1", 0), "info": (3, "<f8", -1),
                 "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0), "action_mask": (7, "|b1", None),
-                "matrix_paths_obs": (8, "|u1", None), "path_features": (9, "<f4", None)}
+                "matrix_paths_obs": (8, "|u1", None), "path_features": (9, "<f4", None),
+                "link_features": (10, "<f4", None)}
     # The views of the pending service: [num_envs, dim] rows of the last call at the device pitch.  name -> (the message while no
     # call has been made, (dim, pitch in items) of those rows, item size).  Every mask layout and every j of the path features has
     # a buffer of its own: a view taken after a "joint" call keeps showing the joint rows (as the last "joint" call left them)
@@ -855,7 +878,9 @@ class BatchedOpticalEnv:
               "matrix_paths_obs": ("no MatrixObservationWithPaths yet: call matrix_observation_with_paths() (fetch=False only "
                                    "queues it) first", lambda self: self.matrix_paths_obs_shape(), 1),
               "path_features": ("no path features yet: call path_features() (fetch=False only queues it) first",
-                                lambda self: self.path_features_shape(self._pf_j)[::2], 4)}
+                                lambda self: self.path_features_shape(self._pf_j)[::2], 4),
+              "link_features": ("no link features yet: call link_features() (fetch=False only queues it) first",
+                                lambda self: self.link_features_shape()[::3], 4)}
 
     def device_array(self, name):
         """The batch's device-resident I/O array `name` as an object with `__cuda_array_interface__` (what

@@ -334,6 +334,11 @@ class _SingleEnv:
         [1 + 2 N + rows * (2 j + 3)]."""
         return self.batch.path_features(j, modulation)[0]
 
+    def link_features(self):
+        """The env's row of the batch's link features (BatchedOpticalEnv.link_features), computed on the device: float32
+        [1 + 2N + rows * (10 + k)]."""
+        return self.batch.link_features()[0]
+
     def policy_action(self, policy):
         """Action of the on-device heuristic `policy` for the pending service, in the reference's tuple form."""
         a = self.batch.policy(policy)[0]

@@ -364,6 +364,14 @@ class MultiDeviceBatch:
         every shard writes its own rows."""
         return self._view_rows(lambda r, **kw: self.shards[r].path_features(j, modulation, **kw), fetch, out)
 
+    def link_features_shape(self):
+        return self.shards[0].link_features_shape()
+
+    def link_features(self, fetch=True, out=None):
+        """BatchedOpticalEnv.link_features of every shard, rows in env order; with `out` ([num_envs, dim] float32, C-contiguous)
+        every shard writes its own rows."""
+        return self._view_rows(lambda r, **kw: self.shards[r].link_features(**kw), fetch, out)
+
     def matrix_paths_obs_shape(self):
         return self.shards[0].matrix_paths_obs_shape()
 

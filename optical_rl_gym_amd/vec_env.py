@@ -284,7 +284,8 @@ class OpticalVecEnv:
         """observation: "default" (DeepRMSA: its 1-D vector; other families: None, as their Dict observation holds live
         objects), "matrix" (SimpleMatrixObservation built on the device: uint8 [2N + C*E*S]) or "matrix_paths"
         (QoSConstrainedRA only: MatrixObservationWithPaths built on the device, uint8 [E*S*(k+1) + 1]) or "path_features" (RMSA,
-        DeepRMSA, RWA, RMCSA: batch.path_features(j=path_features_j) built on the device, float32 [1 + 2N + rows*(2j+3)]).
+        DeepRMSA, RWA, RMCSA: batch.path_features(j=path_features_j) built on the device, float32 [1 + 2N + rows*(2j+3)]) or
+        "link_features" (the same families: batch.link_features() built on the device, float32 [1 + 2N + C*E*(10+k)]).
         max_logged_episodes / monitor_spill_path: the bound of `episode_log` and where rows beyond it go (EpisodeLog).
         rates_only_info (opt-in; the reference's step() always fills every info entry, rmsa_env.py:228-264): when the info
         keywords are blocking rates only, the step kernel may skip the compactness entries and the two link means — then
@@ -323,6 +324,9 @@ class OpticalVecEnv:
         elif observation == "path_features":
             self.path_features_j = int(path_features_j)
             dim = batch.path_features_shape(self.path_features_j)[0]
+            self.observation_space = _space_module().Box(low=-2.0 ** 30, high=2.0 ** 30, shape=(dim,), dtype=np.float32)
+        elif observation == "link_features":
+            dim = batch.link_features_shape()[0]
             self.observation_space = _space_module().Box(low=-2.0 ** 30, high=2.0 ** 30, shape=(dim,), dtype=np.float32)
         self.info_keywords = tuple(k for k in info_keywords if k in batch.info_keys)
         self._kw_idx = [batch.info_keys.index(k) for k in self.info_keywords]
@@ -393,12 +397,14 @@ class OpticalVecEnv:
                 shape, dtype = (self.num_envs, self.batch.matrix_paths_obs_shape()[0]), np.dtype(np.uint8)
             elif self.observation_mode == "path_features":
                 shape, dtype = (self.num_envs, self.batch.path_features_shape(self.path_features_j)[0]), np.dtype(np.float32)
+            elif self.observation_mode == "link_features":
+                shape, dtype = (self.num_envs, self.batch.link_features_shape()[0]), np.dtype(np.float32)
             self._obs_ring = [make(shape, dtype) if make else np.zeros(shape, dtype) for _ in range(3)]
         self._obs_turn = (self._obs_turn + 1) % 3
         return self._obs_ring[self._obs_turn]
 
     def _direct(self):
-        return bool(self.observation_mode not in ("matrix", "path_features") and getattr(self.batch, "obs_dim", 0)
+        return bool(self.observation_mode not in ("matrix", "path_features", "link_features") and getattr(self.batch, "obs_dim", 0)
                     and self.obs_dtype in (np.dtype(np.float64), np.dtype(np.float32)) and self._direct_obs)
 
     def step_wait(self):
@@ -620,7 +626,7 @@ class OpticalVecEnv:
 
     # ---- zero-copy views for an agent on the same GPU ----
     def device_tensors(self):
-        """{"actions", "reward", "done", "info"[, "obs", "terminal_obs"][, "matrix_paths_obs"][, "path_features"]}: torch views of the batch's device arrays (DLPack /
+        """{"actions", "reward", "done", "info"[, "obs", "terminal_obs"][, "matrix_paths_obs"][, "path_features"][, "link_features"]}: torch views of the batch's device arrays (DLPack /
         __cuda_array_interface__, no copy).  Write actions, `batch.step(None, auto_reset=True, fetch=False)`, `batch.sync()`."""
         names = ["actions", "reward", "done", "info"] + (["obs", "terminal_obs"] if self.batch.obs_dim else [])
         if self.observation_mode == "matrix_paths":  # (queued once so that the device buffer exists; rows as the batch stands)
@@ -629,6 +635,9 @@ class OpticalVecEnv:
         elif self.observation_mode == "path_features":
             self.batch.path_features(self.path_features_j, fetch=False)
             names.append("path_features")
+        elif self.observation_mode == "link_features":
+            self.batch.link_features(fetch=False)
+            names.append("link_features")
         return {n: self.batch.device_tensor(n) for n in names}
 
     def _obs(self, obs):
@@ -638,6 +647,8 @@ class OpticalVecEnv:
             return self.batch.matrix_observation_with_paths(out=self._next_obs_buffer())
         if self.observation_mode == "path_features":
             return self.batch.path_features(self.path_features_j, out=self._next_obs_buffer())
+        if self.observation_mode == "link_features":
+            return self.batch.link_features(out=self._next_obs_buffer())
         if obs is None:
             return None
         return np.array(obs, dtype=self.obs_dtype)

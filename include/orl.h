@@ -503,6 +503,42 @@ int orl_batch_complete_actions(orl_batch* b, int n_given,
                                const int32_t* given /* host [n_envs][n_given], or NULL = columns 0..n_given-1 of ORL_BUF_ACTIONS */,
                                int32_t* actions_out /* host [n_envs][4], or NULL */);
 
+/* Spectrum-assignment rules for RMSA and RWA actions: the agent gives nothing or the path p, and the device picks the first slot
+ * (RWA: the wavelength) s* under a named rule — the single-core sibling of the completion above.  For the pending service of an env
+ * and a path p < n_paths[src, dst]:
+ *   n(p)    the slots the service needs on p: RMSA get_number_slots under the path's best modulation, RWA 1;
+ *   m(p)    the AND over the hops of p of the free-slot rows, slots 0 .. S - 1;
+ *   fits(p) = { s : s + n <= S and m(p)[s .. s + n - 1] all free }
+ * — exactly the set columns p * S + s of the env's ORL_MASK_JOINT row without the fallback.  One deliberate difference from
+ * ORL_POLICY_PATH_FF and the reference wrapper's range(0, S - n) (rmsa_env.py:848-871): s = S - n is tried, as by
+ * orl_batch_complete_actions.  Each rule chooses s* from fits(p): */
+#define ORL_ASSIGN_FIRST_FIT 0  /* min fits(p) */
+#define ORL_ASSIGN_LAST_FIT 1   /* max fits(p) */
+#define ORL_ASSIGN_BEST_FIT 2   /* among the maximal free runs of m(p) of length L >= n the one with the smallest L, ties to the
+                                 * lowest start; s* = its start */
+#define ORL_ASSIGN_EXACT_FIT 3  /* the lowest-start maximal free run with L == n if there is one, else ORL_ASSIGN_FIRST_FIT */
+#define ORL_ASSIGN_MOST_USED 4  /* the s of fits(p) that maximises U(s), ties to the lowest s */
+#define ORL_ASSIGN_LEAST_USED 5 /* the s of fits(p) that minimises U(s), ties to the lowest s */
+/* U(s) = u[s] + .. + u[s + n - 1]; u[w] = the number of links of the env's whole slot map — all of them, not only those on the path
+ * — on which slot w is occupied.  For RWA (n = 1) rules 4 and 5 are the textbook most-used and least-used wavelength rules, for RMSA
+ * their window-sum generalisation.
+ * n_given = 1: the path is given per env; a path that is negative or >= n_paths[src, dst] has no completion.  n_given = 0: the first
+ * path in order with a non-empty fits(p), then the rule on that path (ORL_ASSIGN_FIRST_FIT: k-shortest-path first fit).  "No
+ * completion" is the reject action (k, S), which every heuristic of the reference and ORL_POLICY_PATH_FF return too when nothing
+ * fits.  The kernel writes the env's row of ORL_BUF_ACTIONS as (p, s*, 0, 0), where step(NULL) reads it; it reads only the pending
+ * service and the slot maps as the last step or reset left them: env state, flags and snapshot bytes do not change.
+ * orl_batch_assign_spectrum: one launch on the batch's stream.  given == NULL: the path is column 0 of ORL_BUF_ACTIONS, where an
+ * agent on the GPU writes its choice; with actions_out == NULL as well the call does not synchronise, allocates nothing and is
+ * graph-capturable.  A host `given` [n_envs] int32 goes through a page-locked buffer of the batch into a device buffer of the batch
+ * (both allocated by the first such call, and not those of orl_batch_action_mask_given or orl_batch_complete_actions),
+ * asynchronously on the batch's stream; ORL_BUF_ACTIONS is then written by the kernel only.  With actions_out != NULL the rows are
+ * copied out and the call synchronises.  ORL_E_INVALID, before anything is queued: a family other than RMSA and RWA (a DeepRMSA
+ * action is a block index and cannot express these rules; RMCSA has orl_batch_complete_actions), an unknown rule, n_given outside
+ * 0 .. 1, given != NULL with n_given == 0. */
+int orl_batch_assign_spectrum(orl_batch* b, int rule, int n_given,
+                              const int32_t* given /* host [n_envs] paths, or NULL = column 0 of ORL_BUF_ACTIONS */,
+                              int32_t* actions_out /* host [n_envs][4], or NULL */);
+
 /* Snapshot / restore of the complete simulation state of the batch (slot maps, pending releases, RNG, statistics,
  * counters).  The reference has no equivalent (no checkpointing); used for long PPO runs.  The per-env
  * rates (orl_batch_set_rates) are configuration and not part of it. */

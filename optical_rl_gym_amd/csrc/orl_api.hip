@@ -700,6 +700,8 @@ extern "C" void orl_batch_destroy(orl_batch* b) try {
   if (b->ev_given_up) hipEventDestroy(b->ev_given_up);
   if (b->h_complete_given) hipHostFree(b->h_complete_given);
   if (b->ev_complete_up) hipEventDestroy(b->ev_complete_up);
+  if (b->h_assign_given) hipHostFree(b->h_assign_given);
+  if (b->ev_assign_up) hipEventDestroy(b->ev_assign_up);
   if (b->ev_copy_up) hipEventDestroy(b->ev_copy_up);
   if (b->ev_copy) hipEventDestroy(b->ev_copy);
   if (b->spec_handle) dlclose(b->spec_handle);
@@ -1338,6 +1340,43 @@ extern "C" int orl_batch_complete_actions(orl_batch* b, int n_given, const int32
     stride = n_given;
   }
   ORL_LAUNCH(rmcsa_complete, b, n_given, src, stride);
+  HIPCHK(hipGetLastError());
+  if (actions_out) {
+    HIPCHK(hipMemcpyAsync(actions_out, b->P.actions, (size_t)b->P.B * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+  }
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+// spectrum-assignment rules for RMSA / RWA actions (orl_assign.h)
+extern "C" int orl_batch_assign_spectrum(orl_batch* b, int rule, int n_given, const int32_t* given, int32_t* actions_out) try {
+  if (!b) return fail(ORL_E_INVALID, "null argument");
+  if (b->P.env_type != ENV_RMSA && b->P.env_type != ENV_RWA)
+    return fail(ORL_E_INVALID, "spectrum assignment is defined for RMSA and RWA only (a DeepRMSA action is a block index; RMCSA has orl_batch_complete_actions)");
+  if (rule < ORL_ASSIGN_FIRST_FIT || rule > ORL_ASSIGN_LEAST_USED)
+    return fail(ORL_E_INVALID, "unknown spectrum-assignment rule %d (ORL_ASSIGN_* = 0 .. %d)", rule, ORL_ASSIGN_LEAST_USED);
+  if (n_given < 0 || n_given > 1) return fail(ORL_E_INVALID, "n_given = %d outside 0 .. 1 (nothing, path)", n_given);
+  if (given && n_given == 0) return fail(ORL_E_INVALID, "`given` with n_given == 0: there is no column to read");
+  HIPCHK(hipSetDevice(b->device));
+  const int* src = b->P.actions;  // column 0 of ORL_BUF_ACTIONS: where an agent on the GPU writes its path
+  int stride = 4;
+  if (given) {
+    const size_t bytes = (size_t)b->P.B * sizeof(int32_t);
+    if (!b->assign_given) {
+      if (int rc = view_buffer(b, b->assign_given, bytes, "spectrum assignment")) return rc;
+      HIPCHK(hipHostMalloc((void**)&b->h_assign_given, bytes, hipHostMallocPortable));
+      HIPCHK(hipEventCreateWithFlags(&b->ev_assign_up, hipEventDisableTiming));
+    } else {
+      HIPCHK(hipEventSynchronize(b->ev_assign_up));  // (the last call's upload has left the staging buffer)
+    }
+    memcpy(b->h_assign_given, given, bytes);
+    HIPCHK(hipMemcpyAsync(b->assign_given, b->h_assign_given, bytes, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipEventRecord(b->ev_assign_up, b->stream));
+    src = b->assign_given;
+    stride = 1;
+  }
+  ORL_LAUNCH(assign_spectrum, b, rule, n_given, src, stride);
   HIPCHK(hipGetLastError());
   if (actions_out) {
     HIPCHK(hipMemcpyAsync(actions_out, b->P.actions, (size_t)b->P.B * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));

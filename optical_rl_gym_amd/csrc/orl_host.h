@@ -93,6 +93,9 @@ struct orl_batch {
   int32_t* complete_given = nullptr;    // orl_batch_complete_actions with a host `given`: the prefixes [B][n_given <= 3] on the device and in
   int32_t* h_complete_given = nullptr;  // page-locked memory (both [B][3]), allocated on first use — not the masks' pair: either call may
   hipEvent_t ev_complete_up = nullptr;  // refill its staging buffer without waiting for the other's upload; behind the last upload out of it
+  int32_t* assign_given = nullptr;      // orl_batch_assign_spectrum with a host `given`: the paths [B] on the device and in page-locked
+  int32_t* h_assign_given = nullptr;    // memory, allocated on first use — a pair of its own, as the completion's
+  hipEvent_t ev_assign_up = nullptr;    // behind the last upload out of h_assign_given
   int mask_last = -1;              // layout of the last launch: what ORL_BUF_ACTION_MASK hands out (-1: none yet)
   float* pf_buf[9] = {};           // path features per block count j (1 .. 8): [B][pitch] floats, allocated by the first
                                    // orl_batch_path_features of that j (a view of one stays that j's)
@@ -152,6 +155,8 @@ template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, i
 template <int W> int rmcsa_mask(orl_batch* b, int layout, unsigned char* out, int pitch, const int* given, int gstride);
 // k_rmcsa_complete: the first n_given action columns of env e at given[e * gstride ...] (device) completed first-fit into P.actions
 template <int W> void rmcsa_complete(orl_batch* b, int n_given, const int* given, int gstride);
+// k_assign_spectrum: the path of env e at given[e * gstride] (device; n_given == 0: all paths) and its first slot under `rule` into P.actions
+template <int W> void assign_spectrum(orl_batch* b, int rule, int n_given, const int* given, int gstride);
 template <int W> void path_features(orl_batch* b, float* out, int j, int mod);  // k_path_features -> out [B][round_up(dim, 4)] floats
 template <int W> void link_features(orl_batch* b, float* out);             // k_link_features -> out [B][round_up(dim, 4)] floats
 // k_persist in the form `ch` (the run's choice for the whole batch; use_spec: made for the attached specialisation library) over the

@@ -12,6 +12,7 @@
 //   k_action_mask action masks of the pending service (orl_mask.h)                      8 lanes per env, lane = path
 //   k_rmcsa_mask RMCSA's path-modulation and core-slot masks (orl_rmcsa_mask.h)         8 lanes per env, lane = (path, core) / core
 //   k_rmcsa_complete first-fit completion of a partial RMCSA action (orl_rmcsa_complete.h)  8 lanes per env, lane = (path, core)
+//   k_assign_spectrum spectrum-assignment rules for RMSA / RWA actions (orl_assign.h)  8 lanes per env, lane = path, then word of the row
 //   k_path_features path-feature observation of the pending service (orl_path_obs.h)    8 lanes per env, rows striped over them
 //   k_link_features per-link feature observation of the pending service (orl_link_obs.h)  8 lanes per env, slot rows striped over them
 //               [what these three views share — and k_qos_matrix_obs of orl_api.hip with them — lives in orl_view.h]
@@ -2053,6 +2054,7 @@ __global__ void __launch_bounds__(256) k_obs8(DevParams P, int with_terminal) {
 #include "orl_mask.h"  // k_action_mask: action masks of the pending service (RMSA, DeepRMSA, RWA)
 #include "orl_rmcsa_mask.h"  // k_rmcsa_mask: the two-stage masks of RMCSA (path-modulation, core-slot)
 #include "orl_rmcsa_complete.h"  // k_rmcsa_complete: a partial RMCSA action completed first-fit under the masks' rule
+#include "orl_assign.h"  // k_assign_spectrum: the first slot of an RMSA / RWA action under a named spectrum-assignment rule
 #include "orl_path_obs.h"  // k_path_features: the path-feature observation of the pending service (every slot-map family)
 #include "orl_link_obs.h"  // k_link_features: the per-link feature observation of the pending service (every slot-map family)
 #endif
@@ -2285,6 +2287,20 @@ template <int W> void rmcsa_complete(orl_batch* b, int n_given, const int* given
   ORL_TK(b, "k_rmcsa_complete");
 }
 
+// k_assign_spectrum (orl_assign.h): the path of env e at given[e * gstride] (device int32; n_given == 0: every path in order) and the
+// first slot under `rule` into its row of P.actions.  Rules 4 and 5 run the instantiation with the per-slot occupancy counts and its
+// LDS (4 wavefronts fit 48 KiB for every W: view_waves); the others take none.
+template <int W> void assign_spectrum(orl_batch* b, int rule, int n_given, const int* given, int gstride) {
+  const DevParams& VP = b->P;
+  const bool cnt = rule == ORL_ASSIGN_MOST_USED || rule == ORL_ASSIGN_LEAST_USED;
+  const size_t wave_lds = cnt ? (size_t)8 * assign_env_dwords(W) * sizeof(u32) : 0;
+  const int waves = cnt ? view_waves(wave_lds) : 4;
+  const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
+  if (cnt) hipLaunchKernelGGL((k_assign_spectrum<W, true>), dim3(grid), dim3(64 * waves), waves * wave_lds, b->stream, VP, rule, n_given, given, gstride);
+  else hipLaunchKernelGGL((k_assign_spectrum<W, false>), dim3(grid), dim3(64 * waves), 0, b->stream, VP, rule, n_given, given, gstride);
+  ORL_TK(b, "k_assign_spectrum");
+}
+
 // k_path_features (orl_path_obs.h) into `out` ([B][pitch] floats on the device): j blocks per row, RMCSA under modulation `mod`
 // (-1: each path's best).  The wavefront's rows are staged in LDS where 8 of them fit 48 KiB, else every lane stores its own blocks
 // (-DORL_PATH_OBS_STAGE=0: always — the build the two forms were measured against each other with).
@@ -2469,6 +2485,7 @@ template void obs<ORL_W>(orl_batch*, int);
 template int action_mask<ORL_W>(orl_batch*, int, unsigned char*, int);
 template int rmcsa_mask<ORL_W>(orl_batch*, int, unsigned char*, int, const int*, int);
 template void rmcsa_complete<ORL_W>(orl_batch*, int, const int*, int);
+template void assign_spectrum<ORL_W>(orl_batch*, int, int, const int*, int);
 template void path_features<ORL_W>(orl_batch*, float*, int, int);
 template void link_features<ORL_W>(orl_batch*, float*);
 template void persist<ORL_W>(orl_batch*, const DevParams&, const PersistChoice&, bool, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);

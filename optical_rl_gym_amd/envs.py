@@ -802,6 +802,44 @@ class BatchedOpticalEnv:
         self._ck(self.lib.orl_batch_complete_actions(self._h, n, None if g is None else g.ctypes.data, None if out is None else out.ctypes.data))
         return None if out is None else out.copy()
 
+    # ---- spectrum-assignment rules for RMSA / RWA actions (include/orl.h, orl_batch_assign_spectrum) ---------------------------
+    ASSIGN_RULES = {"first": 0, "last": 1, "best": 2, "exact": 3, "most_used": 4, "least_used": 5}
+
+    @classmethod
+    def assignment_rule(cls, rule):
+        """The ORL_ASSIGN_* id of a rule's name (an int passes through: an unknown id is the library's to refuse)."""
+        if isinstance(rule, str):
+            if rule not in cls.ASSIGN_RULES:
+                raise ValueError("rule must be one of %s, got %r" % (", ".join(map(repr, cls.ASSIGN_RULES)), rule))
+            return cls.ASSIGN_RULES[rule]
+        return int(rule)
+
+    @staticmethod
+    def assignment_paths(paths, n_given, num_envs):
+        """(int32 [num_envs] or None, n_given) from the arguments of assign_spectrum(); ValueError for a bad shape or dtype."""
+        if paths is None:
+            return None, 0 if n_given is None else int(n_given)
+        p = np.asarray(paths)
+        if p.ndim != 1 or p.shape[0] != num_envs or p.dtype.kind not in "iu":
+            raise ValueError("paths must be an int array of shape (%d,), got %s %r" % (num_envs, p.dtype, p.shape))
+        return np.ascontiguousarray(p, np.int32), 1 if n_given is None else int(n_given)
+
+    def assign_spectrum(self, rule="first", paths=None, n_given=None, fetch=True):
+        """RMSA / RWA: choose every env's first slot (RWA: wavelength) on the device under a spectrum-assignment rule — "first",
+        "last", "best", "exact", "most_used" or "least_used" (include/orl.h, ORL_ASSIGN_*) — among the starts at which stepping
+        the action provisions, the set columns of the path's part of the "joint" mask (s = S - n included, which "PATH_FF" never
+        tries): int32 [num_envs, 4] rows (path, slot, 0, 0), left in device_array("actions") for the next step(None).  `paths`: a
+        1-D int array, the path per env; paths=None with n_given=1 reads column 0 of device_array("actions"), where an agent on
+        the GPU writes it; paths=None with n_given=0 (the default) takes the first path in order on which the service fits, then
+        the rule on that path.  No completion (a path out of range, no room) is the reject action (k, S).  Env state and flags are
+        not touched.  fetch=False only queues the launch on the batch's stream (returns None; graph-capturable with paths=None)."""
+        p, n = self.assignment_paths(paths, n_given, self.num_envs)
+        out = self._act if fetch else None
+        self._keep_given = p  # (alive until the call returns: the library copies it before it does)
+        self._ck(self.lib.orl_batch_assign_spectrum(self._h, self.assignment_rule(rule), n, None if p is None else p.ctypes.data,
+                                                    None if out is None else out.ctypes.data))
+        return None if out is None else out.copy()
+
     # ---- MatrixObservationWithPaths (include/orl.h, orl_batch_matrix_paths_observation): QoSConstrainedRA only ---------------
     def matrix_paths_obs_shape(self):
         """(dim, pitch): dim = links * S * (k + 1) + 1 columns per env, rows pitch bytes apart in the device buffer."""

@@ -348,7 +348,18 @@ class _SingleEnv:
         return (int(a[0]), int(a[1]))
 
 
-class RMSAEnv(_SingleEnv):
+class _SpectrumRules:
+    """RMSAEnv and RWAEnv: the device's spectrum-assignment rules for the pending service."""
+
+    def assign_spectrum(self, rule="first", path=None):
+        """The action (path, first slot / wavelength) under the spectrum-assignment rule `rule` — "first", "last", "best", "exact",
+        "most_used" or "least_used" (BatchedOpticalEnv.assign_spectrum) — on `path`, or with path=None on the first path on which
+        the service fits; the reject action (k, S) when there is none."""
+        paths = None if path is None else np.array([int(path)], np.int32)
+        return self._decode(self.batch.assign_spectrum(rule, paths=paths, n_given=0 if path is None else 1)[0])
+
+
+class RMSAEnv(_SpectrumRules, _SingleEnv):
     BATCH_CLS = BatchedRMSAEnv
 
 
@@ -380,7 +391,7 @@ class DeepRMSAEnv(_SingleEnv):
         return action // self.j, action % self.j
 
 
-class RWAEnv(_SingleEnv):
+class RWAEnv(_SpectrumRules, _SingleEnv):
     BATCH_CLS = BatchedRWAEnv
     DEFAULT_SLOTS = 80
     DEFAULT_REJECTION = True

@@ -356,6 +356,14 @@ class MultiDeviceBatch:
         out = self._map(lambda r: self.shards[r].complete_actions(given=self._cut(g, r), n_given=n, fetch=fetch))
         return self._cat(out) if fetch else None
 
+    def assign_spectrum(self, rule="first", paths=None, n_given=None, fetch=True):
+        """BatchedOpticalEnv.assign_spectrum of every shard; `paths` ([num_envs]) is cut by the shards' bounds."""
+        from .envs import BatchedOpticalEnv
+
+        p, n = BatchedOpticalEnv.assignment_paths(paths, n_given, self.num_envs)
+        out = self._map(lambda r: self.shards[r].assign_spectrum(rule, paths=self._cut(p, r), n_given=n, fetch=fetch))
+        return self._cat(out) if fetch else None
+
     def path_features_shape(self, j=1):
         return self.shards[0].path_features_shape(j)
 

@@ -280,7 +280,7 @@ class OpticalVecEnv:
 
     def __init__(self, batch, info_keywords=("episode_service_blocking_rate", "episode_bit_rate_blocking_rate"),
                  obs_dtype=np.float64, observation="default", max_logged_episodes=1 << 20, monitor_spill_path=None,
-                 rates_only_info=False, path_features_j=1, action_completion=None):
+                 rates_only_info=False, path_features_j=1, action_completion=None, spectrum_assignment=None):
         """observation: "default" (DeepRMSA: its 1-D vector; other families: None, as their Dict observation holds live
         objects), "matrix" (SimpleMatrixObservation built on the device: uint8 [2N + C*E*S]) or "matrix_paths"
         (QoSConstrainedRA only: MatrixObservationWithPaths built on the device, uint8 [E*S*(k+1) + 1]) or "path_features" (RMSA,
@@ -295,6 +295,11 @@ class OpticalVecEnv:
         "path_modulation": a one-head agent chooses the path (Discrete(k + 1)) or the pair (Discrete(k * M + 1), action p * M + m),
         the last action being reject, and the device completes the action first-fit (batch.complete_actions) before it steps it;
         `action_masks()` is then the batch's "path_modulation" row, for "path" reduced with any() over each path's M columns.
+        spectrum_assignment (RMSA and RWA only): None — the family's MultiDiscrete (path, slot) space — or a rule of
+        batch.assign_spectrum ("first", "last", "best", "exact", "most_used", "least_used"): a one-head agent chooses the path
+        (Discrete(k + 1), the last action being reject) and the device picks the slot under the rule before it steps the action;
+        `action_masks()` is then the batch's "joint" row reduced with any() over each path's S columns (not the "path" row, which
+        leaves out s = S - n), plus the reject column.
         Out of scope: `batch.copy_envs` under a VecEnv.  The host-side episode accumulators kept here (returns, lengths, the
         episode log) do not follow a copy of env states on the device."""
         self.batch = batch
@@ -311,6 +316,16 @@ class OpticalVecEnv:
             self._n_mod = len(batch.modulation_formats)
             cols = batch.k_paths * (self._n_mod if action_completion == "path_modulation" else 1)
             self.action_space = _space_module().Discrete(cols + 1)
+        self.spectrum_assignment = spectrum_assignment
+        if spectrum_assignment is not None:
+            if action_completion is not None:
+                raise ValueError("spectrum_assignment and action_completion exclude each other")
+            if getattr(batch, "ENV_TYPE", None) not in (0, 2) or not hasattr(batch, "assign_spectrum"):
+                raise ValueError("spectrum_assignment is defined for RMSA and RWA batches only (RMCSA has action_completion)")
+            from .envs import BatchedOpticalEnv
+
+            BatchedOpticalEnv.assignment_rule(spectrum_assignment)  # (ValueError for an unknown name)
+            self.action_space = _space_module().Discrete(batch.k_paths + 1)
         if observation == "matrix":
             t = batch.topology
             dim = 2 * t.n_nodes + batch.num_spatial_resources * t.n_links * batch.num_spectrum_resources
@@ -368,6 +383,10 @@ class OpticalVecEnv:
         self._queued = False
         if self.action_completion is not None:  # the prefix completed on the device; the step then takes the device-resident actions
             self.batch.complete_actions(given=self._completion_prefix(self._actions), fetch=False)
+            self._actions = None
+        elif self.spectrum_assignment is not None:  # the slot chosen on the device; reject becomes path k, which has no completion
+            a = np.asarray(actions).reshape(self.num_envs).astype(np.int64)
+            self.batch.assign_spectrum(self.spectrum_assignment, paths=np.minimum(a, self.batch.k_paths).astype(np.int32), fetch=False)
             self._actions = None
         if self._async:
             direct = self._direct()
@@ -577,6 +596,10 @@ class OpticalVecEnv:
                 return pm
             body = pm[:, :-1].reshape(self.num_envs, self.batch.k_paths, self._n_mod).any(axis=2)
             return np.concatenate([body, pm[:, -1:]], axis=1)
+        if self.spectrum_assignment is not None:
+            jm = self.batch.action_mask("joint")
+            body = jm[:, :-1].reshape(self.num_envs, self.batch.k_paths, self.batch.num_spectrum_resources).any(axis=2)
+            return np.concatenate([body, jm[:, -1:]], axis=1)
         return sb3_action_masks(self.batch, self.batch.action_mask("joint"), self.action_space)
 
     def _env_action_masks(self, i):

@@ -629,6 +629,15 @@ int orl_debug_persist_choice(const orl_env_config* cfg, const orl_topology_desc*
  * or 0 for an invalid configuration. */
 int orl_debug_run_plan(const orl_env_config* cfg, const orl_topology_desc* topo, int64_t n_envs, int64_t n_steps, int tuned, int n_cu,
                        int log_cap_have, int64_t run_base, int wg_dirty, int32_t* out);
+/* The shape of a per-step view's rows and the geometry of its launch (csrc/orl_view_plan.h) without a device or a configuration
+ * (tests/test_view_plan.py), from raw sizes: the env family, the row width W in 64-bit words (1, 2, 5 or 8), the batch B and the
+ * sizes N, E, K, C, S, J, M of a batch, all >= 1.  view: 0 action mask, 1 RMCSA mask, 2 action completion, 3 spectrum assignment,
+ * 4 path features, 5 link features, 6 MatrixObservationWithPaths; arg: the mask layout (ORL_MASK_*), the rule (ORL_ASSIGN_*), the
+ * path features' j.  out[0..4] = row length (0: the family has no such layout), blocks per row, values per block, device pitch in
+ * elements, bytes per element; out[5..12] = accepted (0: the call refuses the shape, the rest 0), wavefronts and threads per
+ * workgroup, grid, dynamic LDS bytes, path features staged in LDS, link features' slot rows per round (0: whole rows), assignment
+ * with occupancy counts.  Returns 13, or 0 for arguments outside every batch. */
+int orl_debug_view_plan(int env_type, int W, int64_t B, int N, int E, int K, int C, int S, int J, int M, int view, int arg, int32_t* out);
 /* Which kernel orl_batch_step launches for this batch: 2 = k_agent (8 lanes per env, the persistent kernel's phases for one
  * step; QoSConstrainedRA: k_agent_qos, from 20 480 envs), 0 = k_step (one wavefront per env). */
 int orl_batch_debug_step_kernel(orl_batch* b);

@@ -102,6 +102,7 @@ EXPORTS = {
     "orl_debug_persist_choice": (C.c_int, [C.POINTER(EnvConfig), C.POINTER(TopologyDesc), C.c_int64, C.c_int, C.POINTER(C.c_int32)]),
     "orl_debug_run_plan": (C.c_int, [C.POINTER(EnvConfig), C.POINTER(TopologyDesc), C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int,
                                      C.POINTER(C.c_int32)]),
+    "orl_debug_view_plan": (C.c_int, [C.c_int, C.c_int, C.c_int64] + [C.c_int] * 9 + [C.POINTER(C.c_int32)]),
     "orl_batch_debug_step_kernel": (C.c_int, [C.c_void_p]),
     "orl_build_has_alt": (C.c_int, []),
     "orl_batch_debug_prof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

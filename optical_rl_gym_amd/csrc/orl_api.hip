@@ -132,6 +132,12 @@ __global__ void k_matrix_obs(DevParams P, unsigned char* out) {
 
 #include "orl_view.h"     // what the views of the pending service share (the kernels of orl_kernels.hip; here: 16 bits -> 16 bytes)
 #include "orl_qos_obs.h"  // k_qos_matrix_obs: MatrixObservationWithPaths of QoSConstrainedRA (qos_constrained_ra.py:440-493)
+// (the kernels of these four are the per-W units': here the LDS sizes of their envs alone, for view_plan)
+#include "orl_mask.h"
+#include "orl_rmcsa_mask.h"
+#include "orl_assign.h"
+#include "orl_link_obs.h"
+#include "orl_view_plan.h"  // view_shape, view_plan: the shape of each view's rows and the geometry of its launch
 
 #include "orl_copy.h"  // k_copy_envs: the rows of env src[p] of one batch into env dst[p] of another (orl_batch_copy_envs)
 
@@ -696,12 +702,10 @@ extern "C" void orl_batch_destroy(orl_batch* b) try {
   if (b->h_tail) hipHostFree(b->h_tail);
   if (b->h_actions) hipHostFree(b->h_actions);
   if (b->h_copy_idx) hipHostFree(b->h_copy_idx);
-  if (b->h_mask_given) hipHostFree(b->h_mask_given);
-  if (b->ev_given_up) hipEventDestroy(b->ev_given_up);
-  if (b->h_complete_given) hipHostFree(b->h_complete_given);
-  if (b->ev_complete_up) hipEventDestroy(b->ev_complete_up);
-  if (b->h_assign_given) hipHostFree(b->h_assign_given);
-  if (b->ev_assign_up) hipEventDestroy(b->ev_assign_up);
+  for (GivenStage& g : b->given) {  // (g.dev is one of b->allocs)
+    if (g.host) hipHostFree(g.host);
+    if (g.up) hipEventDestroy(g.up);
+  }
   if (b->ev_copy_up) hipEventDestroy(b->ev_copy_up);
   if (b->ev_copy) hipEventDestroy(b->ev_copy);
   if (b->spec_handle) dlclose(b->spec_handle);
@@ -941,16 +945,21 @@ extern "C" int orl_batch_set_paths(orl_batch* b, const int32_t* paths) try {
 }
 ORL_ABI_CATCH_INT
 
+// the rows of ORL_BUF_ACTIONS, [B][4], into the host's `out`, and waits; out == nullptr: nothing queued, no wait
+static int actions_to_host(orl_batch* b, int32_t* out) {
+  if (!out) return ORL_OK;
+  HIPCHK(hipMemcpyAsync(out, b->P.actions, (size_t)b->P.B * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+  HIPCHK(hipStreamSynchronize(b->stream));
+  return ORL_OK;
+}
+
 extern "C" int orl_batch_policy(orl_batch* b, int policy_id, int32_t* actions_out) try {
   if (!b) return fail(ORL_E_INVALID, "null batch");
   if (!policy_ok(b, policy_id)) return fail(ORL_E_INVALID, "policy %d is not defined for this env family", policy_id);
   HIPCHK(hipSetDevice(b->device));
   ORL_LAUNCH(policy, b, policy_id);
-  if (actions_out) {
-    HIPCHK(hipMemcpyAsync(actions_out, b->P.actions, (size_t)b->P.B * 4 * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    HIPCHK(hipGetLastError());
-  }
+  if (int rc = actions_to_host(b, actions_out)) return rc;
+  if (actions_out) HIPCHK(hipGetLastError());
   return ORL_OK;
 }
 ORL_ABI_CATCH_INT
@@ -1147,10 +1156,7 @@ extern "C" int orl_host_free(void* p) try {
 }
 ORL_ABI_CATCH_INT
 
-// ---- the views of the pending service (action masks, path features, MatrixObservationWithPaths): what their entry points share ----
-// device pitch of a view's row of `dim` bytes: rows are written as 16-byte stores
-static int64_t byte_row_pitch(int64_t dim) { return (dim + 15) / 16 * 16; }
-
+// ---- the views of the pending service: what their entry points share.  Row shapes and launch geometry: orl_view_plan.h ----
 // A view's device buffer, allocated by the first call that needs it (which therefore comes before a graph capture).  A failed
 // allocation leaves the batch as it was: the slot null, nothing recorded, no error left for a later call to find.
 template <typename T> static int view_buffer(orl_batch* b, T*& slot, size_t bytes, const char* what) {
@@ -1166,24 +1172,30 @@ template <typename T> static int view_buffer(orl_batch* b, T*& slot, size_t byte
   return ORL_OK;
 }
 
-// a view's rows — [B][dim] elements of `elem` bytes at a device pitch of `pitch` elements — densely into the host's `out`; waits
-static int view_rows_to_host(orl_batch* b, const void* buf, size_t elem, int64_t dim, int64_t pitch, void* out) {
-  HIPCHK(hipMemcpy2DAsync(out, (size_t)dim * elem, buf, (size_t)pitch * elem, (size_t)dim * elem, (size_t)b->P.B, hipMemcpyDeviceToHost, b->stream));
+// a view's rows of shape `sh` densely into the host's `out` (nullptr: nothing queued, no wait); waits
+static int view_rows_to_host(orl_batch* b, const void* buf, const ViewShape& sh, void* out) {
+  if (!out) return ORL_OK;
+  const size_t row = (size_t)sh.dim * sh.elem_bytes;
+  HIPCHK(hipMemcpy2DAsync(out, row, buf, (size_t)sh.pitch * sh.elem_bytes, row, (size_t)b->P.B, hipMemcpyDeviceToHost, b->stream));
   HIPCHK(hipStreamSynchronize(b->stream));
   return ORL_OK;
 }
 
-// MatrixObservationWithPaths (orl_qos_obs.h): row length and device pitch, in 64 bits
-static int64_t qos_obs_dim(const DevParams& P) { return (int64_t)P.E * P.S * (P.K + 1) + 1; }
-static int64_t qos_obs_pitch(const DevParams& P) { return byte_row_pitch(qos_obs_dim(P)); }
-
-// action masks (orl_mask.h, orl_rmcsa_mask.h): row length of `layout` for this batch's family, 0 = not supported
-static int mask_dim(const DevParams& P, int layout) {
-  if (P.env_type == ENV_RMCSA) return layout == ORL_MASK_PATH_MOD ? P.K * P.M + 1 : (layout == ORL_MASK_CORE_SLOT ? P.C * P.S + 1 : 0);
-  if (P.env_type != ENV_RMSA && P.env_type != ENV_DEEPRMSA && P.env_type != ENV_RWA) return 0;
-  if (layout == ORL_MASK_JOINT) return P.K * (P.env_type == ENV_DEEPRMSA ? P.J : P.S) + 1;
-  if (layout == ORL_MASK_PATH && P.env_type != ENV_DEEPRMSA) return P.K + 1;
-  return 0;
+// A host `given` of `cols` columns per env through the stage's page-locked buffer into its device buffer (both [B][cap_cols],
+// allocated by the first call), queued on the batch's stream; the actions buffer is not touched
+static int stage_given(orl_batch* b, GivenStage& g, const int32_t* given, int cap_cols, int cols, const char* what) {
+  const size_t cap = (size_t)b->P.B * cap_cols * sizeof(int32_t), bytes = (size_t)b->P.B * cols * sizeof(int32_t);
+  if (!g.up) {
+    if (int rc = view_buffer(b, g.dev, cap, what)) return rc;
+    if (!g.host) HIPCHK(hipHostMalloc((void**)&g.host, cap, hipHostMallocPortable));
+    HIPCHK(hipEventCreateWithFlags(&g.up, hipEventDisableTiming));
+  } else {
+    HIPCHK(hipEventSynchronize(g.up));  // (the last call's upload has left the staging buffer)
+  }
+  memcpy(g.host, given, bytes);
+  HIPCHK(hipMemcpyAsync(g.dev, g.host, bytes, hipMemcpyHostToDevice, b->stream));
+  HIPCHK(hipEventRecord(g.up, b->stream));
+  return ORL_OK;
 }
 
 extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_ptr, int64_t* n_elements) try {
@@ -1198,21 +1210,20 @@ extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_pt
     case ORL_BUF_TERM_OBS: *device_ptr = b->P.term_obs; *n_elements = B * b->P.obs_dim; break;
     case ORL_BUF_PATHS: *device_ptr = b->P.path_col; *n_elements = B; break;
     case ORL_BUF_ACTION_MASK:
-      if (b->mask_last < 0) { *device_ptr = nullptr; *n_elements = 0; break; }
-      *device_ptr = b->mask_buf[b->mask_last];
-      *n_elements = B * byte_row_pitch(mask_dim(b->P, b->mask_last));
+      *device_ptr = b->mask_last < 0 ? nullptr : b->mask_buf[b->mask_last];
+      *n_elements = b->mask_last < 0 ? 0 : B * view_shape(b->P, VIEW_ACTION_MASK, b->mask_last).pitch;
       break;
     case ORL_BUF_PATH_FEATURES:
       *device_ptr = b->pf_last ? b->pf_buf[b->pf_last] : nullptr;
-      *n_elements = b->pf_last ? B * path_obs_pitch(path_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, b->pf_last)) : 0;
+      *n_elements = b->pf_last ? B * view_shape(b->P, VIEW_PATH_FEATURES, b->pf_last).pitch : 0;
       break;
     case ORL_BUF_LINK_FEATURES:
       *device_ptr = b->lf_buf;
-      *n_elements = b->lf_buf ? B * path_obs_pitch(link_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, b->P.E)) : 0;
+      *n_elements = b->lf_buf ? B * view_shape(b->P, VIEW_LINK_FEATURES, 0).pitch : 0;
       break;
     case ORL_BUF_MATRIX_PATHS_OBS:
       *device_ptr = b->qobs_buf;
-      *n_elements = b->qobs_buf ? B * qos_obs_pitch(b->P) : 0;
+      *n_elements = b->qobs_buf ? B * view_shape(b->P, VIEW_MATRIX_PATHS_OBS, 0).pitch : 0;
       break;
     default: return fail(ORL_E_INVALID, "unknown buffer %d", which);
   }
@@ -1251,64 +1262,51 @@ static int mask_check(const orl_batch* b, int layout) {
   if (t == ENV_RMCSA && !two_stage)
     return fail(ORL_E_INVALID, "the joint and path action masks are not available for RMCSA: use ORL_MASK_PATH_MOD and ORL_MASK_CORE_SLOT");
   if (t != ENV_RMCSA && two_stage) return fail(ORL_E_INVALID, "ORL_MASK_PATH_MOD and ORL_MASK_CORE_SLOT are defined for RMCSA only");
-  if (!mask_dim(b->P, layout)) return fail(ORL_E_INVALID, "DeepRMSA has no path-only action space: use ORL_MASK_JOINT");
+  if (!view_shape(b->P, VIEW_ACTION_MASK, layout).dim) return fail(ORL_E_INVALID, "DeepRMSA has no path-only action space: use ORL_MASK_JOINT");
   return ORL_OK;  // (DeepRMSA: a path's blocks are bits of one u64, and batch_create_impl admits j <= 8)
 }
 
 extern "C" int orl_batch_action_mask_shape(const orl_batch* b, int layout, int32_t* dim, int32_t* pitch) try {
   if (!b || !dim || !pitch) return fail(ORL_E_INVALID, "null argument");
   if (int rc = mask_check(b, layout)) return rc;
-  *dim = mask_dim(b->P, layout);
-  *pitch = (int32_t)byte_row_pitch(*dim);
+  const ViewShape sh = view_shape(b->P, VIEW_ACTION_MASK, layout);
+  *dim = (int32_t)sh.dim;
+  *pitch = (int32_t)sh.pitch;
   return ORL_OK;
 }
 ORL_ABI_CATCH_INT
-
-// ORL_MASK_CORE_SLOT: the caller's (path, modulation) pairs through the batch's page-locked buffer into its device buffer [B][2],
-// queued on the batch's stream; the actions buffer is not touched
-static int upload_mask_given(orl_batch* b, const int32_t* given) {
-  const size_t bytes = (size_t)b->P.B * 2 * sizeof(int32_t);
-  if (!b->mask_given) {
-    HIPCHK(hipMalloc((void**)&b->mask_given, bytes));
-    b->allocs.push_back(b->mask_given);
-    HIPCHK(hipHostMalloc((void**)&b->h_mask_given, bytes, hipHostMallocPortable));
-    HIPCHK(hipEventCreateWithFlags(&b->ev_given_up, hipEventDisableTiming));
-  } else {
-    HIPCHK(hipEventSynchronize(b->ev_given_up));  // (the last call's upload has left the staging buffer)
-  }
-  memcpy(b->h_mask_given, given, bytes);
-  HIPCHK(hipMemcpyAsync(b->mask_given, b->h_mask_given, bytes, hipMemcpyHostToDevice, b->stream));
-  HIPCHK(hipEventRecord(b->ev_given_up, b->stream));
-  return ORL_OK;
-}
 
 extern "C" int orl_batch_action_mask_given(orl_batch* b, int layout, const int32_t* given, uint8_t* out) try {
   if (!b) return fail(ORL_E_INVALID, "null argument");
   if (int rc = mask_check(b, layout)) return rc;
   if (given && layout != ORL_MASK_CORE_SLOT) return fail(ORL_E_INVALID, "`given` belongs to ORL_MASK_CORE_SLOT only");
   HIPCHK(hipSetDevice(b->device));
-  const int dim = mask_dim(b->P, layout), pitch = (int)byte_row_pitch(dim);
   const bool rmcsa = b->P.env_type == ENV_RMCSA;
-  if (rmcsa && ORL_LAUNCH(rmcsa_mask, b, layout, nullptr, pitch, nullptr, 0))  // (out == nullptr: the check alone, before anything is allocated or queued)
-    return fail(ORL_E_INVALID, "RMCSA action masks of k = %d paths, %d modulations, %d cores x %d slots exceed the kernel's LDS budget", b->P.K,
-                b->P.M, b->P.C, b->P.S);
+  const ViewShape sh = view_shape(b->P, VIEW_ACTION_MASK, layout);
+  if (!view_plan(b->P, b->wt, rmcsa ? VIEW_RMCSA_MASK : VIEW_ACTION_MASK, layout).ok) {  // (before anything is allocated or queued)
+    if (rmcsa)
+      return fail(ORL_E_INVALID, "RMCSA action masks of k = %d paths, %d modulations, %d cores x %d slots exceed the kernel's LDS budget", b->P.K,
+                  b->P.M, b->P.C, b->P.S);
+    return fail(ORL_E_INVALID, "action masks of k = %d paths x %d columns exceed the kernel's LDS budget", b->P.K, (int)sh.dim - 1);
+  }
   unsigned char*& buf = b->mask_buf[layout];  // one buffer per layout: a device view of one layout's rows never sees the other's
-  if (int rc = view_buffer(b, buf, (size_t)(b->P.B * (int64_t)pitch), "action mask")) return rc;
+  if (int rc = view_buffer(b, buf, (size_t)(b->P.B * sh.pitch), "action mask")) return rc;
   if (rmcsa) {
     const int* src = b->P.actions;  // columns 0 and 1 of ORL_BUF_ACTIONS: where an agent on the GPU writes its stage-1 choice
     int stride = 4;
     if (given) {
-      if (int rc = upload_mask_given(b, given)) return rc;
-      src = b->mask_given;
+      GivenStage& g = b->given[orl_batch::GIVEN_MASK];
+      if (int rc = stage_given(b, g, given, 2, 2, "action mask")) return rc;
+      src = g.dev;
       stride = 2;
     }
-    ORL_LAUNCH(rmcsa_mask, b, layout, buf, pitch, src, stride);
-  } else if (ORL_LAUNCH(action_mask, b, layout, buf, pitch)) {
-    return fail(ORL_E_INVALID, "action masks of k = %d paths x %d columns exceed the kernel's LDS budget", b->P.K, dim - 1);
+    ORL_LAUNCH(rmcsa_mask, b, layout, buf, src, stride);
+  } else {
+    ORL_LAUNCH(action_mask, b, layout, buf);
   }
   HIPCHK(hipGetLastError());
   b->mask_last = layout;
-  return out ? view_rows_to_host(b, buf, 1, dim, pitch, out) : ORL_OK;
+  return view_rows_to_host(b, buf, sh, out);
 }
 ORL_ABI_CATCH_INT
 
@@ -1325,27 +1323,14 @@ extern "C" int orl_batch_complete_actions(orl_batch* b, int n_given, const int32
   const int* src = b->P.actions;  // columns 0 .. n_given - 1 of ORL_BUF_ACTIONS: where an agent on the GPU writes its choice
   int stride = 4;
   if (given) {
-    const size_t cap = (size_t)b->P.B * 3 * sizeof(int32_t), bytes = (size_t)b->P.B * n_given * sizeof(int32_t);
-    if (!b->complete_given) {
-      if (int rc = view_buffer(b, b->complete_given, cap, "action completion")) return rc;
-      HIPCHK(hipHostMalloc((void**)&b->h_complete_given, cap, hipHostMallocPortable));
-      HIPCHK(hipEventCreateWithFlags(&b->ev_complete_up, hipEventDisableTiming));
-    } else {
-      HIPCHK(hipEventSynchronize(b->ev_complete_up));  // (the last call's upload has left the staging buffer)
-    }
-    memcpy(b->h_complete_given, given, bytes);
-    HIPCHK(hipMemcpyAsync(b->complete_given, b->h_complete_given, bytes, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipEventRecord(b->ev_complete_up, b->stream));
-    src = b->complete_given;
+    GivenStage& g = b->given[orl_batch::GIVEN_COMPLETE];
+    if (int rc = stage_given(b, g, given, 3, n_given, "action completion")) return rc;
+    src = g.dev;
     stride = n_given;
   }
   ORL_LAUNCH(rmcsa_complete, b, n_given, src, stride);
   HIPCHK(hipGetLastError());
-  if (actions_out) {
-    HIPCHK(hipMemcpyAsync(actions_out, b->P.actions, (size_t)b->P.B * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-  }
-  return ORL_OK;
+  return actions_to_host(b, actions_out);
 }
 ORL_ABI_CATCH_INT
 
@@ -1362,27 +1347,14 @@ extern "C" int orl_batch_assign_spectrum(orl_batch* b, int rule, int n_given, co
   const int* src = b->P.actions;  // column 0 of ORL_BUF_ACTIONS: where an agent on the GPU writes its path
   int stride = 4;
   if (given) {
-    const size_t bytes = (size_t)b->P.B * sizeof(int32_t);
-    if (!b->assign_given) {
-      if (int rc = view_buffer(b, b->assign_given, bytes, "spectrum assignment")) return rc;
-      HIPCHK(hipHostMalloc((void**)&b->h_assign_given, bytes, hipHostMallocPortable));
-      HIPCHK(hipEventCreateWithFlags(&b->ev_assign_up, hipEventDisableTiming));
-    } else {
-      HIPCHK(hipEventSynchronize(b->ev_assign_up));  // (the last call's upload has left the staging buffer)
-    }
-    memcpy(b->h_assign_given, given, bytes);
-    HIPCHK(hipMemcpyAsync(b->assign_given, b->h_assign_given, bytes, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipEventRecord(b->ev_assign_up, b->stream));
-    src = b->assign_given;
+    GivenStage& g = b->given[orl_batch::GIVEN_ASSIGN];
+    if (int rc = stage_given(b, g, given, 1, 1, "spectrum assignment")) return rc;
+    src = g.dev;
     stride = 1;
   }
   ORL_LAUNCH(assign_spectrum, b, rule, n_given, src, stride);
   HIPCHK(hipGetLastError());
-  if (actions_out) {
-    HIPCHK(hipMemcpyAsync(actions_out, b->P.actions, (size_t)b->P.B * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-  }
-  return ORL_OK;
+  return actions_to_host(b, actions_out);
 }
 ORL_ABI_CATCH_INT
 
@@ -1398,9 +1370,10 @@ static int path_features_check(const orl_batch* b, int j, int modulation) {
 extern "C" int orl_batch_path_features_shape(const orl_batch* b, int j, int32_t* dim, int32_t* rows, int32_t* pitch) try {
   if (!b || !dim || !rows || !pitch) return fail(ORL_E_INVALID, "null argument");
   if (int rc = path_features_check(b, j, -1)) return rc;
-  *dim = path_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, j);
-  *rows = path_obs_rows(b->P.env_type, b->P.K, b->P.C);
-  *pitch = path_obs_pitch(*dim);
+  const ViewShape sh = view_shape(b->P, VIEW_PATH_FEATURES, j);
+  *dim = (int32_t)sh.dim;
+  *rows = sh.rows;
+  *pitch = (int32_t)sh.pitch;
   return ORL_OK;
 }
 ORL_ABI_CATCH_INT
@@ -1409,13 +1382,13 @@ extern "C" int orl_batch_path_features(orl_batch* b, int j, int modulation, floa
   if (!b) return fail(ORL_E_INVALID, "null argument");
   if (int rc = path_features_check(b, j, modulation)) return rc;
   HIPCHK(hipSetDevice(b->device));
-  const int dim = path_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, j), pitch = path_obs_pitch(dim);
+  const ViewShape sh = view_shape(b->P, VIEW_PATH_FEATURES, j);
   float*& buf = b->pf_buf[j];  // one buffer per j: a device view of one j's rows never sees another's
-  if (int rc = view_buffer(b, buf, (size_t)(b->P.B * (int64_t)pitch) * sizeof(float), "path features")) return rc;
+  if (int rc = view_buffer(b, buf, (size_t)(b->P.B * sh.pitch) * sizeof(float), "path features")) return rc;
   ORL_LAUNCH(path_features, b, buf, j, modulation);
   HIPCHK(hipGetLastError());
   b->pf_last = j;
-  return out ? view_rows_to_host(b, buf, sizeof(float), dim, pitch, out) : ORL_OK;
+  return view_rows_to_host(b, buf, sh, out);
 }
 ORL_ABI_CATCH_INT
 
@@ -1428,10 +1401,11 @@ static int link_features_check(const orl_batch* b) {
 extern "C" int orl_batch_link_features_shape(const orl_batch* b, int32_t* dim, int32_t* rows, int32_t* width, int32_t* pitch) try {
   if (!b || !dim || !rows || !width || !pitch) return fail(ORL_E_INVALID, "null argument");
   if (int rc = link_features_check(b)) return rc;
-  *dim = link_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, b->P.E);
-  *rows = link_obs_rows(b->P.env_type, b->P.C, b->P.E);
-  *width = link_obs_width(b->P.K);
-  *pitch = path_obs_pitch(*dim);
+  const ViewShape sh = view_shape(b->P, VIEW_LINK_FEATURES, 0);
+  *dim = (int32_t)sh.dim;
+  *rows = sh.rows;
+  *width = sh.width;
+  *pitch = (int32_t)sh.pitch;
   return ORL_OK;
 }
 ORL_ABI_CATCH_INT
@@ -1440,17 +1414,17 @@ extern "C" int orl_batch_link_features(orl_batch* b, float* out) try {
   if (!b) return fail(ORL_E_INVALID, "null argument");
   if (int rc = link_features_check(b)) return rc;
   HIPCHK(hipSetDevice(b->device));
-  const int dim = link_obs_dim(b->P.env_type, b->P.N, b->P.K, b->P.C, b->P.E), pitch = path_obs_pitch(dim);
-  if (int rc = view_buffer(b, b->lf_buf, (size_t)(b->P.B * (int64_t)pitch) * sizeof(float), "link features")) return rc;
+  const ViewShape sh = view_shape(b->P, VIEW_LINK_FEATURES, 0);
+  if (int rc = view_buffer(b, b->lf_buf, (size_t)(b->P.B * sh.pitch) * sizeof(float), "link features")) return rc;
   ORL_LAUNCH(link_features, b, b->lf_buf);
   HIPCHK(hipGetLastError());
-  return out ? view_rows_to_host(b, b->lf_buf, sizeof(float), dim, pitch, out) : ORL_OK;
+  return view_rows_to_host(b, b->lf_buf, sh, out);
 }
 ORL_ABI_CATCH_INT
 
 static int qos_obs_check(const orl_batch* b) {
   if (b->P.env_type != ENV_QOS) return fail(ORL_E_INVALID, "MatrixObservationWithPaths is defined for QoSConstrainedRA only");
-  if ((size_t)ORL_QOBS_WAVES * qos_obs_wave_lds(b->P.E, b->P.K) > 64 * 1024)
+  if (!view_plan(b->P, b->wt, VIEW_MATRIX_PATHS_OBS, 0).ok)
     return fail(ORL_E_INVALID, "MatrixObservationWithPaths of %d links x %d paths exceeds the kernel's LDS budget", b->P.E, b->P.K);
   return ORL_OK;
 }
@@ -1458,8 +1432,9 @@ static int qos_obs_check(const orl_batch* b) {
 extern "C" int orl_batch_matrix_paths_obs_shape(const orl_batch* b, int32_t* dim, int32_t* pitch) try {
   if (!b || !dim || !pitch) return fail(ORL_E_INVALID, "null argument");
   if (int rc = qos_obs_check(b)) return rc;
-  *dim = (int32_t)qos_obs_dim(b->P);
-  *pitch = (int32_t)qos_obs_pitch(b->P);
+  const ViewShape sh = view_shape(b->P, VIEW_MATRIX_PATHS_OBS, 0);
+  *dim = (int32_t)sh.dim;
+  *pitch = (int32_t)sh.pitch;
   return ORL_OK;
 }
 ORL_ABI_CATCH_INT
@@ -1468,14 +1443,13 @@ extern "C" int orl_batch_matrix_paths_observation(orl_batch* b, uint8_t* out) tr
   if (!b) return fail(ORL_E_INVALID, "null argument");
   if (int rc = qos_obs_check(b)) return rc;
   HIPCHK(hipSetDevice(b->device));
-  const int64_t B = b->P.B, dim = qos_obs_dim(b->P), pitch = qos_obs_pitch(b->P);
-  if (int rc = view_buffer(b, b->qobs_buf, (size_t)(B * pitch), "MatrixObservationWithPaths")) return rc;
-  const unsigned grid = (unsigned)((B + ORL_QOBS_WAVES - 1) / ORL_QOBS_WAVES);
-  const size_t lds = (size_t)ORL_QOBS_WAVES * qos_obs_wave_lds(b->P.E, b->P.K);
-  hipLaunchKernelGGL(k_qos_matrix_obs, dim3(grid), dim3(256), lds, b->stream, b->P, b->qobs_buf, (int)pitch);
+  const ViewShape sh = view_shape(b->P, VIEW_MATRIX_PATHS_OBS, 0);
+  if (int rc = view_buffer(b, b->qobs_buf, (size_t)(b->P.B * sh.pitch), "MatrixObservationWithPaths")) return rc;
+  const ViewPlan pl = view_plan(b->P, b->wt, VIEW_MATRIX_PATHS_OBS, 0);
+  hipLaunchKernelGGL(k_qos_matrix_obs, dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, b->P, b->qobs_buf, (int)sh.pitch);
   ORL_TK(b, "k_qos_matrix_obs");
   HIPCHK(hipGetLastError());
-  return out ? view_rows_to_host(b, b->qobs_buf, 1, dim, pitch, out) : ORL_OK;
+  return view_rows_to_host(b, b->qobs_buf, sh, out);
 }
 ORL_ABI_CATCH_INT
 
@@ -2074,6 +2048,22 @@ extern "C" int orl_debug_run_plan(const orl_env_config* cfg, const orl_topology_
                          pl.clear_counters ? 1 : 0};
   memcpy(out, v, sizeof v);
   return 11;
+}
+catch (...) { return 0; }
+extern "C" int orl_debug_view_plan(int env_type, int W, int64_t B, int N, int E, int K, int C, int S, int J, int M, int view, int arg,
+                                   int32_t* out) try {
+  if (!out || env_type < 0 || env_type > ORL_ENV_QOS || (W != 1 && W != 2 && W != 5 && W != 8) || B < 1 || N < 1 || E < 1 || K < 1 || C < 1 || S < 1 ||
+      J < 1 || M < 1 || view < 0 || view >= VIEW_COUNT)
+    return 0;
+  DevParams P;
+  memset(&P, 0, sizeof P);
+  P.env_type = env_type; P.B = B; P.N = N; P.E = E; P.K = K; P.C = C; P.S = S; P.J = J; P.M = M;
+  const ViewShape sh = view_shape(P, view, arg);
+  const ViewPlan pl = view_plan(P, W, view, arg);
+  const int32_t v[13] = {(int32_t)sh.dim, sh.rows, sh.width, (int32_t)sh.pitch, sh.elem_bytes, pl.ok, pl.waves, pl.block, (int32_t)pl.grid, (int32_t)pl.lds_bytes,
+                         pl.staged, pl.chunk, pl.counted};
+  memcpy(out, v, sizeof v);
+  return 13;
 }
 catch (...) { return 0; }
 extern "C" int orl_batch_load_spec(orl_batch* b, const char* so_path) try {

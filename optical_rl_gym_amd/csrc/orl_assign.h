@@ -37,6 +37,7 @@
 // dwords of LDS one env's byte counters take (CNT): W words of 17 dwords, padded to 8 (mod 32)
 __host__ __device__ inline int assign_env_dwords(int W) { return 17 * W + ((8 - 17 * W) & 31); }
 
+#ifdef ORL_W  // (the kernel: the per-W units, orl_kernels.hip; the API unit takes the size above for its view_plan)
 // BEST_FIT / EXACT_FIT on r = fits(p), by the group's lane gl: over the maximal runs of r that start in word gl (none for gl >= W)
 // the smallest key (l << 10) | start, the run having l + 1 bits — a free run of n + l slots.  The run's last bit is the lowest
 // "last bit of a run" at or above its start: in word gl, or the lowest one of the words above.  0x7fffffff: no run starts there
@@ -182,3 +183,4 @@ __global__ void __launch_bounds__(256) k_assign_spectrum(DevParams P, int rule, 
     *(int4*)(P.actions + v.env * 4) = a;
   }
 }
+#endif

@@ -42,6 +42,11 @@ struct orl_topology {
 // per-kernel timing (orl_batch_run, time_kernels == 1): an event after every launch
 struct TkRec { std::vector<hipEvent_t> ev; std::vector<const char*> name; };
 
+// A host `given` on its way to the device (stage_given, orl_api.hip): the device buffer a kernel reads it from, the page-locked
+// buffer it is copied through, and the event behind the last upload out of that one — the next call waits for it before it refills
+// the buffer.  All three allocated on first use.
+struct GivenStage { int32_t* dev = nullptr; int32_t* host = nullptr; hipEvent_t up = nullptr; };
+
 struct orl_batch {
   orl::DevParams P;
   TkRec* tk = nullptr;
@@ -87,15 +92,11 @@ struct orl_batch {
   double* ep_rew_buf = nullptr;    // QoSConstrainedRA: the float64 reward sums beside it, same shape
   unsigned char* mask_buf[4] = {nullptr, nullptr, nullptr, nullptr};  // action masks per layout (ORL_MASK_*): [B][pitch] bytes, allocated
                                    // by the first orl_batch_action_mask of that layout (a view of one stays that layout's)
-  int32_t* mask_given = nullptr;   // ORL_MASK_CORE_SLOT with a host `given`: the (path, modulation) pairs [B][2] on the device and in
-  int32_t* h_mask_given = nullptr; // page-locked memory, allocated on first use
-  hipEvent_t ev_given_up = nullptr;  // behind the last upload out of h_mask_given: the next call waits for it before it refills the buffer
-  int32_t* complete_given = nullptr;    // orl_batch_complete_actions with a host `given`: the prefixes [B][n_given <= 3] on the device and in
-  int32_t* h_complete_given = nullptr;  // page-locked memory (both [B][3]), allocated on first use — not the masks' pair: either call may
-  hipEvent_t ev_complete_up = nullptr;  // refill its staging buffer without waiting for the other's upload; behind the last upload out of it
-  int32_t* assign_given = nullptr;      // orl_batch_assign_spectrum with a host `given`: the paths [B] on the device and in page-locked
-  int32_t* h_assign_given = nullptr;    // memory, allocated on first use — a pair of its own, as the completion's
-  hipEvent_t ev_assign_up = nullptr;    // behind the last upload out of h_assign_given
+  // host `given`s: [0] ORL_MASK_CORE_SLOT's (path, modulation) pairs [B][2], [1] orl_batch_complete_actions' prefixes [B][n_given <= 3]
+  // (capacity [B][3]), [2] orl_batch_assign_spectrum's paths [B].  One stage per call on purpose: each may refill its staging
+  // buffer without waiting for another's upload.
+  enum { GIVEN_MASK, GIVEN_COMPLETE, GIVEN_ASSIGN, GIVEN_STAGES };
+  GivenStage given[GIVEN_STAGES];
   int mask_last = -1;              // layout of the last launch: what ORL_BUF_ACTION_MASK hands out (-1: none yet)
   float* pf_buf[9] = {};           // path features per block count j (1 .. 8): [B][pitch] floats, allocated by the first
                                    // orl_batch_path_features of that j (a view of one stays that j's)
@@ -124,15 +125,6 @@ static inline void slot_maps_change(orl_batch* b, hipStream_t st) {
   }
 }
 
-// path features (orl_path_obs.h, orl_batch_path_features): block rows per env, row length for j blocks per row, device pitch in floats
-static inline int path_obs_rows(int env_type, int K, int C) { return env_type == orl::ENV_RMCSA ? K * C : K; }
-static inline int path_obs_dim(int env_type, int N, int K, int C, int j) { return 1 + 2 * N + path_obs_rows(env_type, K, C) * (2 * j + 3); }
-static inline int path_obs_pitch(int dim) { return (dim + 3) / 4 * 4; }
-// link features (orl_link_obs.h, orl_batch_link_features): slot rows per env, values per row, row length; the pitch is path_obs_pitch's
-static inline int link_obs_rows(int env_type, int C, int E) { return (env_type == orl::ENV_RMCSA ? C : 1) * E; }
-static inline int link_obs_width(int K) { return 10 + K; }
-static inline int link_obs_dim(int env_type, int N, int K, int C, int E) { return 1 + 2 * N + link_obs_rows(env_type, C, E) * link_obs_width(K); }
-
 #define ORL_TK(B_, NAME)                                                                 \
   do {                                                                                   \
     if ((B_)->tk) {                                                                      \
@@ -150,15 +142,17 @@ template <int W> void reset(orl_batch* b, int full, const unsigned char* dmask);
 template <int W> void policy(orl_batch* b, int pol);                       // stand-alone slot scan -> P.actions
 template <int W> void step64(orl_batch* b, int auto_reset, int want_info, int fused_policy);  // one wavefront per env
 template <int W> void obs(orl_batch* b, int with_terminal);                // DeepRMSA observation
-template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, int pitch);  // k_action_mask -> out [B][pitch]
-// k_rmcsa_mask -> out [B][pitch]; given: device (path, modulation) of env e at given[e * gstride + 0 / 1]; -1: refused (nothing launched)
-template <int W> int rmcsa_mask(orl_batch* b, int layout, unsigned char* out, int pitch, const int* given, int gstride);
+// The views of the pending service: each launches what view_plan (orl_view_plan.h) says, into rows of view_shape's pitch.  A plan
+// that is not ok is the caller's to refuse before it allocates or queues anything.
+template <int W> void action_mask(orl_batch* b, int layout, unsigned char* out);  // k_action_mask -> out [B][pitch]
+// k_rmcsa_mask -> out [B][pitch]; given: device (path, modulation) of env e at given[e * gstride + 0 / 1]
+template <int W> void rmcsa_mask(orl_batch* b, int layout, unsigned char* out, const int* given, int gstride);
 // k_rmcsa_complete: the first n_given action columns of env e at given[e * gstride ...] (device) completed first-fit into P.actions
 template <int W> void rmcsa_complete(orl_batch* b, int n_given, const int* given, int gstride);
 // k_assign_spectrum: the path of env e at given[e * gstride] (device; n_given == 0: all paths) and its first slot under `rule` into P.actions
 template <int W> void assign_spectrum(orl_batch* b, int rule, int n_given, const int* given, int gstride);
-template <int W> void path_features(orl_batch* b, float* out, int j, int mod);  // k_path_features -> out [B][round_up(dim, 4)] floats
-template <int W> void link_features(orl_batch* b, float* out);             // k_link_features -> out [B][round_up(dim, 4)] floats
+template <int W> void path_features(orl_batch* b, float* out, int j, int mod);  // k_path_features -> out [B][pitch] floats
+template <int W> void link_features(orl_batch* b, float* out);             // k_link_features -> out [B][pitch] floats
 // k_persist in the form `ch` (the run's choice for the whole batch; use_spec: made for the attached specialisation library) over the
 // env range of view VP up to step `target` of this run, then k_rel_tail, on stream st
 template <int W> void persist(orl_batch* b, const orl::DevParams& VP, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,

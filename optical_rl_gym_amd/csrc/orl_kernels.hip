@@ -2050,13 +2050,15 @@ __global__ void __launch_bounds__(256) k_obs8(DevParams P, int with_terminal) {
 }
 
 #ifndef ORL_SPEC_ONLY
-#include "orl_view.h"  // what the three views below share: the opening, the pending service, bit rows -> byte rows, the LDS budget
+#include "orl_view.h"  // what the views below share: the opening, the pending service, bit rows -> byte rows
 #include "orl_mask.h"  // k_action_mask: action masks of the pending service (RMSA, DeepRMSA, RWA)
 #include "orl_rmcsa_mask.h"  // k_rmcsa_mask: the two-stage masks of RMCSA (path-modulation, core-slot)
 #include "orl_rmcsa_complete.h"  // k_rmcsa_complete: a partial RMCSA action completed first-fit under the masks' rule
 #include "orl_assign.h"  // k_assign_spectrum: the first slot of an RMSA / RWA action under a named spectrum-assignment rule
 #include "orl_path_obs.h"  // k_path_features: the path-feature observation of the pending service (every slot-map family)
 #include "orl_link_obs.h"  // k_link_features: the per-link feature observation of the pending service (every slot-map family)
+#include "orl_qos_obs.h"  // (its kernel is the API unit's: here the LDS size of its wavefront alone)
+#include "orl_view_plan.h"  // view_shape, view_plan: the shape of each view's rows and the geometry of its launch
 #endif
 
 // ---- QoSConstrainedRA for an agent in the loop: 8 lanes per env (round 5) --------------------------------------------------------
@@ -2250,85 +2252,65 @@ template <int W> void obs(orl_batch* b, int with_terminal) {
   ORL_TK(b, "k_obs");
 }
 
-// k_action_mask (orl_mask.h) into `out` ([B][pitch] bytes on the device); -1 when the LDS rows of 4 wavefronts (32 envs) exceed 48 KiB
-template <int W> int action_mask(orl_batch* b, int layout, unsigned char* out, int pitch) {
+// ---- the views of the pending service: plan (orl_view_plan.h: the launch's geometry, and the shape of the rows it writes), launch ----
+// A plan that is not ok is refused by the API before it calls these.
+
+// k_action_mask (orl_mask.h) into `out` ([B][pitch] bytes on the device)
+template <int W> void action_mask(orl_batch* b, int layout, unsigned char* out) {
   const DevParams& VP = b->P;
-  const size_t wave = (size_t)8 * mask_env_words(layout, VP.env_type, W, VP.K) * sizeof(u32);
-  const int waves = 4;
-  if (view_waves(wave) < waves) return -1;
-  const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
-  hipLaunchKernelGGL((k_action_mask<W>), dim3(grid), dim3(64 * waves), waves * wave, b->stream, VP, out, layout, pitch);
+  const ViewPlan pl = view_plan(VP, W, VIEW_ACTION_MASK, layout);
+  hipLaunchKernelGGL((k_action_mask<W>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, out, layout, (int)view_shape(VP, VIEW_ACTION_MASK, layout).pitch);
   ORL_TK(b, "k_action_mask");
-  return 0;
 }
 
 // k_rmcsa_mask (orl_rmcsa_mask.h) into `out` ([B][pitch] bytes on the device); `given`: device int32, the (path, modulation) of env e
-// at given[e * gstride + 0 / 1] (ORL_MASK_CORE_SLOT).  -1, and no launch, when the LDS rows of one wavefront's 8 envs exceed 48 KiB
-// or a path's M modulations do not fit its 32-bit word; out == nullptr: that check alone
-template <int W> int rmcsa_mask(orl_batch* b, int layout, unsigned char* out, int pitch, const int* given, int gstride) {
+// at given[e * gstride + 0 / 1] (ORL_MASK_CORE_SLOT)
+template <int W> void rmcsa_mask(orl_batch* b, int layout, unsigned char* out, const int* given, int gstride) {
   const DevParams& VP = b->P;
-  const size_t wave = (size_t)8 * rmcsa_mask_env_words(layout, W, VP.K, VP.C) * sizeof(u32);
-  const int waves = view_waves(wave);
-  if (!waves || VP.M > 32) return -1;
-  if (!out) return 0;
-  const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
-  hipLaunchKernelGGL((k_rmcsa_mask<W>), dim3(grid), dim3(64 * waves), waves * wave, b->stream, VP, out, layout, pitch, given, gstride);
+  const ViewPlan pl = view_plan(VP, W, VIEW_RMCSA_MASK, layout);
+  hipLaunchKernelGGL((k_rmcsa_mask<W>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, out, layout, (int)view_shape(VP, VIEW_RMCSA_MASK, layout).pitch, given,
+                     gstride);
   ORL_TK(b, "k_rmcsa_mask");
-  return 0;
 }
 
 // k_rmcsa_complete (orl_rmcsa_complete.h): the first n_given columns of env e at given[e * gstride ...] (device int32) completed into
 // its row of P.actions
 template <int W> void rmcsa_complete(orl_batch* b, int n_given, const int* given, int gstride) {
   const DevParams& VP = b->P;
-  const int waves = 4;
-  const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
-  hipLaunchKernelGGL((k_rmcsa_complete<W>), dim3(grid), dim3(64 * waves), 0, b->stream, VP, n_given, given, gstride);
+  const ViewPlan pl = view_plan(VP, W, VIEW_COMPLETE, 0);
+  hipLaunchKernelGGL((k_rmcsa_complete<W>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, n_given, given, gstride);
   ORL_TK(b, "k_rmcsa_complete");
 }
 
 // k_assign_spectrum (orl_assign.h): the path of env e at given[e * gstride] (device int32; n_given == 0: every path in order) and the
 // first slot under `rule` into its row of P.actions.  Rules 4 and 5 run the instantiation with the per-slot occupancy counts and its
-// LDS (4 wavefronts fit 48 KiB for every W: view_waves); the others take none.
+// LDS; the others take none.
 template <int W> void assign_spectrum(orl_batch* b, int rule, int n_given, const int* given, int gstride) {
   const DevParams& VP = b->P;
-  const bool cnt = rule == ORL_ASSIGN_MOST_USED || rule == ORL_ASSIGN_LEAST_USED;
-  const size_t wave_lds = cnt ? (size_t)8 * assign_env_dwords(W) * sizeof(u32) : 0;
-  const int waves = cnt ? view_waves(wave_lds) : 4;
-  const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
-  if (cnt) hipLaunchKernelGGL((k_assign_spectrum<W, true>), dim3(grid), dim3(64 * waves), waves * wave_lds, b->stream, VP, rule, n_given, given, gstride);
-  else hipLaunchKernelGGL((k_assign_spectrum<W, false>), dim3(grid), dim3(64 * waves), 0, b->stream, VP, rule, n_given, given, gstride);
+  const ViewPlan pl = view_plan(VP, W, VIEW_ASSIGN, rule);
+  if (pl.counted) hipLaunchKernelGGL((k_assign_spectrum<W, true>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, rule, n_given, given, gstride);
+  else hipLaunchKernelGGL((k_assign_spectrum<W, false>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, rule, n_given, given, gstride);
   ORL_TK(b, "k_assign_spectrum");
 }
 
 // k_path_features (orl_path_obs.h) into `out` ([B][pitch] floats on the device): j blocks per row, RMCSA under modulation `mod`
-// (-1: each path's best).  The wavefront's rows are staged in LDS where 8 of them fit 48 KiB, else every lane stores its own blocks
+// (-1: each path's best).  The wavefront's rows are staged in LDS where 8 of them fit, else every lane stores its own blocks
 // (-DORL_PATH_OBS_STAGE=0: always — the build the two forms were measured against each other with).
 template <int W> void path_features(orl_batch* b, float* out, int j, int mod) {
   const DevParams& VP = b->P;
-  const int dim = path_obs_dim(VP.env_type, VP.N, VP.K, VP.C, j), pitch = path_obs_pitch(dim);
-  const size_t wave = (size_t)8 * pitch * sizeof(float);
-  const int fit = ORL_PATH_OBS_STAGE ? view_waves(wave) : 0, waves = fit ? fit : 4;
-  const size_t lds = fit ? waves * wave : 0;
-  const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
-  hipLaunchKernelGGL((k_path_features<W>), dim3(grid), dim3(64 * waves), lds, b->stream, VP, out, j, mod, dim, pitch, fit ? 1 : 0);
+  const ViewPlan pl = view_plan(VP, W, VIEW_PATH_FEATURES, j);
+  const ViewShape sh = view_shape(VP, VIEW_PATH_FEATURES, j);
+  hipLaunchKernelGGL((k_path_features<W>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, out, j, mod, (int)sh.dim, (int)sh.pitch, pl.staged ? 1 : 0);
   ORL_TK(b, "k_path_features");
 }
 
-// k_link_features (orl_link_obs.h) into `out` ([B][pitch] floats on the device).  The wavefront's rows are staged whole in LDS where
-// 8 of them, beside the 8 envs' link sets, fit 48 KiB; else in rounds of `chunk` slot rows per env, the most (a multiple of 8) that
-// 4, 2 or 1 wavefronts' staging fits.
+// k_link_features (orl_link_obs.h) into `out` ([B][pitch] floats on the device), the wavefront's rows staged whole in LDS or in rounds
+// of pl.chunk slot rows per env
 template <int W> void link_features(orl_batch* b, float* out) {
   const DevParams& VP = b->P;
-  const int dim = link_obs_dim(VP.env_type, VP.N, VP.K, VP.C, VP.E), pitch = path_obs_pitch(dim), F = link_obs_width(VP.K);
-  int waves = view_waves(link_obs_wave_lds(VP.K, pitch)), chunk = 0;
-  if (!waves) {
-    waves = view_waves(link_obs_wave_lds(VP.K, 8 * F));  // (k = 64: 8 blocks of 74 floats for 8 envs + their link sets = 27 kB, one wavefront)
-    chunk = (int)((48 * 1024 / waves - link_obs_wave_lds(VP.K, 0)) / (8 * F * sizeof(float))) / 8 * 8;
-  }
-  const size_t lds = waves * link_obs_wave_lds(VP.K, chunk ? chunk * F : pitch);
-  const unsigned grid = (unsigned)((VP.B + 8 * waves - 1) / (8 * waves));
-  hipLaunchKernelGGL((k_link_features<W>), dim3(grid), dim3(64 * waves), lds, b->stream, VP, out, dim, pitch, chunk);
+  const ViewPlan pl = view_plan(VP, W, VIEW_LINK_FEATURES, 0);
+  const ViewShape sh = view_shape(VP, VIEW_LINK_FEATURES, 0);
+  hipLaunchKernelGGL((k_link_features<W>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, out, (int)sh.dim, (int)sh.pitch, pl.chunk);
   ORL_TK(b, "k_link_features");
 }
 
@@ -2482,8 +2464,8 @@ template int prof_read<ORL_W>(unsigned long long*, int);
 template void policy<ORL_W>(orl_batch*, int);
 template void step64<ORL_W>(orl_batch*, int, int, int);
 template void obs<ORL_W>(orl_batch*, int);
-template int action_mask<ORL_W>(orl_batch*, int, unsigned char*, int);
-template int rmcsa_mask<ORL_W>(orl_batch*, int, unsigned char*, int, const int*, int);
+template void action_mask<ORL_W>(orl_batch*, int, unsigned char*);
+template void rmcsa_mask<ORL_W>(orl_batch*, int, unsigned char*, const int*, int);
 template void rmcsa_complete<ORL_W>(orl_batch*, int, const int*, int);
 template void assign_spectrum<ORL_W>(orl_batch*, int, int, const int*, int);
 template void path_features<ORL_W>(orl_batch*, float*, int, int);

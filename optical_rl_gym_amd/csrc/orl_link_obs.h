@@ -1,6 +1,6 @@
 // orl_link_obs.h — the per-link feature observation of the pending service (include/orl.h, orl_batch_link_features); included by
-// orl_kernels.hip behind orl_view.h (the kernel's opening, the decode of the pending service, the row header and the LDS budget
-// rule are shared with the other views and live there).
+// orl_kernels.hip behind orl_view.h (the kernel's opening, the decode of the pending service and the row header are shared
+// with the other views and live there; the LDS budget rule: orl_view_plan.h).
 //
 // Per env one row of dim = 1 + 2 N + R F float32 values at a device pitch of round_up(dim, 4) floats; consecutive envs are
 // contiguous.  The header is the path features' {bit_rate / 100 (RWA: 0), one-hot min(src, dst), one-hot max(src, dst)}; then one
@@ -29,7 +29,7 @@
 // No atomics, no host synchronisation: graph-capturable.
 #pragma once
 
-// (link_obs_rows / link_obs_width / link_obs_dim: orl_host.h, shared with the API unit)
+// (the row's shape: orl_view_plan.h, view_shape)
 
 // LDS bytes of one wavefront: its 8 envs' K link sets of two words each, then `floats` floats of staging for each of the 8 envs (whole:
 // the pitch; chunked: chunk x (10 + K))
@@ -37,6 +37,7 @@ __host__ __device__ inline size_t link_obs_wave_lds(int K, int floats) {
   return (size_t)8 * 2 * K * sizeof(u64) + (size_t)8 * floats * sizeof(float);
 }
 
+#ifdef ORL_W  // (the kernel: the per-W units, orl_kernels.hip; the API unit takes the size above for its view_plan)
 // one slot row's block: the 10 + K values of row `a` of link l; ls: the link's record of DevParams::lstat, pm: the env's K link sets
 template <int W>
 __device__ __forceinline__ void link_obs_block(const Row<W>& a, int S, const sp::Recip& rS, const double* ls, const u64* pm, int l, int K,
@@ -140,3 +141,4 @@ __global__ void __launch_bounds__(256) k_link_features(DevParams P, float* out, 
   const uint4* src4 = (const uint4*)stage;
   for (int g = lane; g < nch; g += 64) dst4[g] = src4[g];
 }
+#endif

@@ -1,6 +1,6 @@
 // orl_mask.h — action masks of the pending service (include/orl.h, orl_batch_action_mask); included by orl_kernels.hip behind
 // orl_view.h, which holds what this view shares with the others: the kernel's opening (view_lanes), the decode of the pending service
-// (view_pending), the rows' way from LDS to memory (view_store_rows) and the LDS budget rule (view_waves).
+// (view_pending) and the rows' way from LDS to memory (view_store_rows); the LDS budget rule (view_waves) is orl_view_plan.h's.
 //
 // Per env, one row of `dim` bytes (0/1) at a device pitch of round_up(dim, 16); consecutive envs are contiguous.
 //   ORL_MASK_JOINT  RMSA / RWA: column p * S + s = action (path p, first slot / wavelength s); DeepRMSA: column p * j + b = action
@@ -27,6 +27,7 @@ __host__ __device__ inline int mask_row_words(int layout, int env_type, int W) {
 }
 __host__ __device__ inline int mask_env_words(int layout, int env_type, int W, int K) { return K * mask_row_words(layout, env_type, W) + 2; }
 
+#ifdef ORL_W  // (the kernel: the per-W units, orl_kernels.hip; the API unit takes the size above for its view_plan)
 template <int W>
 __global__ void __launch_bounds__(256) k_action_mask(DevParams P, unsigned char* out, int layout, int pitch) {
   const ViewLanes v = view_lanes();
@@ -66,3 +67,4 @@ __global__ void __launch_bounds__(256) k_action_mask(DevParams P, unsigned char*
   wave_fence();
   view_store_rows(lds, K, rw, cpp, ew, K * rw, P.allow_rejection, v.env0, P.B, out, pitch);
 }
+#endif

@@ -25,11 +25,7 @@
 // No atomics, no host synchronisation: graph-capturable.
 #pragma once
 
-#ifndef ORL_PATH_OBS_STAGE
-#define ORL_PATH_OBS_STAGE 1  // 0: the direct form for every shape (A/B builds)
-#endif
-
-// (path_obs_rows / path_obs_dim / path_obs_pitch: orl_host.h, shared with the API unit)
+// (the row's shape and ORL_PATH_OBS_STAGE: orl_view_plan.h, view_shape / view_plan)
 
 // one row's block: the 2 j + 3 values of the free-slot row m for a service of n slots
 template <int W>

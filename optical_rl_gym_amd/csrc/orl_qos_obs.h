@@ -24,6 +24,7 @@
 // LDS bytes of one wavefront: E (k + 1) u16 run lengths, padded to 16 bytes
 __host__ __device__ inline int qos_obs_wave_lds(int E, int K) { return (E * (K + 1) * 2 + 15) / 16 * 16; }
 
+#ifndef ORL_W  // (the kernel: the API unit; the per-W units, orl_kernels.hip, take the size above for their view_plan)
 __global__ void __launch_bounds__(256) k_qos_matrix_obs(DevParams P, unsigned char* out, int pitch) {
   const int lane = lane_id();
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -94,3 +95,4 @@ __global__ void __launch_bounds__(256) k_qos_matrix_obs(DevParams P, unsigned ch
     if (off >= S) { off -= S; g++; }
   }
 }
+#endif

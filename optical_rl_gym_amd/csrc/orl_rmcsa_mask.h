@@ -1,6 +1,6 @@
 // orl_rmcsa_mask.h — the two-stage action masks of RMCSA's pending service (include/orl.h, ORL_MASK_PATH_MOD / ORL_MASK_CORE_SLOT);
-// included by orl_kernels.hip behind orl_view.h (the kernel's opening, the decode of the pending service, the rows' way from LDS
-// to memory and the LDS budget rule are shared with the other views and live there).
+// included by orl_kernels.hip behind orl_view.h (the kernel's opening, the decode of the pending service and the rows' way from
+// LDS to memory are shared with the other views and live there; the LDS budget rule: orl_view_plan.h).
 //
 // An RMCSA action is (path p, modulation m, core c, first slot s).  With n = nslots[br_idx][m], stepping it provisions iff
 // (rmcsa_env.py:209-289 with is_path_free :767-794, get_number_slots :753-765, _crosstalk_is_acceptable :341-384)
@@ -32,6 +32,7 @@ __host__ __device__ inline int rmcsa_mask_row_words(int layout, int W) { return 
 __host__ __device__ inline int rmcsa_mask_env_words(int layout, int W, int K, int C) {
   return rmcsa_mask_rows(layout, K, C) * rmcsa_mask_row_words(layout, W) + 2 + (layout == ORL_MASK_PATH_MOD ? K * C : 0);
 }
+#ifdef ORL_W  // (the kernel: the per-W units, orl_kernels.hip; the API unit takes the size above for its view_plan)
 // is modulation m within both reach limits for a path of length len at bit-rate index br_idx?
 __device__ __forceinline__ bool rmcsa_reach(const DevParams& P, double len, int m, int br_idx) {
   return len < P.lmax_xt[m] && len < P.lmax_snr[m * P.n_br + br_idx];
@@ -95,3 +96,4 @@ __global__ void __launch_bounds__(256) k_rmcsa_mask(DevParams P, unsigned char* 
   wave_fence();
   view_store_rows(lds, nrows, rw, cpp, ew, nrows * rw, P.allow_rejection, v.env0, P.B, out, pitch);
 }
+#endif

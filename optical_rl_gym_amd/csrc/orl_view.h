@@ -6,8 +6,7 @@
 //   view_pending       the pending service of an env, decoded from its scalar record
 //   view_obs_header    the float32 header of the feature rows (orl_path_obs.h, orl_link_obs.h) and their pad columns
 //   view_store_rows    a wavefront's 8 envs' bit rows in LDS -> their output rows of 0/1 bytes, as 16-byte stores
-//   view_waves         wavefronts per workgroup that 48 KiB of LDS allow (host)
-// (orl_device.h has no decode of the scalar record short of the whole Env; k_policy reads the svc_desc word instead.)
+// (The host side of the views — row shapes, launch geometry, the LDS budget rule view_waves — is orl_view_plan.h.  orl_device.h has no decode of the scalar record short of the whole Env; k_policy reads the svc_desc word instead.)
 #pragma once
 
 // 4 bits -> 4 bytes of 0/1 (bit i lands at bit 8 i; the four partial products do not overlap)
@@ -91,12 +90,4 @@ __device__ __forceinline__ void view_store_rows(const u32* lds, int nrows, int r
     if (allow && ncols >= c0 && ncols < c0 + 16) bits |= 1u << (ncols - c0);  // reject column
     *(uint4*)(out + e * pitch + c0) = view_bits16_bytes(bits);
   }
-}
-
-// wavefronts per workgroup of a view whose wavefront keeps `bytes_per_wavefront` of LDS: the most of 4, 2, 1 that fit 48 KiB; 0: not
-// even one does
-inline int view_waves(size_t bytes_per_wavefront) {
-  for (int w = 4; w >= 1; w >>= 1)
-    if (w * bytes_per_wavefront <= 48 * 1024) return w;
-  return 0;
 }

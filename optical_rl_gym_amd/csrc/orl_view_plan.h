@@ -1,0 +1,141 @@
+// orl_view_plan.h — the host-side decisions of the per-step device views of the pending service: the shape of a view's rows
+// (view_shape) and the geometry of its launch (view_plan).
+//
+// Like the form choice (orl_persist_form.h) and the run plan (orl_run_plan.h) both are pure functions of the batch's sizes, pinned
+// without a device by tests/test_view_plan.py (orl_debug_view_plan).  No HIP call in here.  Included behind the views' headers
+// (orl_mask.h, orl_rmcsa_mask.h, orl_assign.h, orl_link_obs.h, orl_qos_obs.h), which keep the LDS sizes of one env or wavefront
+// next to the kernels that lay them out; orl_kernels.hip and orl_api.hip both see all of them, their kernels only where they are
+// launched.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#ifndef ORL_PATH_OBS_STAGE
+#define ORL_PATH_OBS_STAGE 1  // 0: the path features' direct form for every shape (A/B builds)
+#endif
+
+enum ViewKind {
+  VIEW_ACTION_MASK = 0,    // k_action_mask (RMSA, DeepRMSA, RWA); arg: the layout
+  VIEW_RMCSA_MASK,         // k_rmcsa_mask; arg: the layout
+  VIEW_COMPLETE,           // k_rmcsa_complete
+  VIEW_ASSIGN,             // k_assign_spectrum; arg: the rule
+  VIEW_PATH_FEATURES,      // k_path_features; arg: j
+  VIEW_LINK_FEATURES,      // k_link_features
+  VIEW_MATRIX_PATHS_OBS,   // k_qos_matrix_obs
+  VIEW_COUNT
+};
+
+// LDS of one workgroup: what a kernel gets without asking for more (every view but the last stays within it), and the most a
+// workgroup can ask for
+constexpr size_t kViewLdsDefault = 48 * 1024;
+constexpr size_t kViewLdsMax = 64 * 1024;
+
+// wavefronts per workgroup of a view whose wavefront keeps `bytes_per_wavefront` of LDS: the most of 4, 2, 1 that fit
+// kViewLdsDefault; 0: not even one does
+inline int view_waves(size_t bytes_per_wavefront) {
+  for (int w = 4; w >= 1; w >>= 1)
+    if (w * bytes_per_wavefront <= kViewLdsDefault) return w;
+  return 0;
+}
+
+// A view's rows: per env `dim` elements of `elem_bytes` at a device pitch of `pitch` elements (rows are written as 16-byte
+// stores); the feature rows are a header and `rows` blocks of `width` values.  dim == 0: this family has no such layout.
+struct ViewShape { int64_t dim; int rows, width; int64_t pitch; int elem_bytes; };
+// arg: the mask layout (ORL_MASK_*), the path features' j
+inline ViewShape view_shape(const orl::DevParams& P, int view, int arg) {
+  const bool rmcsa = P.env_type == orl::ENV_RMCSA;
+  ViewShape s = {0, 0, 0, 0, 1};
+  switch (view) {
+    case VIEW_ACTION_MASK:
+    case VIEW_RMCSA_MASK:  // (orl_mask.h, orl_rmcsa_mask.h: the family decides which layouts exist)
+      if (rmcsa) s.dim = arg == ORL_MASK_PATH_MOD ? P.K * P.M + 1 : (arg == ORL_MASK_CORE_SLOT ? P.C * P.S + 1 : 0);
+      else if (P.env_type != orl::ENV_RMSA && P.env_type != orl::ENV_DEEPRMSA && P.env_type != orl::ENV_RWA) s.dim = 0;
+      else if (arg == ORL_MASK_JOINT) s.dim = P.K * (P.env_type == orl::ENV_DEEPRMSA ? P.J : P.S) + 1;
+      else if (arg == ORL_MASK_PATH && P.env_type != orl::ENV_DEEPRMSA) s.dim = P.K + 1;
+      break;
+    case VIEW_COMPLETE:
+    case VIEW_ASSIGN:  // the env's row of ORL_BUF_ACTIONS
+      s.dim = 4; s.elem_bytes = 4;
+      break;
+    case VIEW_PATH_FEATURES:  // (orl_path_obs.h) the header, then a block of 2 j + 3 values per path (RMCSA: per path and core)
+      s.rows = rmcsa ? P.K * P.C : P.K; s.width = 2 * arg + 3; s.elem_bytes = 4;
+      s.dim = 1 + 2 * P.N + s.rows * s.width;
+      break;
+    case VIEW_LINK_FEATURES:  // (orl_link_obs.h) the header, then a block of 10 + k values per slot row
+      s.rows = (rmcsa ? P.C : 1) * P.E; s.width = 10 + P.K; s.elem_bytes = 4;
+      s.dim = 1 + 2 * P.N + s.rows * s.width;
+      break;
+    case VIEW_MATRIX_PATHS_OBS:  // (orl_qos_obs.h)
+      s.dim = (int64_t)P.E * P.S * (P.K + 1) + 1;
+      break;
+  }
+  const int64_t per16 = 16 / s.elem_bytes;
+  s.pitch = (s.dim + per16 - 1) / per16 * per16;
+  return s;
+}
+
+// A view's launch.  ok == 0: refused (the rows of the least workgroup the kernel runs in exceed the LDS limit, or a path's
+// modulations its 32-bit word) — everything else is 0 then.  Every view but MatrixObservationWithPaths (one env per wavefront)
+// puts 8 envs on a wavefront.
+struct ViewPlan {
+  bool ok;
+  int waves, block;   // wavefronts and threads per workgroup
+  unsigned grid;
+  size_t lds_bytes;   // dynamic LDS of a workgroup
+  bool staged;        // path features: the wavefront's rows are assembled in LDS (else every lane stores its own blocks)
+  int chunk;          // link features: slot rows per env and round through LDS (a multiple of 8); 0: the rows whole
+  bool counted;       // spectrum assignment: the instantiation with the per-slot occupancy counts
+};
+// W: the batch's row width in 64-bit words; arg: the mask layout, the assignment rule (ORL_ASSIGN_*), the path features' j
+inline ViewPlan view_plan(const orl::DevParams& P, int W, int view, int arg) {
+  ViewPlan r = {};
+  int per_wave = 8;  // envs of a wavefront
+  size_t wave = 0;   // LDS bytes of a wavefront
+  switch (view) {
+    case VIEW_ACTION_MASK:  // 4 wavefronts per workgroup, or refused
+      wave = (size_t)8 * mask_env_words(arg, P.env_type, W, P.K) * sizeof(uint32_t);
+      r.waves = view_waves(wave) < 4 ? 0 : 4;
+      break;
+    case VIEW_RMCSA_MASK:
+      wave = (size_t)8 * rmcsa_mask_env_words(arg, W, P.K, P.C) * sizeof(uint32_t);
+      r.waves = P.M > 32 ? 0 : view_waves(wave);
+      break;
+    case VIEW_COMPLETE:
+      r.waves = 4;
+      break;
+    case VIEW_ASSIGN:  // (the counts of 4 wavefronts fit for every W: orl_assign.h)
+      r.counted = arg == ORL_ASSIGN_MOST_USED || arg == ORL_ASSIGN_LEAST_USED;
+      wave = r.counted ? (size_t)8 * assign_env_dwords(W) * sizeof(uint32_t) : 0;
+      r.waves = r.counted ? view_waves(wave) : 4;
+      break;
+    case VIEW_PATH_FEATURES: {  // staged where a wavefront's 8 rows fit
+      wave = (size_t)8 * view_shape(P, view, arg).pitch * sizeof(float);
+      const int fit = ORL_PATH_OBS_STAGE ? view_waves(wave) : 0;
+      r.staged = fit != 0;
+      r.waves = fit ? fit : 4;
+      if (!fit) wave = 0;
+    } break;
+    // the rows whole where 8 of them fit beside the 8 envs' link sets; else in rounds of `chunk` slot rows per env, the most (a
+    // multiple of 8) that 4, 2 or 1 wavefronts' staging fits
+    case VIEW_LINK_FEATURES: {
+      const ViewShape s = view_shape(P, view, 0);
+      r.waves = view_waves(link_obs_wave_lds(P.K, (int)s.pitch));
+      if (!r.waves) {
+        r.waves = view_waves(link_obs_wave_lds(P.K, 8 * s.width));  // (k = 64: 8 blocks of 74 floats for 8 envs + their link sets = 27 kB, one wavefront)
+        if (r.waves) r.chunk = (int)((kViewLdsDefault / r.waves - link_obs_wave_lds(P.K, 0)) / (8 * s.width * sizeof(float))) / 8 * 8;
+      }
+      wave = link_obs_wave_lds(P.K, r.chunk ? r.chunk * s.width : (int)s.pitch);
+    } break;
+    case VIEW_MATRIX_PATHS_OBS:
+      per_wave = 1;
+      wave = (size_t)qos_obs_wave_lds(P.E, P.K);
+      r.waves = ORL_QOBS_WAVES * wave > kViewLdsMax ? 0 : ORL_QOBS_WAVES;
+      break;
+  }
+  if (!r.waves) return ViewPlan{};
+  r.ok = true;
+  r.block = 64 * r.waves;
+  r.grid = (unsigned)((P.B + per_wave * r.waves - 1) / (per_wave * r.waves));
+  r.lds_bytes = r.waves * wave;
+  return r;
+}

@@ -13,8 +13,27 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 def golden_names(prefix="g"):
     """g* = step traces (gen_golden.py), w* = wrappers / seed / full reset (gen_golden_wrappers.py), v* = seed() on a live env of
-    the other families (gen_golden_seed.py)."""
-    return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, prefix + "*.npz")))
+    the other families (gen_golden_seed.py).  A trace is <letter><number>_<what>.npz: the tables of host decisions beside them
+    (view_plan.npz, run_plan.npz, ...) are no traces."""
+    return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, prefix + "[0-9]*.npz")))
+
+
+VIEW_PLAN_FIELDS = ("dim", "rows", "width", "pitch", "elem_bytes", "ok", "waves", "block", "grid", "lds_bytes", "staged", "chunk", "counted")
+VIEWS = ("action_mask", "rmcsa_mask", "complete", "assign", "path_features", "link_features", "matrix_paths_obs")
+
+
+def view_plan_of(env, view, arg=0):
+    """The shape and launch plan of a view of this batch (include/orl.h, orl_debug_view_plan) as a dict over VIEW_PLAN_FIELDS: what a
+    GPU case asserts so that it keeps reaching the branch of the plan it is there for.  view: a name of VIEWS; arg: the mask
+    layout id, the assignment rule id, the path features' j."""
+    import ctypes
+
+    cfg, d = env._cfg, env._desc
+    out = (ctypes.c_int32 * len(VIEW_PLAN_FIELDS))()
+    n = env.lib.orl_debug_view_plan(cfg.env_type, env.lib.orl_batch_row_words(env._h), env.num_envs, d.n_nodes, d.n_links, d.k_paths,
+                                    cfg.num_spatial_resources, cfg.num_spectrum_resources, max(1, cfg.j), d.n_modulations, VIEWS.index(view), arg, out)
+    assert n == len(VIEW_PLAN_FIELDS)
+    return dict(zip(VIEW_PLAN_FIELDS, out))
 
 
 def load_golden(name):

@@ -120,6 +120,46 @@ def test_rmcsa_rows_equal_the_restatement(name, n_envs):
     env.close()
 
 
+@pytest.fixture(scope="module")
+def topo_dir(tmp_path_factory):
+    return tmp_path_factory.mktemp("link_features_topologies")
+
+
+# The chunked cases above (c7_s65, c31_s64) stage their rounds on 4 wavefronts per workgroup: with 5 paths the link sets are small.
+# The 8 envs' link sets take 128 k bytes and a round of 8 slot rows 256 (10 + k) (csrc/orl_view_plan.h): from k = 26 only 2
+# wavefronts' staging fits 48 KiB, from k = 58 only 1.  k6full (6 nodes, 15 links) with 2 cores: 30 blocks of 10 + k values, chunked.
+@pytest.mark.parametrize("k,waves", [(40, 2), (64, 1)])
+def test_rmcsa_rows_chunked_on_two_and_one_wavefronts(k, waves, topo_dir):
+    import optical_rl_gym_amd as orl
+    from tests import envelope
+    from tests.helpers import view_plan_of
+
+    n, C = 20, 2
+    kw = dict(slot_agent.CASE_BY_NAME["rmcsa_c7_s65"].kw, num_spatial_resources=C)
+    env = orl.make("RMCSA", topology=envelope.topology_npz("k6full", k, topo_dir), num_envs=n, seeds=list(range(700, 700 + n)), **kw)
+    t = env.topology
+    plan = view_plan_of(env, "link_features")
+    assert plan["ok"] == 1 and plan["chunk"] > 0 and plan["chunk"] < plan["rows"] and plan["waves"] == waves, plan
+    busy = 0
+    for point in (0, 25, 50):
+        if point:
+            env.run("SAP_BM_FC_FF", 25)
+        env_type, avail, services = pf.state_of(env)
+        want = np.float32(lf.restate_fast(env_type, avail, services, t, env.link_stats_all()))
+        got = env.link_features()
+        dim, rows, width, pitch = env.link_features_shape()
+        assert (dim, rows, width) == lf.shape_of(t, C) == (1 + 2 * 6 + C * 15 * (10 + k), C * 15, 10 + k) and pitch == (dim + 3) // 4 * 4
+        assert (dim, rows, width, pitch) == tuple(plan[f] for f in ("dim", "rows", "width", "pitch"))
+        assert got.shape == want.shape == (n, dim) and got.dtype == np.float32
+        bad = np.flatnonzero((_u32(got) != _u32(want)).any(axis=1))
+        assert len(bad) == 0, "after %d steps: %d envs differ, first env %d at column %d" % (
+            point, len(bad), bad[0], np.flatnonzero(_u32(got[bad[0]]) != _u32(want[bad[0]]))[0])
+        busy += int((np.asarray(avail) == 0).sum())
+    assert busy > 0  # (rows that are not entirely free)
+    env.check()
+    env.close()
+
+
 @pytest.mark.parametrize("n", [32, 27, 9])
 def test_rows_after_every_way_of_stepping(n):
     case = slot_agent.CASE_BY_NAME["rmsa_s129"]

@@ -136,6 +136,51 @@ def test_mask_equals_restatement_on_every_env(name, n_envs, allow_rejection):
     env.close()
 
 
+@pytest.fixture(scope="module")
+def topo_dir(tmp_path_factory):
+    return tmp_path_factory.mktemp("rmcsa_mask_topologies")
+
+
+# The cases above all launch 4 wavefronts per workgroup (csrc/orl_view_plan.h: what 48 KiB of LDS rows allow).  Path-modulation keeps
+# k + 2 + k C words per env: 64 paths (k6full: 6 nodes, 15 links) with 7 cores leave room for 2 wavefronts, with 11 cores for 1.
+# Core-slot keeps 2 W C + 2 words: 31 cores of 512 slots leave room for 2 (and no accepted shape for fewer).
+@pytest.mark.parametrize("topo,k,C,S,layout,waves", [("k6full", 64, 7, 64, "path_modulation", 2), ("k6full", 64, 11, 64, "path_modulation", 1),
+                                                     ("nsfnet_chen", 5, 31, 512, "core_slot", 2)])
+def test_mask_equals_restatement_on_two_and_one_wavefronts(topo, k, C, S, layout, waves, topo_dir):
+    import optical_rl_gym_amd as orl
+    from tests import envelope
+    from tests.helpers import view_plan_of
+
+    n = 24
+    kw = dict(slot_agent.CASE_BY_NAME["rmcsa_c7_s64"].kw, num_spatial_resources=C, num_spectrum_resources=S)
+    env = orl.make("RMCSA", topology=envelope.topology_npz(topo, k, topo_dir), num_envs=n, seeds=list(range(500, 500 + n)), **kw)
+    plan = view_plan_of(env, "rmcsa_mask", env.MASK_LAYOUTS[layout])
+    assert plan["ok"] == 1 and plan["waves"] == waves and plan["grid"] == -(-n // (8 * waves)), plan
+    tab = rr.tables_of(env)
+    n_mod = len(tab["lmax_xt"])
+    rng = np.random.default_rng(k + C)
+    ones = zeros = 0
+    for point in (0, 30, 60):
+        if point:
+            env.run("SAP_BM_FC_FF", 30)
+        avail, services = _state(env)
+        pv = rr.prov_all(avail, services, env.topology, tab)
+        given = np.stack([rng.integers(-1, k + 1, n), rng.integers(-1, n_mod + 1, n)], axis=1).astype(np.int32)  # (out of range at either end too)
+        for lay in rr.LAYOUTS:
+            g = given if lay == "core_slot" else None
+            got = env.action_mask(lay, given=g)
+            want = rr.restate_rmcsa_fast(None, None, env.topology, tab, lay, given=g, allow_rejection=env.allow_rejection, pv=pv)
+            assert got.shape == want.shape and got.dtype == np.bool_, (point, lay)
+            bad = np.flatnonzero((got != want).any(axis=1))
+            assert len(bad) == 0, "after %d steps, %s: %d envs differ, first %d (given %r)" % (point, lay, len(bad), bad[0], given[bad[0]])
+            if lay == layout:
+                ones += int(got[:, :-1].sum())
+                zeros += int((~got[:, :-1]).sum())
+    assert ones > 0 and zeros > 0
+    env.check()
+    env.close()
+
+
 @pytest.mark.parametrize("allow_rejection", [False, True])
 def test_mask_predicts_the_step_of_every_column(allow_rejection):
     C, S, n = 3, 40, 64

@@ -314,6 +314,9 @@ int orl_host_free(void* p);
                                   * its first call; n_elements = 0 before any call */
 #define ORL_BUF_LINK_FEATURES 10  /* f32 [n_envs][pitch]: rows of the last orl_batch_link_features (pitch, in floats, of
                                   * orl_batch_link_features_shape); allocated by the first call, n_elements = 0 before it */
+#define ORL_BUF_ASSIGN_TABLE 11   /* int32 [n_envs][pitch]: the per-path table of the last orl_batch_route_spectrum, row p at columns
+                                   * 4p .. 4p+3 (pitch of orl_batch_assign_table_shape); allocated by the first call, n_elements = 0
+                                   * before it */
 int orl_batch_device_buffer(orl_batch* b, int which, void** device_ptr, int64_t* n_elements);
 /* The HIP stream (hipStream_t) the batch queues its launches on.  An agent on the same GPU that queues ITS kernels on this
  * stream too (torch: `torch.cuda.ExternalStream(ptr)`) needs no synchronisation between its network and orl_batch_step: the
@@ -538,6 +541,45 @@ int orl_batch_complete_actions(orl_batch* b, int n_given,
 int orl_batch_assign_spectrum(orl_batch* b, int rule, int n_given,
                               const int32_t* given /* host [n_envs] paths, or NULL = column 0 of ORL_BUF_ACTIONS */,
                               int32_t* actions_out /* host [n_envs][4], or NULL */);
+
+/* Routing rules and the per-path assignment table for RMSA and RWA actions: where orl_batch_assign_spectrum settles on the first path
+ * that fits, this call computes the rule's winner on EVERY candidate path, hands the winners out as a table an agent on the GPU can
+ * read (its action set, or features), and reduces them to one action under a routing order.  With n(p), m(p), fits(p), u[w] and U(s)
+ * as defined above — for the pending service of an env and a path p < n_paths[src, dst]: n(p) the slots the service needs on p
+ * (RMSA: under the path's best modulation, RWA: 1); m(p) the AND over the hops of p of the free-slot rows; fits(p) = { s : s + n <= S
+ * and m(p)[s .. s + n - 1] all free }, s = S - n included; u[w] the links of the env's whole slot map with slot w occupied and U(s) =
+ * u[s] + .. + u[s + n - 1] — and free(p) = popcount(m(p)):
+ * The winner of a path with a non-empty fits(p) is (s*(p), c*(p)); c* is an integer cost, smaller is better.
+ *   rule                    s*                                                c*
+ *   ORL_ASSIGN_FIRST_FIT    min fits(p)                                       s*
+ *   ORL_ASSIGN_LAST_FIT     max fits(p)                                       S - n - s*
+ *   ORL_ASSIGN_BEST_FIT     as orl_batch_assign_spectrum                      L - n, L the length of the chosen maximal free run
+ *   ORL_ASSIGN_EXACT_FIT    as orl_batch_assign_spectrum                      0 if a run with L == n exists, else 1 + s*
+ *   ORL_ASSIGN_MOST_USED    as orl_batch_assign_spectrum                      n E - U(s*), E the links of the map
+ *   ORL_ASSIGN_LEAST_USED   as orl_batch_assign_spectrum                      U(s*)
+ *   ORL_ASSIGN_MIN_CUTS     the s of fits(p) with the fewest cuts, ties to    cuts(p, s*)
+ *                           the lowest s
+ * cuts(p, s) = the number of hops l of p with s >= 1, s + n <= S - 1, slot s - 1 free on link l and slot s + n free on link l: the
+ * block then splits a free run of that link in two.  A start at slot 0 or a block ending at slot S - 1 cuts nothing on that side. */
+#define ORL_ASSIGN_MIN_CUTS 6      /* accepted by orl_batch_route_spectrum only */
+/* Routes, all over the paths with a non-empty fits(p): */
+#define ORL_ROUTE_KSP 0            /* the lowest p: orl_batch_assign_spectrum with n_given = 0 */
+#define ORL_ROUTE_BEST 1           /* the smallest c*(p), ties to the lowest p (with ORL_ASSIGN_FIRST_FIT: FF-KSP, the lowest slot over all paths) */
+#define ORL_ROUTE_LEAST_LOADED 2   /* the largest free(p), ties to the lowest p (with ORL_ASSIGN_FIRST_FIT: the reference's
+                                    * least_loaded_path_first_fit, except that s = S - n counts as a fit, as everywhere in these rules) */
+#define ORL_ROUTE_NO_FIT 0x7fffffff
+/* The action is (p, s*(p), 0, 0) in the env's row of ORL_BUF_ACTIONS, where step(NULL) reads it; the reject action (k, S, 0, 0) if no
+ * path fits.  The table is int32 [n_envs][k][4] (ORL_BUF_ASSIGN_TABLE; the device pitch is 4 k): row p is (s*, c*, n(p), free(p));
+ * (S, ORL_ROUTE_NO_FIT, n(p), free(p)) for a path on which nothing fits; (S, ORL_ROUTE_NO_FIT, 0, 0) for p >= n_paths[src, dst].  An
+ * argmin over column 1 is ORL_ROUTE_BEST.
+ * orl_batch_route_spectrum: one launch on the batch's stream; no atomics; with actions_out == NULL and table_out == NULL it does not
+ * synchronise and, after the first call (which allocates the table), allocates nothing: graph-capturable.  With an output pointer the
+ * rows are copied out ([n_envs][4], [n_envs][k][4]) and the call synchronises.  Env state, flags and snapshot bytes do not change.
+ * ORL_E_INVALID, before anything is queued: a family other than RMSA and RWA, a rule outside 0 .. 6, a route outside 0 .. 2.
+ * orl_batch_assign_table_shape: *rows = k, *width = 4 and the device pitch in int32 (4 k) of ORL_BUF_ASSIGN_TABLE's rows. */
+int orl_batch_route_spectrum(orl_batch* b, int rule, int route, int32_t* actions_out /* host [n_envs][4], or NULL */,
+                             int32_t* table_out /* host [n_envs][k][4], or NULL */);
+int orl_batch_assign_table_shape(const orl_batch* b, int32_t* rows, int32_t* width, int32_t* pitch);
 
 /* Snapshot / restore of the complete simulation state of the batch (slot maps, pending releases, RNG, statistics,
  * counters).  The reference has no equivalent (no checkpointing); used for long PPO runs.  The per-env

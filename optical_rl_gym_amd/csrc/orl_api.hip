@@ -136,6 +136,7 @@ __global__ void k_matrix_obs(DevParams P, unsigned char* out) {
 #include "orl_mask.h"
 #include "orl_rmcsa_mask.h"
 #include "orl_assign.h"
+#include "orl_route.h"
 #include "orl_link_obs.h"
 #include "orl_view_plan.h"  // view_shape, view_plan: the shape of each view's rows and the geometry of its launch
 
@@ -1225,6 +1226,10 @@ extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_pt
       *device_ptr = b->qobs_buf;
       *n_elements = b->qobs_buf ? B * view_shape(b->P, VIEW_MATRIX_PATHS_OBS, 0).pitch : 0;
       break;
+    case ORL_BUF_ASSIGN_TABLE:
+      *device_ptr = b->route_table;
+      *n_elements = b->route_table ? B * view_shape(b->P, VIEW_ROUTE, 0).pitch : 0;
+      break;
     default: return fail(ORL_E_INVALID, "unknown buffer %d", which);
   }
   return ORL_OK;
@@ -1355,6 +1360,43 @@ extern "C" int orl_batch_assign_spectrum(orl_batch* b, int rule, int n_given, co
   ORL_LAUNCH(assign_spectrum, b, rule, n_given, src, stride);
   HIPCHK(hipGetLastError());
   return actions_to_host(b, actions_out);
+}
+ORL_ABI_CATCH_INT
+
+// routing rules and the per-path assignment table (orl_route.h)
+static int route_check(const orl_batch* b) {
+  if (b->P.env_type != ENV_RMSA && b->P.env_type != ENV_RWA)
+    return fail(ORL_E_INVALID, "routing rules are defined for RMSA and RWA only (a DeepRMSA action is a block index; RMCSA has orl_batch_complete_actions)");
+  return ORL_OK;
+}
+
+extern "C" int orl_batch_assign_table_shape(const orl_batch* b, int32_t* rows, int32_t* width, int32_t* pitch) try {
+  if (!b || !rows || !width || !pitch) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = route_check(b)) return rc;
+  const ViewShape sh = view_shape(b->P, VIEW_ROUTE, 0);
+  *rows = sh.rows;
+  *width = sh.width;
+  *pitch = (int32_t)sh.pitch;
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+extern "C" int orl_batch_route_spectrum(orl_batch* b, int rule, int route, int32_t* actions_out, int32_t* table_out) try {
+  if (!b) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = route_check(b)) return rc;
+  if (rule < ORL_ASSIGN_FIRST_FIT || rule > ORL_ASSIGN_MIN_CUTS)
+    return fail(ORL_E_INVALID, "unknown spectrum-assignment rule %d (ORL_ASSIGN_* = 0 .. %d)", rule, ORL_ASSIGN_MIN_CUTS);
+  if (route < ORL_ROUTE_KSP || route > ORL_ROUTE_LEAST_LOADED)
+    return fail(ORL_E_INVALID, "unknown route %d (ORL_ROUTE_* = 0 .. %d)", route, ORL_ROUTE_LEAST_LOADED);
+  HIPCHK(hipSetDevice(b->device));
+  const ViewShape sh = view_shape(b->P, VIEW_ROUTE, rule);
+  if (int rc = view_buffer(b, b->route_table, (size_t)(b->P.B * sh.pitch) * sizeof(int32_t), "assignment table")) return rc;
+  ORL_LAUNCH(route_spectrum, b, rule, route, b->route_table);
+  HIPCHK(hipGetLastError());
+  if (table_out) HIPCHK(hipMemcpyAsync(table_out, b->route_table, (size_t)(b->P.B * sh.pitch) * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+  if (actions_out) return actions_to_host(b, actions_out);
+  if (table_out) HIPCHK(hipStreamSynchronize(b->stream));
+  return ORL_OK;
 }
 ORL_ABI_CATCH_INT
 

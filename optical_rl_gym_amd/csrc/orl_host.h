@@ -105,6 +105,8 @@ struct orl_batch {
                                    // ORL_BUF_LINK_FEATURES hands out
   unsigned char* qobs_buf = nullptr;  // MatrixObservationWithPaths (QoSConstrainedRA): [B][pitch] bytes, allocated by the first
                                     // orl_batch_matrix_paths_observation; what ORL_BUF_MATRIX_PATHS_OBS hands out
+  int32_t* route_table = nullptr;  // the per-path assignment table: [B][4 K] int32, allocated by the first orl_batch_route_spectrum; what
+                                   // ORL_BUF_ASSIGN_TABLE hands out
   // orl_batch_copy_envs (as the destination): the pair indices [2][n] on the device and in page-locked memory, grown on demand
   long long* copy_idx = nullptr;
   long long* h_copy_idx = nullptr;
@@ -151,6 +153,8 @@ template <int W> void rmcsa_mask(orl_batch* b, int layout, unsigned char* out, c
 template <int W> void rmcsa_complete(orl_batch* b, int n_given, const int* given, int gstride);
 // k_assign_spectrum: the path of env e at given[e * gstride] (device; n_given == 0: all paths) and its first slot under `rule` into P.actions
 template <int W> void assign_spectrum(orl_batch* b, int rule, int n_given, const int* given, int gstride);
+// k_route_spectrum: every path's winner under `rule` -> table [B][K][4] (device), the action under `route` into P.actions
+template <int W> void route_spectrum(orl_batch* b, int rule, int route, int32_t* table);
 template <int W> void path_features(orl_batch* b, float* out, int j, int mod);  // k_path_features -> out [B][pitch] floats
 template <int W> void link_features(orl_batch* b, float* out);             // k_link_features -> out [B][pitch] floats
 // k_persist in the form `ch` (the run's choice for the whole batch; use_spec: made for the attached specialisation library) over the

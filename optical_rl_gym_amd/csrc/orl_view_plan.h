@@ -3,7 +3,7 @@
 //
 // Like the form choice (orl_persist_form.h) and the run plan (orl_run_plan.h) both are pure functions of the batch's sizes, pinned
 // without a device by tests/test_view_plan.py (orl_debug_view_plan).  No HIP call in here.  Included behind the views' headers
-// (orl_mask.h, orl_rmcsa_mask.h, orl_assign.h, orl_link_obs.h, orl_qos_obs.h), which keep the LDS sizes of one env or wavefront
+// (orl_mask.h, orl_rmcsa_mask.h, orl_assign.h, orl_route.h, orl_link_obs.h, orl_qos_obs.h), which keep the LDS sizes of one env or wavefront
 // next to the kernels that lay them out; orl_kernels.hip and orl_api.hip both see all of them, their kernels only where they are
 // launched.
 #pragma once
@@ -22,6 +22,7 @@ enum ViewKind {
   VIEW_PATH_FEATURES,      // k_path_features; arg: j
   VIEW_LINK_FEATURES,      // k_link_features
   VIEW_MATRIX_PATHS_OBS,   // k_qos_matrix_obs
+  VIEW_ROUTE,              // k_route_spectrum; arg: the rule
   VIEW_COUNT
 };
 
@@ -68,6 +69,10 @@ inline ViewShape view_shape(const orl::DevParams& P, int view, int arg) {
     case VIEW_MATRIX_PATHS_OBS:  // (orl_qos_obs.h)
       s.dim = (int64_t)P.E * P.S * (P.K + 1) + 1;
       break;
+    case VIEW_ROUTE:  // (orl_route.h) the per-path table: a row of (s*, c*, n, free) per path
+      s.rows = P.K; s.width = 4; s.elem_bytes = 4;
+      s.dim = 4 * P.K;
+      break;
   }
   const int64_t per16 = 16 / s.elem_bytes;
   s.pitch = (s.dim + per16 - 1) / per16 * per16;
@@ -86,7 +91,7 @@ struct ViewPlan {
   int chunk;          // link features: slot rows per env and round through LDS (a multiple of 8); 0: the rows whole
   bool counted;       // spectrum assignment: the instantiation with the per-slot occupancy counts
 };
-// W: the batch's row width in 64-bit words; arg: the mask layout, the assignment rule (ORL_ASSIGN_*), the path features' j
+// W: the batch's row width in 64-bit words; arg: the mask layout, the assignment rule (ORL_ASSIGN_*; VIEW_ROUTE too), the path features' j
 inline ViewPlan view_plan(const orl::DevParams& P, int W, int view, int arg) {
   ViewPlan r = {};
   int per_wave = 8;  // envs of a wavefront
@@ -104,6 +109,7 @@ inline ViewPlan view_plan(const orl::DevParams& P, int W, int view, int arg) {
       r.waves = 4;
       break;
     case VIEW_ASSIGN:  // (the counts of 4 wavefronts fit for every W: orl_assign.h)
+    case VIEW_ROUTE:   // (orl_route.h: the same counts for the same rules; ORL_ASSIGN_MIN_CUTS keeps its planes in registers)
       r.counted = arg == ORL_ASSIGN_MOST_USED || arg == ORL_ASSIGN_LEAST_USED;
       wave = r.counted ? (size_t)8 * assign_env_dwords(W) * sizeof(uint32_t) : 0;
       r.waves = r.counted ? view_waves(wave) : 4;

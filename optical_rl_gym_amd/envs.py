@@ -840,6 +840,51 @@ class BatchedOpticalEnv:
                                                     None if out is None else out.ctypes.data))
         return None if out is None else out.copy()
 
+    # ---- routing rules and the per-path assignment table (include/orl.h, orl_batch_route_spectrum): RMSA and RWA ---------------
+    ROUTE_RULES = dict(ASSIGN_RULES, min_cuts=6)
+    ROUTES = {"ksp": 0, "best": 1, "least_loaded": 2}
+
+    @classmethod
+    def route_ids(cls, rule, route):
+        """The (ORL_ASSIGN_*, ORL_ROUTE_*) ids of a rule's and a route's names (ints pass through: an unknown id is the library's to
+        refuse)."""
+        ids = []
+        for what, names, value in (("rule", cls.ROUTE_RULES, rule), ("route", cls.ROUTES, route)):
+            if isinstance(value, str):
+                if value not in names:
+                    raise ValueError("%s must be one of %s, got %r" % (what, ", ".join(map(repr, names)), value))
+                value = names[value]
+            ids.append(int(value))
+        return tuple(ids)
+
+    def assign_table_shape(self):
+        """(rows, width, pitch) of the per-path assignment table: rows = k blocks of width = 4 int32 per env, rows of the device
+        buffer pitch = 4 k int32 apart."""
+        r, w, p = C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self.lib.orl_batch_assign_table_shape(self._h, C.byref(r), C.byref(w), C.byref(p)))
+        return r.value, w.value, p.value
+
+    def route_spectrum(self, rule="first", route="best", fetch=True, table=False):
+        """RMSA / RWA: choose every env's path AND first slot (RWA: wavelength) on the device.  For every candidate path the kernel
+        computes the winner (s*, c*) of `rule` — "first", "last", "best", "exact", "most_used", "least_used" (assign_spectrum's) or
+        "min_cuts" (the start that splits the fewest free runs of the path's links) — c* being the rule's integer cost of that
+        choice (include/orl.h), and `route` picks among the paths that fit: "ksp" the lowest path (assign_spectrum's choice),
+        "best" the smallest c* ("first" + "best" is FF-KSP: the lowest slot over all paths), "least_loaded" the path with the most
+        free slots.  Returns int32 [num_envs, 4] rows (path, slot, 0, 0), left in device_array("actions") for the next step(None);
+        the reject action (k, S) where no path fits.  table=True: (actions, table), table int32 [num_envs, k, 4] with row p =
+        (s*, c*, slots needed on p, free slots of p) — (S, 0x7fffffff, ., .) for a path without a fit, (S, 0x7fffffff, 0, 0) for a
+        path the pair does not have — which stays on the device as device_array("assign_table") ([num_envs, 4 k]).  Env state and
+        flags are not touched.  fetch=False only queues the launch on the batch's stream (returns None; graph-capturable after
+        the first call)."""
+        rid, tid = self.route_ids(rule, route)
+        out = self._act if fetch else None
+        tab = np.empty((self.num_envs, self.k_paths, 4), np.int32) if fetch and table else None
+        self._ck(self.lib.orl_batch_route_spectrum(self._h, rid, tid, None if out is None else out.ctypes.data,
+                                                   None if tab is None else tab.ctypes.data))
+        if out is None:
+            return None
+        return (out.copy(), tab) if table else out.copy()
+
     # ---- MatrixObservationWithPaths (include/orl.h, orl_batch_matrix_paths_observation): QoSConstrainedRA only ---------------
     def matrix_paths_obs_shape(self):
         """(dim, pitch): dim = links * S * (k + 1) + 1 columns per env, rows pitch bytes apart in the device buffer."""
@@ -906,7 +951,7 @@ class BatchedOpticalEnv:
     _BUFFERS = {"actions": (0, "<i4", 4), "reward": (1, "<f8", 0), "done": (2, "|u1", 0), "info": (3, "<f8", -1),
                 "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0), "action_mask": (7, "|b1", None),
                 "matrix_paths_obs": (8, "|u1", None), "path_features": (9, "<f4", None),
-                "link_features": (10, "<f4", None)}
+                "link_features": (10, "<f4", None), "assign_table": (11, "<i4", None)}
     # The views of the pending service: [num_envs, dim] rows of the last call at the device pitch.  name -> (the message while no
     # call has been made, (dim, pitch in items) of those rows, item size).  Every mask layout and every j of the path features has
     # a buffer of its own: a view taken after a "joint" call keeps showing the joint rows (as the last "joint" call left them)
@@ -918,7 +963,9 @@ class BatchedOpticalEnv:
               "path_features": ("no path features yet: call path_features() (fetch=False only queues it) first",
                                 lambda self: self.path_features_shape(self._pf_j)[::2], 4),
               "link_features": ("no link features yet: call link_features() (fetch=False only queues it) first",
-                                lambda self: self.link_features_shape()[::3], 4)}
+                                lambda self: self.link_features_shape()[::3], 4),
+              "assign_table": ("no assignment table yet: call route_spectrum() (fetch=False only queues it) first",
+                               lambda self: (4 * self.assign_table_shape()[0], self.assign_table_shape()[2]), 4)}
 
     def device_array(self, name):
         """The batch's device-resident I/O array `name` as an object with `__cuda_array_interface__` (what

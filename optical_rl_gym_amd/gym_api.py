@@ -358,6 +358,12 @@ class _SpectrumRules:
         paths = None if path is None else np.array([int(path)], np.int32)
         return self._decode(self.batch.assign_spectrum(rule, paths=paths, n_given=0 if path is None else 1)[0])
 
+    def route_spectrum(self, rule="first", route="best"):
+        """The action (path, first slot / wavelength) the routing order `route` — "ksp", "best" or "least_loaded" — picks among
+        every candidate path's winner under `rule` (assign_spectrum's rules and "min_cuts": BatchedOpticalEnv.route_spectrum); the
+        reject action (k, S) when the service fits on no path."""
+        return self._decode(self.batch.route_spectrum(rule, route)[0])
+
 
 class RMSAEnv(_SpectrumRules, _SingleEnv):
     BATCH_CLS = BatchedRMSAEnv

@@ -364,6 +364,16 @@ class MultiDeviceBatch:
         out = self._map(lambda r: self.shards[r].assign_spectrum(rule, paths=self._cut(p, r), n_given=n, fetch=fetch))
         return self._cat(out) if fetch else None
 
+    def route_spectrum(self, rule="first", route="best", fetch=True, table=False):
+        """BatchedOpticalEnv.route_spectrum of every shard; the shards' action rows (and table rows) concatenated."""
+        out = self._map(lambda r: self.shards[r].route_spectrum(rule, route, fetch=fetch, table=table))
+        if not fetch:
+            return None
+        return (self._cat([o[0] for o in out]), self._cat([o[1] for o in out])) if table else self._cat(out)
+
+    def assign_table_shape(self):
+        return self.shards[0].assign_table_shape()
+
     def path_features_shape(self, j=1):
         return self.shards[0].path_features_shape(j)
 

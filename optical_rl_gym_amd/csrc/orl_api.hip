@@ -273,9 +273,9 @@ ORL_ABI_CATCH_INT
 
 extern "C" int orl_topology_create(const orl_topology_desc* d, int device_id, orl_topology** out) try {
   if (!d || !out) return fail(ORL_E_INVALID, "null argument");
-  if (d->n_nodes < 2 || d->n_nodes > 512 || d->n_links < 1 || d->n_links > 128 || d->k_paths < 1 || d->k_paths > 64 ||
-      d->max_hops < 1 || d->max_hops > 30 || d->n_modulations < 1 || d->n_modulations > 255)
-    return fail(ORL_E_INVALID, "topology out of supported range (N<=512, E<=128, k<=64, hops<=30)");
+  if (d->n_nodes < 2 || d->n_nodes > 512 || d->n_links < 1 || d->n_links > ORL_MAX_LINKS || d->k_paths < 1 || d->k_paths > ORL_MAX_PATHS ||
+      d->max_hops < 1 || d->max_hops > ORL_MAX_HOPS || d->n_modulations < 1 || d->n_modulations > 255)
+    return fail(ORL_E_INVALID, "topology out of supported range (N<=512, E<=%d, k<=%d, hops<=%d)", ORL_MAX_LINKS, ORL_MAX_PATHS, ORL_MAX_HOPS);
   if (!d->n_paths || !d->path_hops || !d->path_links || !d->path_length || !d->path_modulation || !d->edge_iter_order)
     return fail(ORL_E_INVALID, "null topology table");
   const int N = d->n_nodes, E = d->n_links, K = d->k_paths, H = d->max_hops, M = d->n_modulations;
@@ -475,7 +475,7 @@ static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int
   if (qos && (c->n_service_classes < 1 || c->n_service_classes > 64 || !c->cum_class || !c->class_reward))
     return fail(ORL_E_INVALID, "QoSConstrainedRA needs 1..64 service classes with their tables");
   const int S = c->num_spectrum_resources, C = c->num_spatial_resources;
-  if (S < 2 || S > 512) return fail(ORL_E_INVALID, "num_spectrum_resources must be in [2, 512]");
+  if (S < 2 || S > ORL_MAX_SLOTS) return fail(ORL_E_INVALID, "num_spectrum_resources must be in [2, %d]", ORL_MAX_SLOTS);
   if (C < 1 || C > 31 || (c->env_type != ORL_ENV_RMCSA && C != 1)) return fail(ORL_E_INVALID, "bad num_spatial_resources");
   if (c->env_type == ORL_ENV_DEEPRMSA && (c->j < 1 || c->j > 8)) return fail(ORL_E_INVALID, "j must be in [1, 8]");
   if (c->n_bit_rates < 1 || c->n_bit_rates > 4096) return fail(ORL_E_INVALID, "bad n_bit_rates");
@@ -487,7 +487,7 @@ static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int
   if (c->bit_rate_mode == 1 && !c->cum_bit_rate) return fail(ORL_E_INVALID, "cum_bit_rate missing");
   if (!no_rates) {
     for (int i = 0; i < c->n_bit_rates * t->M; i++)
-      if (c->n_slots[i] < 1 || c->n_slots[i] > 64) return fail(ORL_E_INVALID, "n_slots entries must be in [1, 64]");
+      if (c->n_slots[i] < 1 || c->n_slots[i] > ORL_MAX_NEED) return fail(ORL_E_INVALID, "n_slots entries must be in [1, %d]", ORL_MAX_NEED);
     for (int i = 0; i < c->n_bit_rates; i++)
       if (c->bit_rates[i] < 0 || c->bit_rates[i] > 32767) return fail(ORL_E_INVALID, "bit rates must be < 32768");
   }
@@ -1199,6 +1199,18 @@ static int stage_given(orl_batch* b, GivenStage& g, const int32_t* given, int ca
   return ORL_OK;
 }
 
+// Where a view's kernel reads its `given` columns: the leading columns of ORL_BUF_ACTIONS themselves (stride 4: where an agent on
+// the GPU writes its choice), or a host `given` of `cols` columns through the call's own stage (orl_host.h)
+static int given_source(orl_batch* b, const int32_t* given, GivenStage& g, int cap_cols, int cols, const char* what, const int*& src, int& stride) {
+  src = b->P.actions;
+  stride = 4;
+  if (!given) return ORL_OK;
+  if (int rc = stage_given(b, g, given, cap_cols, cols, what)) return rc;
+  src = g.dev;
+  stride = cols;
+  return ORL_OK;
+}
+
 extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_ptr, int64_t* n_elements) try {
   if (!b || !device_ptr || !n_elements) return fail(ORL_E_INVALID, "null argument");
   const int64_t B = b->P.B;
@@ -1297,14 +1309,9 @@ extern "C" int orl_batch_action_mask_given(orl_batch* b, int layout, const int32
   unsigned char*& buf = b->mask_buf[layout];  // one buffer per layout: a device view of one layout's rows never sees the other's
   if (int rc = view_buffer(b, buf, (size_t)(b->P.B * sh.pitch), "action mask")) return rc;
   if (rmcsa) {
-    const int* src = b->P.actions;  // columns 0 and 1 of ORL_BUF_ACTIONS: where an agent on the GPU writes its stage-1 choice
-    int stride = 4;
-    if (given) {
-      GivenStage& g = b->given[orl_batch::GIVEN_MASK];
-      if (int rc = stage_given(b, g, given, 2, 2, "action mask")) return rc;
-      src = g.dev;
-      stride = 2;
-    }
+    const int* src;  // (path, modulation): the agent's stage-1 choice
+    int stride;
+    if (int rc = given_source(b, given, b->given[orl_batch::GIVEN_MASK], 2, 2, "action mask", src, stride)) return rc;
     ORL_LAUNCH(rmcsa_mask, b, layout, buf, src, stride);
   } else {
     ORL_LAUNCH(action_mask, b, layout, buf);
@@ -1325,38 +1332,37 @@ extern "C" int orl_batch_complete_actions(orl_batch* b, int n_given, const int32
   if (n_given < 0 || n_given > 3) return fail(ORL_E_INVALID, "n_given = %d outside 0 .. 3 (nothing, path, + modulation, + core)", n_given);
   if (given && n_given == 0) return fail(ORL_E_INVALID, "`given` with n_given == 0: there is no column to read");
   HIPCHK(hipSetDevice(b->device));
-  const int* src = b->P.actions;  // columns 0 .. n_given - 1 of ORL_BUF_ACTIONS: where an agent on the GPU writes its choice
-  int stride = 4;
-  if (given) {
-    GivenStage& g = b->given[orl_batch::GIVEN_COMPLETE];
-    if (int rc = stage_given(b, g, given, 3, n_given, "action completion")) return rc;
-    src = g.dev;
-    stride = n_given;
-  }
+  const int* src;
+  int stride;
+  if (int rc = given_source(b, given, b->given[orl_batch::GIVEN_COMPLETE], 3, n_given, "action completion", src, stride)) return rc;
   ORL_LAUNCH(rmcsa_complete, b, n_given, src, stride);
   HIPCHK(hipGetLastError());
   return actions_to_host(b, actions_out);
 }
 ORL_ABI_CATCH_INT
 
+// spectrum-assignment and routing rules (orl_assign.h, orl_route.h): the families that have them (`what`: the subject of the refusal),
+// and a rule within ORL_ASSIGN_FIRST_FIT .. `last`, the last rule the call accepts
+static int rule_family_check(const orl_batch* b, const char* what) {
+  if (b->P.env_type == ENV_RMSA || b->P.env_type == ENV_RWA) return ORL_OK;
+  return fail(ORL_E_INVALID, "%s defined for RMSA and RWA only (a DeepRMSA action is a block index; RMCSA has orl_batch_complete_actions)", what);
+}
+static int rule_range_check(int rule, int last) {
+  if (rule >= ORL_ASSIGN_FIRST_FIT && rule <= last) return ORL_OK;
+  return fail(ORL_E_INVALID, "unknown spectrum-assignment rule %d (ORL_ASSIGN_* = 0 .. %d)", rule, last);
+}
+
 // spectrum-assignment rules for RMSA / RWA actions (orl_assign.h)
 extern "C" int orl_batch_assign_spectrum(orl_batch* b, int rule, int n_given, const int32_t* given, int32_t* actions_out) try {
   if (!b) return fail(ORL_E_INVALID, "null argument");
-  if (b->P.env_type != ENV_RMSA && b->P.env_type != ENV_RWA)
-    return fail(ORL_E_INVALID, "spectrum assignment is defined for RMSA and RWA only (a DeepRMSA action is a block index; RMCSA has orl_batch_complete_actions)");
-  if (rule < ORL_ASSIGN_FIRST_FIT || rule > ORL_ASSIGN_LEAST_USED)
-    return fail(ORL_E_INVALID, "unknown spectrum-assignment rule %d (ORL_ASSIGN_* = 0 .. %d)", rule, ORL_ASSIGN_LEAST_USED);
+  if (int rc = rule_family_check(b, "spectrum assignment is")) return rc;
+  if (int rc = rule_range_check(rule, ORL_ASSIGN_LEAST_USED)) return rc;
   if (n_given < 0 || n_given > 1) return fail(ORL_E_INVALID, "n_given = %d outside 0 .. 1 (nothing, path)", n_given);
   if (given && n_given == 0) return fail(ORL_E_INVALID, "`given` with n_given == 0: there is no column to read");
   HIPCHK(hipSetDevice(b->device));
-  const int* src = b->P.actions;  // column 0 of ORL_BUF_ACTIONS: where an agent on the GPU writes its path
-  int stride = 4;
-  if (given) {
-    GivenStage& g = b->given[orl_batch::GIVEN_ASSIGN];
-    if (int rc = stage_given(b, g, given, 1, 1, "spectrum assignment")) return rc;
-    src = g.dev;
-    stride = 1;
-  }
+  const int* src;
+  int stride;
+  if (int rc = given_source(b, given, b->given[orl_batch::GIVEN_ASSIGN], 1, 1, "spectrum assignment", src, stride)) return rc;
   ORL_LAUNCH(assign_spectrum, b, rule, n_given, src, stride);
   HIPCHK(hipGetLastError());
   return actions_to_host(b, actions_out);
@@ -1364,15 +1370,9 @@ extern "C" int orl_batch_assign_spectrum(orl_batch* b, int rule, int n_given, co
 ORL_ABI_CATCH_INT
 
 // routing rules and the per-path assignment table (orl_route.h)
-static int route_check(const orl_batch* b) {
-  if (b->P.env_type != ENV_RMSA && b->P.env_type != ENV_RWA)
-    return fail(ORL_E_INVALID, "routing rules are defined for RMSA and RWA only (a DeepRMSA action is a block index; RMCSA has orl_batch_complete_actions)");
-  return ORL_OK;
-}
-
 extern "C" int orl_batch_assign_table_shape(const orl_batch* b, int32_t* rows, int32_t* width, int32_t* pitch) try {
   if (!b || !rows || !width || !pitch) return fail(ORL_E_INVALID, "null argument");
-  if (int rc = route_check(b)) return rc;
+  if (int rc = rule_family_check(b, "routing rules are")) return rc;
   const ViewShape sh = view_shape(b->P, VIEW_ROUTE, 0);
   *rows = sh.rows;
   *width = sh.width;
@@ -1383,9 +1383,8 @@ ORL_ABI_CATCH_INT
 
 extern "C" int orl_batch_route_spectrum(orl_batch* b, int rule, int route, int32_t* actions_out, int32_t* table_out) try {
   if (!b) return fail(ORL_E_INVALID, "null argument");
-  if (int rc = route_check(b)) return rc;
-  if (rule < ORL_ASSIGN_FIRST_FIT || rule > ORL_ASSIGN_MIN_CUTS)
-    return fail(ORL_E_INVALID, "unknown spectrum-assignment rule %d (ORL_ASSIGN_* = 0 .. %d)", rule, ORL_ASSIGN_MIN_CUTS);
+  if (int rc = rule_family_check(b, "routing rules are")) return rc;
+  if (int rc = rule_range_check(rule, ORL_ASSIGN_MIN_CUTS)) return rc;
   if (route < ORL_ROUTE_KSP || route > ORL_ROUTE_LEAST_LOADED)
     return fail(ORL_E_INVALID, "unknown route %d (ORL_ROUTE_* = 0 .. %d)", route, ORL_ROUTE_LEAST_LOADED);
   HIPCHK(hipSetDevice(b->device));

@@ -2302,8 +2302,9 @@ template <int W> void route_spectrum(orl_batch* b, int rule, int route, int32_t*
   const DevParams& VP = b->P;
   const ViewPlan pl = view_plan(VP, W, VIEW_ROUTE, rule);
   int4* out = (int4*)table;
-  if (rule == ORL_ASSIGN_MIN_CUTS) hipLaunchKernelGGL((k_route_spectrum<W, ROUTE_CUTS>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, rule, route, out);
-  else if (pl.counted) hipLaunchKernelGGL((k_route_spectrum<W, ROUTE_COUNTED>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, rule, route, out);
+  const int mode = route_mode_of(rule);
+  if (mode == ROUTE_CUTS) hipLaunchKernelGGL((k_route_spectrum<W, ROUTE_CUTS>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, rule, route, out);
+  else if (mode == ROUTE_COUNTED) hipLaunchKernelGGL((k_route_spectrum<W, ROUTE_COUNTED>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, rule, route, out);
   else hipLaunchKernelGGL((k_route_spectrum<W, ROUTE_PLAIN>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, rule, route, out);
   ORL_TK(b, "k_route_spectrum");
 }

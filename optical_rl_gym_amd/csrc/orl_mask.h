@@ -45,8 +45,8 @@ __global__ void __launch_bounds__(256) k_action_mask(DevParams P, unsigned char*
       Row<W> r = row_mask_lo<W>(0);
       if (p < sv.np) {
         const int pidx = sv.pb + p;
-        const Row<W> m = path_and_rec<W>(path_rec_load(P, pidx), sv.bm, P.E, S, 0);
-        const int n = rwa ? 1 : (int)P.nslots_path[(size_t)pidx * P.n_br + sv.br_idx];
+        const Row<W> m = view_path_row<W>(P, sv.bm, pidx, 0);
+        const int n = view_need(P, sv, pidx, rwa);
         r = row_runs_ge<W>(m, n);  // bit s: slots s .. s + n - 1 free on every hop (bits >= S are 0: s + n <= S)
         if (deep) {
           const int nb = row_popc<W>(row_and<W>(row_starts<W>(m), r));  // maximal free runs of >= n slots

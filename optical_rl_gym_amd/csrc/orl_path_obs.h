@@ -66,8 +66,8 @@ __device__ __forceinline__ void path_obs_env(const DevParams& P, i64 env, int gl
     float* blk = o + 1 + 2 * N + r * WD;
     if (p < np) {
       const int pidx = pb + p;
-      const Row<W> m = path_and_rec<W>(path_rec_load(P, pidx), bm, P.E, S, core);
-      const int n = rwa ? 1 : ((rmcsa && mod >= 0) ? (int)P.nslots[br_idx * P.M + mod] : (int)P.nslots_path[(size_t)pidx * P.n_br + br_idx]);
+      const Row<W> m = view_path_row<W>(P, bm, pidx, core);
+      const int n = (rmcsa && mod >= 0) ? (int)P.nslots[br_idx * P.M + mod] : view_need(P, sv, pidx, rwa);
       path_obs_block<W>(m, n, S, J, blk);
     } else {
       for (int i = 0; i < WD; i++) blk[i] = -1.0f;

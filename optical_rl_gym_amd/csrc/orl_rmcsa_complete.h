@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(256) k_rmcsa_complete(DevParams P, int n_given
   const ViewLanes v = view_lanes();
   if (v.env >= P.B) return;  // (whole groups: the ballot and the exchanges below stay within a group)
   const int lane = v.lane, gl = v.gl;
-  const int K = P.K, S = P.S, M = P.M, C = P.C;
+  const int M = P.M, C = P.C;
   const PendingSvc sv = view_pending(P, v.env);
   const int br_idx = sv.br_idx, np = sv.np, pb = sv.pb;
   const unsigned char* nsl = P.nslots + br_idx * M;
@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(256) k_rmcsa_complete(DevParams P, int n_given
       else mod = rmcsa_best_in_reach(P, nsl, len, br_idx);
       if (mod >= 0) {
         // bit s: s .. s + n - 1 free on every hop (bits >= S of the AND-row are 0, so s + n <= S)
-        const Row<W> r = row_runs_ge<W>(path_and_rec<W>(path_rec_load(P, pb + pth), sv.bm, P.E, S, core), (int)nsl[mod]);
+        const Row<W> r = row_runs_ge<W>(view_path_row<W>(P, sv.bm, pb + pth, core), (int)nsl[mod]);
         if (row_any<W>(r)) slot = row_ctz<W>(r);
       }
     }
@@ -73,9 +73,5 @@ __global__ void __launch_bounds__(256) k_rmcsa_complete(DevParams P, int n_given
       bmod = g8::gget(mod, l, lane);
     }
   }
-  if (gl == 0) {
-    int4 a = make_int4(K, M, C, S);
-    if (best >= 0) a = make_int4(p0 + best / n_c, bmod, c0 + (best - (best / n_c) * n_c), bslot);
-    *(int4*)(P.actions + v.env * 4) = a;
-  }
+  if (gl == 0) view_store_action<true>(P, v.env, best >= 0, make_int4(p0 + best / n_c, bmod, c0 + (best - (best / n_c) * n_c), bslot));
 }

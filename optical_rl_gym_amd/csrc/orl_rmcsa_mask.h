@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(256) k_rmcsa_mask(DevParams P, unsigned char* 
         bool reach = false;
         for (int m = 0; m < M; m++) reach = reach || rmcsa_reach(P, len, m, br_idx);
         int run = 0;
-        if (reach) run = row_longest_run<W>(path_and_rec<W>(path_rec_load(P, pb + pth), bm, P.E, S, core));
+        if (reach) run = row_longest_run<W>(view_path_row<W>(P, bm, pb + pth, core));
         runs[q] = (u32)run;
       }
       wave_fence();

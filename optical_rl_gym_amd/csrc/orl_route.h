@@ -1,5 +1,6 @@
 // orl_route.h — routing rules and the per-path assignment table for RMSA and RWA actions (include/orl.h, orl_batch_route_spectrum);
-// included by orl_kernels.hip behind orl_view.h and orl_assign.h (whose definitions of n(p), m(p), fits(p), u[] and U(s) hold here).
+// included by orl_kernels.hip behind orl_view.h and orl_assign.h, whose n(p), m(p), fits(p), u[], U(s), keys, counts' layout and best /
+// exact fit decision are the ones used here.
 //
 // For EVERY candidate path p of the env's pending service the kernel computes the winner (s*(p), c*(p)) of the launch's rule — the
 // slot orl_batch_assign_spectrum would choose on p, and an integer cost of that choice, smaller = better:
@@ -15,25 +16,35 @@
 //
 // Layout of the work: as k_assign_spectrum — 8 lanes per env, one candidate path per lane, chunks of 8 for k > 8 — but with no
 // early exit: the table needs every path.  The route's running best stays in a register across the chunks, as ONE packed key
-// reduced with g8_min:   key = primary << 16 | p << 10 | s*
-//   s* < S <= 512: 10 bits; p < K <= 64: 6 bits; primary = 0 (KSP), c* (BEST: at most n E <= 64 * 128 = 2^13, 14 bits) or
-//   S - free(p) <= 512 (LEAST_LOADED): 30 bits in all, every key below ORL_ROUTE_NO_FIT = 0x7fffffff, the key of "no fit".
-// Three instantiations, chosen by the launcher from the rule:
+// reduced with g8_min (key_route).  Three instantiations, chosen by the launcher from the rule (route_mode_of):
 //   ROUTE_PLAIN    rules 0 - 3: every lane on its own fits row (assign_runs_key word by word for best / exact fit); no LDS
-//   ROUTE_COUNTED  rules 4, 5: u[] once per group into LDS exactly as k_assign_spectrum<W, true> (same layout, assign_env_dwords),
-//                  then the paths of the chunk that fit in turn: the path's fits row goes word by word to the group's lanes, lane w
-//                  slides the window sum over the set bits of word w, a g8_max over (U, s) gives the path's winner to its lane
+//   ROUTE_COUNTED  rules 4, 5: u[] once per group into LDS, then the paths of the chunk that fit in turn: the path's fits row goes
+//                  word by word to the group's lanes, lane w scans the window over word w, a g8_max gives the path's winner to its lane
 //   ROUTE_CUTS     rule 6, bit-parallel: for hop l with free row f, (f << 1) & (f >> n) has bit s set exactly where a block at s
 //                  cuts link l (bits >= S of f are 0 and nothing is shifted in at bit 0: the slots S and -1 do not exist); the rows
-//                  of the hops add up in 5 bit-sliced planes (a path record holds at most 30 hops < 32), the minimum over the set
-//                  bits of fits(p) is taken plane by plane from the top (cand & ~plane where that is non-empty), its lowest bit is
-//                  s*, and the count is read back from the planes at s*.  5 W 64-bit registers the other rules do not carry.
+//                  of the hops add up in bit-sliced planes, the minimum over the set bits of fits(p) is taken plane by plane from
+//                  the top (cand & ~plane where that is non-empty), its lowest bit is s*, and the count is read back from the
+//                  planes at s*.  5 W 64-bit registers the other rules do not carry.
 // No atomics, no host synchronisation: graph-capturable.  Env state and flags are only read.
 #pragma once
 
 enum { ROUTE_PLAIN = 0, ROUTE_COUNTED = 1, ROUTE_CUTS = 2 };
+__host__ __device__ inline int route_mode_of(int rule) {
+  return rule == ORL_ASSIGN_MIN_CUTS ? ROUTE_CUTS : (assign_rule_counted(rule) ? ROUTE_COUNTED : ROUTE_PLAIN);
+}
 
 #ifdef ORL_W  // (the kernel: the per-W units, orl_kernels.hip)
+// (primary, p, s*) of a path that fits: the smallest key = the route's choice.  primary = 0 (KSP), c* (BEST) or S - free(p)
+// (LEAST_LOADED); every key lies below ORL_ROUTE_NO_FIT, the key of "no fit"
+enum { KEY_PATH_BITS = 6, KEY_PATH_MAX = (1 << KEY_PATH_BITS) - 1, ROUTE_CUT_PLANES = 5 };
+constexpr long long kRoutePrimaryMax = ORL_MAX_NEED * ORL_MAX_LINKS > ORL_MAX_SLOTS ? ORL_MAX_NEED * ORL_MAX_LINKS : ORL_MAX_SLOTS;  // c* <= n E, 1 + s* or S - free <= S
+static_assert(ORL_MAX_PATHS <= KEY_PATH_MAX + 1, "a path does not fit the route key's path field");
+static_assert(((kRoutePrimaryMax << KEY_PATH_BITS | KEY_PATH_MAX) << KEY_SLOT_BITS | KEY_SLOT_MAX) < ORL_ROUTE_NO_FIT, "a route key reaches ORL_ROUTE_NO_FIT");
+static_assert(ORL_MAX_HOPS < (1 << ROUTE_CUT_PLANES), "cuts(p, s) <= hops does not fit the cut planes");
+__device__ __forceinline__ int key_route(int primary, int p, int s) { return (primary << (KEY_PATH_BITS + KEY_SLOT_BITS)) | (p << KEY_SLOT_BITS) | s; }
+__device__ __forceinline__ int key_route_path(int key) { return (key >> KEY_SLOT_BITS) & KEY_PATH_MAX; }
+__device__ __forceinline__ int key_route_slot(int key) { return key & KEY_SLOT_MAX; }
+
 // a >> st, 1 <= st <= 64 (a service of 64 slots shifts by a whole word)
 template <int W> __device__ __forceinline__ Row<W> route_shr(const Row<W>& a, int st) {
   if (st < 64) return row_shr_small<W>(a, st);
@@ -51,18 +62,18 @@ template <int W> __device__ __forceinline__ Row<W> route_shl1(const Row<W>& a) {
 }
 
 // m(p) of the path record, and into pl[j] bit j of cuts(p, s) for every s at once (ROUTE_CUTS)
-template <int W> __device__ __forceinline__ Row<W> route_and_cuts(const PathRec& rec, const u64* bm, int S, int n, Row<W> (&pl)[5]) {
+template <int W> __device__ __forceinline__ Row<W> route_and_cuts(const PathRec& rec, const u64* bm, int S, int n, Row<W> (&pl)[ROUTE_CUT_PLANES]) {
   const Row<W> all = row_mask_lo<W>(S);
   Row<W> m = all;
 #pragma unroll
-  for (int j = 0; j < 5; j++) pl[j] = row_mask_lo<W>(0);
+  for (int j = 0; j < ROUTE_CUT_PLANES; j++) pl[j] = row_mask_lo<W>(0);
   const int hops = path_rec_byte(rec, 0);
   for (int h = 0; h < hops; h++) {
     const Row<W> f = row_and<W>(row_load<W>(bm + path_rec_byte(rec, 2 + h) * W), all);
     m = row_and<W>(m, f);
     Row<W> x = row_and<W>(route_shl1<W>(f), route_shr<W>(f, n));  // bit s: f[s - 1] and f[s + n]
 #pragma unroll
-    for (int j = 0; j < 5; j++) {  // planes += x
+    for (int j = 0; j < ROUTE_CUT_PLANES; j++) {  // planes += x
 #pragma unroll
       for (int i = 0; i < W; i++) {
         const u64 t = pl[j].w[i] & x.w[i];
@@ -75,13 +86,13 @@ template <int W> __device__ __forceinline__ Row<W> route_and_cuts(const PathRec&
 }
 
 // u[] of the env as byte counters in the group's part of LDS (ROUTE_COUNTED): the construction and layout of k_assign_spectrum<W,
-// true> (orl_assign.h) — lane w < W counts the 64 slots of word w over all E link rows in 8 bit-sliced planes and expands them
-// to bytes, slot w at byte (w >> 6) * 68 + (w & 63).  Complete for the group's lanes on return.
+// true> (orl_assign.h, which has it inline; assign_count reads both) — lane w < W counts the 64 slots of word w over all E link
+// rows in bit-sliced planes and expands them to bytes.  Complete for the group's lanes on return.
 template <int W> __device__ __forceinline__ const unsigned char* route_counts(const PendingSvc& sv, int E, const ViewLanes& v) {
   const int gl = v.gl;
-  u64 pl[8];
+  u64 pl[COUNT_PLANES];
 #pragma unroll
-  for (int j = 0; j < 8; j++) pl[j] = 0ull;
+  for (int j = 0; j < COUNT_PLANES; j++) pl[j] = 0ull;
   if (gl < W) {
     const u64* col = sv.bm + gl;
     int e = 0;
@@ -97,11 +108,11 @@ template <int W> __device__ __forceinline__ const unsigned char* route_counts(co
   }
   u32* mine = (u32*)orl_lds_raw + ((size_t)v.wv * 8 + (v.lane >> 3)) * assign_env_dwords(W);
   if (gl < W) {
-    u32* o = mine + 17 * gl;
+    u32* o = mine + ASSIGN_WORD_DWORDS * gl;
     for (int qd = 0; qd < 16; qd++) {
       u32 acc = 0u;
 #pragma unroll
-      for (int j = 0; j < 8; j++) acc += view_nibble_bytes((u32)(pl[j] >> (4 * qd)) & 15u) << j;
+      for (int j = 0; j < COUNT_PLANES; j++) acc += view_nibble_bytes((u32)(pl[j] >> (4 * qd)) & 15u) << j;
       o[qd] = acc;
     }
   }
@@ -125,10 +136,10 @@ __global__ void __launch_bounds__(256) k_route_spectrum(DevParams P, int rule, i
     const int q = base + gl;
     Row<W> r = row_mask_lo<W>(0);  // fits(q)
     int n = 0, nfree = 0, slot = S, cost = ORL_ROUTE_NO_FIT;
-    Row<W> pl[MODE == ROUTE_CUTS ? 5 : 1];
+    Row<W> pl[MODE == ROUTE_CUTS ? ROUTE_CUT_PLANES : 1];
     if (q < np) {
       const int pidx = sv.pb + q;
-      n = rwa ? 1 : (int)P.nslots_path[(size_t)pidx * P.n_br + sv.br_idx];
+      n = view_need(P, sv, pidx, rwa);
       const PathRec rec = path_rec_load(P, pidx);
       Row<W> m;
       if constexpr (MODE == ROUTE_CUTS) m = route_and_cuts<W>(rec, sv.bm, S, n, pl);
@@ -146,21 +157,14 @@ __global__ void __launch_bounds__(256) k_route_spectrum(DevParams P, int rule, i
           slot = row_bitlen<W>(r) - 1;
           cost = S - n - slot;
         } else {
-          // the shortest run of the lane's own row (ties: the lowest start): (L - n) << 10 | start over the runs of every word
-          int key = 0x7fffffff;
+          // the shortest run of the lane's own row (ties: the lowest start), over the runs of every word
+          int key = KEY_NO_RUN;
 #pragma unroll
           for (int i = 0; i < W; i++) {
             const int k = assign_runs_key<W>(r, i);
             key = k < key ? k : key;
           }
-          const int over = key >> 10;
-          if (rule == ORL_ASSIGN_BEST_FIT || over == 0) {
-            slot = key & 1023;
-            cost = over;
-          } else {  // EXACT_FIT without a run of exactly n slots: first fit
-            slot = row_ctz<W>(r);
-            cost = 1 + slot;
-          }
+          assign_run_choice<W>(rule, key, r, slot, cost);
         }
       }
     } else if constexpr (MODE == ROUTE_COUNTED) {
@@ -180,21 +184,20 @@ __global__ void __launch_bounds__(256) k_route_spectrum(DevParams P, int rule, i
         if (fw) {
           const int lo = 64 * gl + (int)__builtin_ctzll(fw), hi = 64 * gl + 63 - (int)__builtin_clzll(fw);
           int U = 0;
-          for (int w = lo; w < lo + nl; w++) U += (int)u[(w >> 6) * 68 + (w & 63)];
+          for (int w = lo; w < lo + nl; w++) U += assign_count(u, w);
           for (int s = lo;; s++) {
             if ((fw >> (s & 63)) & 1ull) {
-              // U <= 64 * 128 < 2^14, s < 2^10: the largest key = the best U, then the lowest s
-              const int k = ((rule == ORL_ASSIGN_MOST_USED ? U : 16383 - U) << 10) | (1023 - s);
+              const int k = key_sum(rule, U, s);
               key = k > key ? k : key;
             }
             if (s == hi) break;
-            U += (int)u[((s + nl) >> 6) * 68 + ((s + nl) & 63)] - (int)u[(s >> 6) * 68 + (s & 63)];  // (s + nl <= hi + nl - 1 < S)
+            U += assign_count(u, s + nl) - assign_count(u, s);  // (s + nl <= hi + nl - 1 < S)
           }
         }
         key = g8_max(key);
         if (gl == l) {
-          const int U = rule == ORL_ASSIGN_MOST_USED ? (key >> 10) : 16383 - (key >> 10);
-          slot = 1023 - (key & 1023);
+          const int U = key_sum_U(rule, key);
+          slot = key_sum_slot(key);
           cost = rule == ORL_ASSIGN_MOST_USED ? n * E - U : U;
         }
       }
@@ -202,14 +205,14 @@ __global__ void __launch_bounds__(256) k_route_spectrum(DevParams P, int rule, i
       if (row_any<W>(r)) {
         Row<W> cand = r;
 #pragma unroll
-        for (int j = 4; j >= 0; j--) {
+        for (int j = ROUTE_CUT_PLANES - 1; j >= 0; j--) {
           const Row<W> t = row_andn<W>(cand, pl[j]);
           if (row_any<W>(t)) cand = t;
         }
         slot = row_ctz<W>(cand);
         cost = 0;
 #pragma unroll
-        for (int j = 0; j < 5; j++) {
+        for (int j = 0; j < ROUTE_CUT_PLANES; j++) {  // cuts(q, slot) back from the planes
           u64 x = 0ull;
 #pragma unroll
           for (int i = 0; i < W; i++)
@@ -220,17 +223,10 @@ __global__ void __launch_bounds__(256) k_route_spectrum(DevParams P, int rule, i
     }
     if (q < K) table[v.env * K + q] = make_int4(slot, cost, n, nfree);
     int key = ORL_ROUTE_NO_FIT;
-    if (cost != ORL_ROUTE_NO_FIT) {
-      const int primary = route == ORL_ROUTE_KSP ? 0 : (route == ORL_ROUTE_BEST ? cost : S - nfree);
-      key = (primary << 16) | (q << 10) | slot;
-    }
+    if (cost != ORL_ROUTE_NO_FIT) key = key_route(route == ORL_ROUTE_KSP ? 0 : (route == ORL_ROUTE_BEST ? cost : S - nfree), q, slot);
     key = g8_min(key);
     best = key < best ? key : best;
   }
-  if (gl == 0) {
-    int4 a = make_int4(K, S, 0, 0);
-    if (best != ORL_ROUTE_NO_FIT) a = make_int4((best >> 10) & 63, best & 1023, 0, 0);
-    *(int4*)(P.actions + v.env * 4) = a;
-  }
+  if (gl == 0) view_store_action<false>(P, v.env, best != ORL_ROUTE_NO_FIT, make_int4(key_route_path(best), key_route_slot(best), 0, 0));
 }
 #endif

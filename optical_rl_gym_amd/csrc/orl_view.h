@@ -4,6 +4,9 @@
 //   view_bits16_bytes  a 16-bit field -> 16 bytes of 0/1, one 16-byte store's worth (every byte view)
 //   view_lanes         the opening of an 8-lanes-per-env kernel: 8 envs per wavefront, blockDim / 64 wavefronts per workgroup
 //   view_pending       the pending service of an env, decoded from its scalar record
+//   view_need          the slots the pending service needs on a path
+//   view_path_row      the AND-row of a path's links, from its record
+//   view_store_action  an env's row of ORL_BUF_ACTIONS, or its family's reject row, as one 16-byte store
 //   view_obs_header    the float32 header of the feature rows (orl_path_obs.h, orl_link_obs.h) and their pad columns
 //   view_store_rows    a wavefront's 8 envs' bit rows in LDS -> their output rows of 0/1 bytes, as 16-byte stores
 // (The host side of the views — row shapes, launch geometry, the LDS budget rule view_waves — is orl_view_plan.h.  orl_device.h has no decode of the scalar record short of the whole Env; k_policy reads the svc_desc word instead.)
@@ -45,6 +48,22 @@ __device__ __forceinline__ PendingSvc view_pending(const DevParams& P, i64 env) 
   s.pb = (s.src * P.N + s.dst) * P.K;
   s.bm = P.bitmap + env * P.bm_words;
   return s;
+}
+
+// slots the pending service needs on path pidx (an index into the path tables: sv.pb + p) at its best modulation; RWA: one wavelength
+__device__ __forceinline__ int view_need(const DevParams& P, const PendingSvc& sv, int pidx, bool rwa) {
+  return rwa ? 1 : (int)P.nslots_path[(size_t)pidx * P.n_br + sv.br_idx];
+}
+// m(pidx): the AND of the path's link rows in `core` of the slot maps bm, bits >= S clear
+template <int W> __device__ __forceinline__ Row<W> view_path_row(const DevParams& P, const u64* bm, int pidx, int core) {
+  return path_and_rec<W>(path_rec_load(P, pidx), bm, P.E, P.S, core);
+}
+// env's row of ORL_BUF_ACTIONS, by one lane: `row` if found, else the reject action of the kernel's family — RMCSA (K, M, C, S), the
+// others (K, S, 0, 0); each caller serves one of the two, so the family is the caller's constant
+template <bool RMCSA> __device__ __forceinline__ void view_store_action(const DevParams& P, i64 env, bool found, int4 row) {
+  int4 a = RMCSA ? make_int4(P.K, P.M, P.C, P.S) : make_int4(P.K, P.S, 0, 0);
+  if (found) a = row;
+  *(int4*)(P.actions + env * 4) = a;
 }
 
 // The header of a feature row o (LDS or global) of dim columns at a pitch of `pitch`, by the env group's 8 lanes: bit_rate / 100 (RWA:

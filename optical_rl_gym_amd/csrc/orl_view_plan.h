@@ -110,7 +110,7 @@ inline ViewPlan view_plan(const orl::DevParams& P, int W, int view, int arg) {
       break;
     case VIEW_ASSIGN:  // (the counts of 4 wavefronts fit for every W: orl_assign.h)
     case VIEW_ROUTE:   // (orl_route.h: the same counts for the same rules; ORL_ASSIGN_MIN_CUTS keeps its planes in registers)
-      r.counted = arg == ORL_ASSIGN_MOST_USED || arg == ORL_ASSIGN_LEAST_USED;
+      r.counted = assign_rule_counted(arg);
       wave = r.counted ? (size_t)8 * assign_env_dwords(W) * sizeof(uint32_t) : 0;
       r.waves = r.counted ? view_waves(wave) : 4;
       break;

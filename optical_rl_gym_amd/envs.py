@@ -805,14 +805,19 @@ class BatchedOpticalEnv:
     # ---- spectrum-assignment rules for RMSA / RWA actions (include/orl.h, orl_batch_assign_spectrum) ---------------------------
     ASSIGN_RULES = {"first": 0, "last": 1, "best": 2, "exact": 3, "most_used": 4, "least_used": 5}
 
+    @staticmethod
+    def _named_id(what, names, value):
+        """The id of a name out of `names` (an int passes through: an unknown id is the library's to refuse)."""
+        if isinstance(value, str):
+            if value not in names:
+                raise ValueError("%s must be one of %s, got %r" % (what, ", ".join(map(repr, names)), value))
+            return names[value]
+        return int(value)
+
     @classmethod
     def assignment_rule(cls, rule):
         """The ORL_ASSIGN_* id of a rule's name (an int passes through: an unknown id is the library's to refuse)."""
-        if isinstance(rule, str):
-            if rule not in cls.ASSIGN_RULES:
-                raise ValueError("rule must be one of %s, got %r" % (", ".join(map(repr, cls.ASSIGN_RULES)), rule))
-            return cls.ASSIGN_RULES[rule]
-        return int(rule)
+        return cls._named_id("rule", cls.ASSIGN_RULES, rule)
 
     @staticmethod
     def assignment_paths(paths, n_given, num_envs):
@@ -848,14 +853,7 @@ class BatchedOpticalEnv:
     def route_ids(cls, rule, route):
         """The (ORL_ASSIGN_*, ORL_ROUTE_*) ids of a rule's and a route's names (ints pass through: an unknown id is the library's to
         refuse)."""
-        ids = []
-        for what, names, value in (("rule", cls.ROUTE_RULES, rule), ("route", cls.ROUTES, route)):
-            if isinstance(value, str):
-                if value not in names:
-                    raise ValueError("%s must be one of %s, got %r" % (what, ", ".join(map(repr, names)), value))
-                value = names[value]
-            ids.append(int(value))
-        return tuple(ids)
+        return cls._named_id("rule", cls.ROUTE_RULES, rule), cls._named_id("route", cls.ROUTES, route)
 
     def assign_table_shape(self):
         """(rows, width, pitch) of the per-path assignment table: rows = k blocks of width = 4 int32 per env, rows of the device

@@ -317,6 +317,9 @@ int orl_host_free(void* p);
 #define ORL_BUF_ASSIGN_TABLE 11   /* int32 [n_envs][pitch]: the per-path table of the last orl_batch_route_spectrum, row p at columns
                                    * 4p .. 4p+3 (pitch of orl_batch_assign_table_shape); allocated by the first call, n_elements = 0
                                    * before it */
+#define ORL_BUF_CORE_TABLE 12     /* int32 [n_envs][pitch]: RMCSA's (path, core) table of the last orl_batch_route_cores, row p C + c at
+                                   * columns 4 (p C + c) .. + 3 (pitch of orl_batch_core_table_shape); allocated by the first call,
+                                   * n_elements = 0 before it */
 int orl_batch_device_buffer(orl_batch* b, int which, void** device_ptr, int64_t* n_elements);
 /* The HIP stream (hipStream_t) the batch queues its launches on.  An agent on the same GPU that queues ITS kernels on this
  * stream too (torch: `torch.cuda.ExternalStream(ptr)`) needs no synchronisation between its network and orl_batch_step: the
@@ -581,6 +584,54 @@ int orl_batch_route_spectrum(orl_batch* b, int rule, int route, int32_t* actions
                              int32_t* table_out /* host [n_envs][k][4], or NULL */);
 int orl_batch_assign_table_shape(const orl_batch* b, int32_t* rows, int32_t* width, int32_t* pitch);
 
+/* Core and spectrum rules with a (path, core) table for RMCSA actions: what orl_batch_route_spectrum is to the single-core families.
+ * orl_batch_complete_actions is first fit in (path, core, slot) order; this call computes a rule's winner on EVERY (path, core) pair,
+ * hands the winners out as a table an agent on the GPU can read, and reduces them to one action (path, modulation, core, first slot)
+ * under a route — first-fit core, least-loaded core, best fit over the cores, the pair that fragments least.  For the pending service of
+ * an env and every candidate pair (p, c), p < n_paths[src, dst] and c < C:
+ *   m(p)       modulation = -1: m*(p) of orl_batch_complete_actions — among the modulations within both reach limits for p at this bit
+ *              rate the one that needs the fewest slots, ties to the lowest index; modulation = m in [0, M): m for every path, usable
+ *              on p only where it is within both reach limits (the convention of orl_batch_path_features).  A path without an m(p)
+ *              cannot be used;
+ *   n(p)       = nslots[br_idx][m(p)];
+ *   row(p, c)  the AND over the hops of p of the free-slot rows of core c, slots 0 .. S - 1; free(p, c) = its popcount;
+ *   fits(p, c) = { s : s + n <= S and row(p, c)[s .. s + n - 1] all free }, s = S - n included: the s at which stepping
+ *              (p, m(p), c, s) provisions.
+ * The winner (s*, c*) of a pair with a non-empty fits(p, c), c* an integer cost (smaller is better), is that of
+ * orl_batch_route_spectrum's table above for ORL_ASSIGN_FIRST_FIT, ORL_ASSIGN_LAST_FIT, ORL_ASSIGN_BEST_FIT, ORL_ASSIGN_EXACT_FIT and
+ * ORL_ASSIGN_MIN_CUTS with row(p, c) for m(p) and fits(p, c) for fits(p); the maximal free runs are those of row(p, c), and cuts(p, s)
+ * counts the hops of p in core c.  ORL_ASSIGN_MOST_USED and ORL_ASSIGN_LEAST_USED are refused: an occupancy count over the C E rows
+ * of all cores does not fit the byte counters those rules are built on.
+ * Prefix: n_given = 0 — every pair is a candidate; 1 — the pairs of the env's given path; 2 — the env's given (path, core) pair alone.
+ * A given column out of range (negative ones included) leaves no candidate.  The route picks among the candidate pairs with a
+ * non-empty fits(p, c); ORL_ROUTE_KSP, ORL_ROUTE_BEST and ORL_ROUTE_LEAST_LOADED read over pairs in path-major order:
+ *   ORL_ROUTE_KSP                    the lowest (p, c): the first path, then the first core, with a fit
+ *   ORL_ROUTE_BEST                   the smallest c*, ties to the lowest (p, c)
+ *   ORL_ROUTE_LEAST_LOADED           the largest free(p, c), ties to the lowest (p, c) */
+#define ORL_ROUTE_KSP_BEST_CORE 3          /* the first path with any fit; among its cores the smallest c*, ties to the lowest core */
+#define ORL_ROUTE_KSP_LEAST_LOADED_CORE 4  /* the first path with any fit; among its cores the largest free(p, c), ties to the lowest core */
+/* (routes 3 and 4 are this call's only: orl_batch_route_spectrum refuses them.)  The action is (p, m(p), c, s*) in the env's row of
+ * ORL_BUF_ACTIONS, where step(NULL) reads it; the reject action (k, M, C, S) if no candidate pair fits.  ORL_ASSIGN_FIRST_FIT with
+ * ORL_ROUTE_KSP and modulation = -1 is orl_batch_complete_actions with the same n_given <= 1.
+ * The table is int32 [n_envs][k C][4] (ORL_BUF_CORE_TABLE; the device pitch is 4 k C), row p C + c — the row order of
+ * orl_batch_path_features — = (s*, c*, n(p), free(p, c)); (S, ORL_ROUTE_NO_FIT, n(p), free(p, c)) for a pair on which nothing fits;
+ * (S, ORL_ROUTE_NO_FIT, 0, 0) for a path the service cannot use: p >= n_paths[src, dst], no modulation within reach, the fixed
+ * modulation beyond reach.  The table is always complete, whatever the prefix.
+ * orl_batch_route_cores: one launch on the batch's stream; no atomics.  given == NULL: the path is column 0 and the core column 2 of
+ * ORL_BUF_ACTIONS — where they live in an action, so an agent on the GPU writes them there and the kernel fills in the modulation and
+ * the slot; with actions_out == NULL and table_out == NULL as well the call does not synchronise and, after the first call (which
+ * allocates the table), allocates nothing: graph-capturable.  A host `given` [n_envs][n_given] int32 — (path) or (path, core) — goes
+ * through a page-locked buffer of the batch into a device buffer of the batch (both allocated by the first such call, this call's
+ * own), asynchronously on the batch's stream; ORL_BUF_ACTIONS is then written by the kernel only.  With an output pointer the rows
+ * are copied out ([n_envs][4], [n_envs][k C][4]) and the call synchronises.  Env state, flags and snapshot bytes do not change.
+ * ORL_E_INVALID, before anything is queued or allocated: a family other than RMCSA, a rule outside 0 .. 3 and 6, a route outside
+ * 0 .. 4, a modulation outside -1 .. M - 1, n_given outside 0 .. 2, given != NULL with n_given == 0.
+ * orl_batch_core_table_shape: *rows = k C, *width = 4 and the device pitch in int32 (4 k C) of ORL_BUF_CORE_TABLE's rows. */
+int orl_batch_route_cores(orl_batch* b, int rule, int route, int modulation /* -1: each path's best */, int n_given,
+                          const int32_t* given /* host [n_envs][n_given], or NULL = columns 0 and 2 of ORL_BUF_ACTIONS */,
+                          int32_t* actions_out /* host [n_envs][4], or NULL */, int32_t* table_out /* host [n_envs][k C][4], or NULL */);
+int orl_batch_core_table_shape(const orl_batch* b, int32_t* rows, int32_t* width, int32_t* pitch);
+
 /* Snapshot / restore of the complete simulation state of the batch (slot maps, pending releases, RNG, statistics,
  * counters).  The reference has no equivalent (no checkpointing); used for long PPO runs.  The per-env
  * rates (orl_batch_set_rates) are configuration and not part of it. */
@@ -674,7 +725,7 @@ int orl_debug_run_plan(const orl_env_config* cfg, const orl_topology_desc* topo,
 /* The shape of a per-step view's rows and the geometry of its launch (csrc/orl_view_plan.h) without a device or a configuration
  * (tests/test_view_plan.py), from raw sizes: the env family, the row width W in 64-bit words (1, 2, 5 or 8), the batch B and the
  * sizes N, E, K, C, S, J, M of a batch, all >= 1.  view: 0 action mask, 1 RMCSA mask, 2 action completion, 3 spectrum assignment,
- * 4 path features, 5 link features, 6 MatrixObservationWithPaths; arg: the mask layout (ORL_MASK_*), the rule (ORL_ASSIGN_*), the
+ * 4 path features, 5 link features, 6 MatrixObservationWithPaths, 7 routing rules, 8 core and spectrum rules (RMCSA only); arg: the mask layout (ORL_MASK_*), the rule (ORL_ASSIGN_*), the
  * path features' j.  out[0..4] = row length (0: the family has no such layout), blocks per row, values per block, device pitch in
  * elements, bytes per element; out[5..12] = accepted (0: the call refuses the shape, the rest 0), wavefronts and threads per
  * workgroup, grid, dynamic LDS bytes, path features staged in LDS, link features' slot rows per round (0: whole rows), assignment

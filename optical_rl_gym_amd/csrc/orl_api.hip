@@ -137,6 +137,7 @@ __global__ void k_matrix_obs(DevParams P, unsigned char* out) {
 #include "orl_rmcsa_mask.h"
 #include "orl_assign.h"
 #include "orl_route.h"
+#include "orl_route_cores.h"
 #include "orl_link_obs.h"
 #include "orl_view_plan.h"  // view_shape, view_plan: the shape of each view's rows and the geometry of its launch
 
@@ -476,7 +477,7 @@ static int batch_create_impl(const orl_env_config* c, const orl_topology* t, int
     return fail(ORL_E_INVALID, "QoSConstrainedRA needs 1..64 service classes with their tables");
   const int S = c->num_spectrum_resources, C = c->num_spatial_resources;
   if (S < 2 || S > ORL_MAX_SLOTS) return fail(ORL_E_INVALID, "num_spectrum_resources must be in [2, %d]", ORL_MAX_SLOTS);
-  if (C < 1 || C > 31 || (c->env_type != ORL_ENV_RMCSA && C != 1)) return fail(ORL_E_INVALID, "bad num_spatial_resources");
+  if (C < 1 || C > ORL_MAX_CORES || (c->env_type != ORL_ENV_RMCSA && C != 1)) return fail(ORL_E_INVALID, "bad num_spatial_resources");
   if (c->env_type == ORL_ENV_DEEPRMSA && (c->j < 1 || c->j > 8)) return fail(ORL_E_INVALID, "j must be in [1, 8]");
   if (c->n_bit_rates < 1 || c->n_bit_rates > 4096) return fail(ORL_E_INVALID, "bad n_bit_rates");
   if (c->episode_length < 1) return fail(ORL_E_INVALID, "episode_length must be positive");
@@ -1242,6 +1243,10 @@ extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_pt
       *device_ptr = b->route_table;
       *n_elements = b->route_table ? B * view_shape(b->P, VIEW_ROUTE, 0).pitch : 0;
       break;
+    case ORL_BUF_CORE_TABLE:
+      *device_ptr = b->core_table;
+      *n_elements = b->core_table ? B * view_shape(b->P, VIEW_ROUTE_CORES, 0).pitch : 0;
+      break;
     default: return fail(ORL_E_INVALID, "unknown buffer %d", which);
   }
   return ORL_OK;
@@ -1393,6 +1398,52 @@ extern "C" int orl_batch_route_spectrum(orl_batch* b, int rule, int route, int32
   ORL_LAUNCH(route_spectrum, b, rule, route, b->route_table);
   HIPCHK(hipGetLastError());
   if (table_out) HIPCHK(hipMemcpyAsync(table_out, b->route_table, (size_t)(b->P.B * sh.pitch) * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+  if (actions_out) return actions_to_host(b, actions_out);
+  if (table_out) HIPCHK(hipStreamSynchronize(b->stream));
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+// core and spectrum rules and the (path, core) table of RMCSA (orl_route_cores.h)
+static int route_cores_family_check(const orl_batch* b) {
+  if (b->P.env_type == ENV_RMCSA) return ORL_OK;
+  return fail(ORL_E_INVALID, "core and spectrum rules are defined for RMCSA only (RMSA and RWA have orl_batch_route_spectrum)");
+}
+
+extern "C" int orl_batch_core_table_shape(const orl_batch* b, int32_t* rows, int32_t* width, int32_t* pitch) try {
+  if (!b || !rows || !width || !pitch) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = route_cores_family_check(b)) return rc;
+  const ViewShape sh = view_shape(b->P, VIEW_ROUTE_CORES, 0);
+  *rows = sh.rows;
+  *width = sh.width;
+  *pitch = (int32_t)sh.pitch;
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+extern "C" int orl_batch_route_cores(orl_batch* b, int rule, int route, int modulation, int n_given, const int32_t* given, int32_t* actions_out,
+                                     int32_t* table_out) try {
+  if (!b) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = route_cores_family_check(b)) return rc;
+  if (assign_rule_counted(rule))
+    return fail(ORL_E_INVALID, "ORL_ASSIGN_MOST_USED and ORL_ASSIGN_LEAST_USED have no (path, core) form: an occupancy count over cores x links = %d rows "
+                "does not fit the rules' byte counters (rules 0 .. 3 and ORL_ASSIGN_MIN_CUTS)", b->P.C * b->P.E);
+  if (int rc = rule_range_check(rule, ORL_ASSIGN_MIN_CUTS)) return rc;
+  if (route < ORL_ROUTE_KSP || route > ORL_ROUTE_KSP_LEAST_LOADED_CORE)
+    return fail(ORL_E_INVALID, "unknown route %d (ORL_ROUTE_* = 0 .. %d)", route, ORL_ROUTE_KSP_LEAST_LOADED_CORE);
+  if (modulation < -1 || modulation >= b->P.M) return fail(ORL_E_INVALID, "modulation %d outside -1 (each path's best) .. %d", modulation, b->P.M - 1);
+  if (n_given < 0 || n_given > 2) return fail(ORL_E_INVALID, "n_given = %d outside 0 .. 2 (nothing, path, + core)", n_given);
+  if (given && n_given == 0) return fail(ORL_E_INVALID, "`given` with n_given == 0: there is no column to read");
+  HIPCHK(hipSetDevice(b->device));
+  const ViewShape sh = view_shape(b->P, VIEW_ROUTE_CORES, rule);
+  const size_t bytes = (size_t)(b->P.B * sh.pitch) * sizeof(int32_t);
+  if (int rc = view_buffer(b, b->core_table, bytes, "(path, core) table")) return rc;
+  const int* src;
+  int stride;
+  if (int rc = given_source(b, given, b->given[orl_batch::GIVEN_ROUTE_CORES], 2, n_given, "core and spectrum rules", src, stride)) return rc;
+  ORL_LAUNCH(route_cores, b, rule, route, modulation, n_given, src, stride, given ? 1 : 2, b->core_table);  // (the core: column 2 of an action row)
+  HIPCHK(hipGetLastError());
+  if (table_out) HIPCHK(hipMemcpyAsync(table_out, b->core_table, bytes, hipMemcpyDeviceToHost, b->stream));
   if (actions_out) return actions_to_host(b, actions_out);
   if (table_out) HIPCHK(hipStreamSynchronize(b->stream));
   return ORL_OK;
@@ -2096,6 +2147,7 @@ extern "C" int orl_debug_view_plan(int env_type, int W, int64_t B, int N, int E,
   if (!out || env_type < 0 || env_type > ORL_ENV_QOS || (W != 1 && W != 2 && W != 5 && W != 8) || B < 1 || N < 1 || E < 1 || K < 1 || C < 1 || S < 1 ||
       J < 1 || M < 1 || view < 0 || view >= VIEW_COUNT)
     return 0;
+  if (view == VIEW_ROUTE_CORES && env_type != ORL_ENV_RMCSA) return 0;  // (no batch of another family has this view)
   DevParams P;
   memset(&P, 0, sizeof P);
   P.env_type = env_type; P.B = B; P.N = N; P.E = E; P.K = K; P.C = C; P.S = S; P.J = J; P.M = M;

@@ -43,7 +43,7 @@ enum { POL_SP_FF = 0, POL_SAP_FF = 1, POL_LLP_FF = 2, POL_SAP_LF = 3,
        POL_PATH_FF = 4 };  // PathOnlyFirstFitAction (rmsa_env.py:840-874, rwa_env.py:505-536): first fit on the path the agent chose
 // The accepted configuration range: orl_topology_create and batch_create_impl (orl_api.hip) refuse what lies beyond, and the packed
 // keys and bit-sliced counters of the views (orl_assign.h, orl_route.h) static_assert their field widths against it
-enum { ORL_MAX_LINKS = 128, ORL_MAX_PATHS = 64, ORL_MAX_HOPS = 30, ORL_MAX_SLOTS = 512, ORL_MAX_NEED = 64 /* slots of one service */ };
+enum { ORL_MAX_LINKS = 128, ORL_MAX_PATHS = 64, ORL_MAX_HOPS = 30, ORL_MAX_SLOTS = 512, ORL_MAX_NEED = 64 /* slots of one service */, ORL_MAX_CORES = 31 };
 
 // scalar-record slots (one 8-byte word each; 32 per env = one 256-B line, lane l owns word l)
 enum {

@@ -93,9 +93,9 @@ struct orl_batch {
   unsigned char* mask_buf[4] = {nullptr, nullptr, nullptr, nullptr};  // action masks per layout (ORL_MASK_*): [B][pitch] bytes, allocated
                                    // by the first orl_batch_action_mask of that layout (a view of one stays that layout's)
   // host `given`s: [0] ORL_MASK_CORE_SLOT's (path, modulation) pairs [B][2], [1] orl_batch_complete_actions' prefixes [B][n_given <= 3]
-  // (capacity [B][3]), [2] orl_batch_assign_spectrum's paths [B].  One stage per call on purpose: each may refill its staging
-  // buffer without waiting for another's upload.
-  enum { GIVEN_MASK, GIVEN_COMPLETE, GIVEN_ASSIGN, GIVEN_STAGES };
+  // (capacity [B][3]), [2] orl_batch_assign_spectrum's paths [B], [3] orl_batch_route_cores' (path, core) prefixes [B][n_given <= 2]
+  // (capacity [B][2]).  One stage per call on purpose: each may refill its staging buffer without waiting for another's upload.
+  enum { GIVEN_MASK, GIVEN_COMPLETE, GIVEN_ASSIGN, GIVEN_ROUTE_CORES, GIVEN_STAGES };
   GivenStage given[GIVEN_STAGES];
   int mask_last = -1;              // layout of the last launch: what ORL_BUF_ACTION_MASK hands out (-1: none yet)
   float* pf_buf[9] = {};           // path features per block count j (1 .. 8): [B][pitch] floats, allocated by the first
@@ -107,6 +107,8 @@ struct orl_batch {
                                     // orl_batch_matrix_paths_observation; what ORL_BUF_MATRIX_PATHS_OBS hands out
   int32_t* route_table = nullptr;  // the per-path assignment table: [B][4 K] int32, allocated by the first orl_batch_route_spectrum; what
                                    // ORL_BUF_ASSIGN_TABLE hands out
+  int32_t* core_table = nullptr;   // RMCSA's (path, core) table: [B][4 K C] int32, allocated by the first orl_batch_route_cores; what
+                                   // ORL_BUF_CORE_TABLE hands out
   // orl_batch_copy_envs (as the destination): the pair indices [2][n] on the device and in page-locked memory, grown on demand
   long long* copy_idx = nullptr;
   long long* h_copy_idx = nullptr;
@@ -155,6 +157,9 @@ template <int W> void rmcsa_complete(orl_batch* b, int n_given, const int* given
 template <int W> void assign_spectrum(orl_batch* b, int rule, int n_given, const int* given, int gstride);
 // k_route_spectrum: every path's winner under `rule` -> table [B][K][4] (device), the action under `route` into P.actions
 template <int W> void route_spectrum(orl_batch* b, int rule, int route, int32_t* table);
+// k_route_cores: every (path, core) pair's winner under `rule` -> table [B][K C][4] (device), the action under `route` over the pairs
+// the prefix admits (path at given[e * gstride], core at given[e * gstride + gcore]) into P.actions
+template <int W> void route_cores(orl_batch* b, int rule, int route, int modulation, int n_given, const int* given, int gstride, int gcore, int32_t* table);
 template <int W> void path_features(orl_batch* b, float* out, int j, int mod);  // k_path_features -> out [B][pitch] floats
 template <int W> void link_features(orl_batch* b, float* out);             // k_link_features -> out [B][pitch] floats
 // k_persist in the form `ch` (the run's choice for the whole batch; use_spec: made for the attached specialisation library) over the

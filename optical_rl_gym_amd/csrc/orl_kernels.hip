@@ -14,6 +14,7 @@
 //   k_rmcsa_complete first-fit completion of a partial RMCSA action (orl_rmcsa_complete.h)  8 lanes per env, lane = (path, core)
 //   k_assign_spectrum spectrum-assignment rules for RMSA / RWA actions (orl_assign.h)  8 lanes per env, lane = path, then word of the row
 //   k_route_spectrum routing rules and the per-path assignment table (orl_route.h)      8 lanes per env, lane = path, every path
+//   k_route_cores core and spectrum rules and the (path, core) table of RMCSA (orl_route_cores.h)  8 lanes per env, lane = (path, core), every pair
 //   k_path_features path-feature observation of the pending service (orl_path_obs.h)    8 lanes per env, rows striped over them
 //   k_link_features per-link feature observation of the pending service (orl_link_obs.h)  8 lanes per env, slot rows striped over them
 //               [what these three views share — and k_qos_matrix_obs of orl_api.hip with them — lives in orl_view.h]
@@ -2057,6 +2058,7 @@ __global__ void __launch_bounds__(256) k_obs8(DevParams P, int with_terminal) {
 #include "orl_rmcsa_complete.h"  // k_rmcsa_complete: a partial RMCSA action completed first-fit under the masks' rule
 #include "orl_assign.h"  // k_assign_spectrum: the first slot of an RMSA / RWA action under a named spectrum-assignment rule
 #include "orl_route.h"  // k_route_spectrum: every path's winner under a rule as a table, reduced to one action under a routing order
+#include "orl_route_cores.h"  // k_route_cores: RMCSA — every (path, core) pair's winner under a rule as a table, one action under a route
 #include "orl_path_obs.h"  // k_path_features: the path-feature observation of the pending service (every slot-map family)
 #include "orl_link_obs.h"  // k_link_features: the per-link feature observation of the pending service (every slot-map family)
 #include "orl_qos_obs.h"  // (its kernel is the API unit's: here the LDS size of its wavefront alone)
@@ -2309,6 +2311,20 @@ template <int W> void route_spectrum(orl_batch* b, int rule, int route, int32_t*
   ORL_TK(b, "k_route_spectrum");
 }
 
+// k_route_cores (orl_route_cores.h): every (path, core) pair's winner under `rule` into `table` ([B][K C] rows of 4 int32 on the device),
+// the action under `route` over the pairs the prefix admits into P.actions.  The path of env e at given[e * gstride], its core at
+// given[e * gstride + gcore] (device int32).  ORL_ASSIGN_MIN_CUTS runs the instantiation with the cut planes, rules 0 - 3 the plain one.
+template <int W> void route_cores(orl_batch* b, int rule, int route, int modulation, int n_given, const int* given, int gstride, int gcore, int32_t* table) {
+  const DevParams& VP = b->P;
+  const ViewPlan pl = view_plan(VP, W, VIEW_ROUTE_CORES, rule);
+  int4* out = (int4*)table;
+  if (route_mode_of(rule) == ROUTE_CUTS)
+    hipLaunchKernelGGL((k_route_cores<W, ROUTE_CUTS>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, rule, route, modulation, n_given, given, gstride, gcore, out);
+  else
+    hipLaunchKernelGGL((k_route_cores<W, ROUTE_PLAIN>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, rule, route, modulation, n_given, given, gstride, gcore, out);
+  ORL_TK(b, "k_route_cores");
+}
+
 // k_path_features (orl_path_obs.h) into `out` ([B][pitch] floats on the device): j blocks per row, RMCSA under modulation `mod`
 // (-1: each path's best).  The wavefront's rows are staged in LDS where 8 of them fit, else every lane stores its own blocks
 // (-DORL_PATH_OBS_STAGE=0: always — the build the two forms were measured against each other with).
@@ -2485,6 +2501,7 @@ template void rmcsa_mask<ORL_W>(orl_batch*, int, unsigned char*, const int*, int
 template void rmcsa_complete<ORL_W>(orl_batch*, int, const int*, int);
 template void assign_spectrum<ORL_W>(orl_batch*, int, int, const int*, int);
 template void route_spectrum<ORL_W>(orl_batch*, int, int, int32_t*);
+template void route_cores<ORL_W>(orl_batch*, int, int, int, int, const int*, int, int, int32_t*);
 template void path_features<ORL_W>(orl_batch*, float*, int, int);
 template void link_features<ORL_W>(orl_batch*, float*);
 template void persist<ORL_W>(orl_batch*, const DevParams&, const PersistChoice&, bool, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);

@@ -85,6 +85,47 @@ template <int W> __device__ __forceinline__ Row<W> route_and_cuts(const PathRec&
   return m;
 }
 
+// The winner (slot, cost) of rules 0 - 3 on r = fits(p) of a service of n slots, r having a set bit: every lane on its own row
+// (ROUTE_PLAIN; orl_route_cores.h takes the same per (path, core) pair)
+template <int W> __device__ __forceinline__ void route_plain_winner(int rule, const Row<W>& r, int S, int n, int& slot, int& cost) {
+  if (rule == ORL_ASSIGN_FIRST_FIT) {
+    slot = row_ctz<W>(r);
+    cost = slot;
+  } else if (rule == ORL_ASSIGN_LAST_FIT) {
+    slot = row_bitlen<W>(r) - 1;
+    cost = S - n - slot;
+  } else {
+    // the shortest run of the lane's own row (ties: the lowest start), over the runs of every word
+    int key = KEY_NO_RUN;
+#pragma unroll
+    for (int i = 0; i < W; i++) {
+      const int k = assign_runs_key<W>(r, i);
+      key = k < key ? k : key;
+    }
+    assign_run_choice<W>(rule, key, r, slot, cost);
+  }
+}
+// The winner of ORL_ASSIGN_MIN_CUTS on r = fits(p), r having a set bit, from the planes of route_and_cuts: the minimum over the set
+// bits plane by plane from the top, its lowest bit, and the count read back from the planes there (ROUTE_CUTS)
+template <int W> __device__ __forceinline__ void route_cuts_winner(const Row<W>& r, const Row<W> (&pl)[ROUTE_CUT_PLANES], int& slot, int& cost) {
+  Row<W> cand = r;
+#pragma unroll
+  for (int j = ROUTE_CUT_PLANES - 1; j >= 0; j--) {
+    const Row<W> t = row_andn<W>(cand, pl[j]);
+    if (row_any<W>(t)) cand = t;
+  }
+  slot = row_ctz<W>(cand);
+  cost = 0;
+#pragma unroll
+  for (int j = 0; j < ROUTE_CUT_PLANES; j++) {  // cuts(q, slot) back from the planes
+    u64 x = 0ull;
+#pragma unroll
+    for (int i = 0; i < W; i++)
+      if (i == (slot >> 6)) x = pl[j].w[i];
+    cost |= (int)((x >> (slot & 63)) & 1ull) << j;
+  }
+}
+
 // u[] of the env as byte counters in the group's part of LDS (ROUTE_COUNTED): the construction and layout of k_assign_spectrum<W,
 // true> (orl_assign.h, which has it inline; assign_count reads both) — lane w < W counts the 64 slots of word w over all E link
 // rows in bit-sliced planes and expands them to bytes.  Complete for the group's lanes on return.
@@ -149,24 +190,7 @@ __global__ void __launch_bounds__(256) k_route_spectrum(DevParams P, int rule, i
       r = row_runs_ge<W>(m, n);
     }
     if constexpr (MODE == ROUTE_PLAIN) {
-      if (row_any<W>(r)) {
-        if (rule == ORL_ASSIGN_FIRST_FIT) {
-          slot = row_ctz<W>(r);
-          cost = slot;
-        } else if (rule == ORL_ASSIGN_LAST_FIT) {
-          slot = row_bitlen<W>(r) - 1;
-          cost = S - n - slot;
-        } else {
-          // the shortest run of the lane's own row (ties: the lowest start), over the runs of every word
-          int key = KEY_NO_RUN;
-#pragma unroll
-          for (int i = 0; i < W; i++) {
-            const int k = assign_runs_key<W>(r, i);
-            key = k < key ? k : key;
-          }
-          assign_run_choice<W>(rule, key, r, slot, cost);
-        }
-      }
+      if (row_any<W>(r)) route_plain_winner<W>(rule, r, S, n, slot, cost);
     } else if constexpr (MODE == ROUTE_COUNTED) {
       // the paths of the chunk that fit, in turn: word gl of the path's fits row and its n to every lane of the group
       u32 fit = g8::gballot(row_any<W>(r), lane);
@@ -202,24 +226,7 @@ __global__ void __launch_bounds__(256) k_route_spectrum(DevParams P, int rule, i
         }
       }
     } else {
-      if (row_any<W>(r)) {
-        Row<W> cand = r;
-#pragma unroll
-        for (int j = ROUTE_CUT_PLANES - 1; j >= 0; j--) {
-          const Row<W> t = row_andn<W>(cand, pl[j]);
-          if (row_any<W>(t)) cand = t;
-        }
-        slot = row_ctz<W>(cand);
-        cost = 0;
-#pragma unroll
-        for (int j = 0; j < ROUTE_CUT_PLANES; j++) {  // cuts(q, slot) back from the planes
-          u64 x = 0ull;
-#pragma unroll
-          for (int i = 0; i < W; i++)
-            if (i == (slot >> 6)) x = pl[j].w[i];
-          cost |= (int)((x >> (slot & 63)) & 1ull) << j;
-        }
-      }
+      if (row_any<W>(r)) route_cuts_winner<W>(r, pl, slot, cost);
     }
     if (q < K) table[v.env * K + q] = make_int4(slot, cost, n, nfree);
     int key = ORL_ROUTE_NO_FIT;

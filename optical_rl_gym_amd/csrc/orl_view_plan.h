@@ -3,7 +3,7 @@
 //
 // Like the form choice (orl_persist_form.h) and the run plan (orl_run_plan.h) both are pure functions of the batch's sizes, pinned
 // without a device by tests/test_view_plan.py (orl_debug_view_plan).  No HIP call in here.  Included behind the views' headers
-// (orl_mask.h, orl_rmcsa_mask.h, orl_assign.h, orl_route.h, orl_link_obs.h, orl_qos_obs.h), which keep the LDS sizes of one env or wavefront
+// (orl_mask.h, orl_rmcsa_mask.h, orl_assign.h, orl_route.h, orl_route_cores.h, orl_link_obs.h, orl_qos_obs.h), which keep the LDS sizes of one env or wavefront
 // next to the kernels that lay them out; orl_kernels.hip and orl_api.hip both see all of them, their kernels only where they are
 // launched.
 #pragma once
@@ -23,6 +23,7 @@ enum ViewKind {
   VIEW_LINK_FEATURES,      // k_link_features
   VIEW_MATRIX_PATHS_OBS,   // k_qos_matrix_obs
   VIEW_ROUTE,              // k_route_spectrum; arg: the rule
+  VIEW_ROUTE_CORES,        // k_route_cores (RMCSA); arg: the rule
   VIEW_COUNT
 };
 
@@ -73,6 +74,10 @@ inline ViewShape view_shape(const orl::DevParams& P, int view, int arg) {
       s.rows = P.K; s.width = 4; s.elem_bytes = 4;
       s.dim = 4 * P.K;
       break;
+    case VIEW_ROUTE_CORES:  // (orl_route_cores.h) the (path, core) table: a row of (s*, c*, n, free) per pair, in the path features' row order
+      if (rmcsa) { s.rows = P.K * P.C; s.width = 4; s.dim = 4 * s.rows; }
+      s.elem_bytes = 4;
+      break;
   }
   const int64_t per16 = 16 / s.elem_bytes;
   s.pitch = (s.dim + per16 - 1) / per16 * per16;
@@ -106,6 +111,7 @@ inline ViewPlan view_plan(const orl::DevParams& P, int W, int view, int arg) {
       r.waves = P.M > 32 ? 0 : view_waves(wave);
       break;
     case VIEW_COMPLETE:
+    case VIEW_ROUTE_CORES:  // (orl_route_cores.h: no LDS; ORL_ASSIGN_MIN_CUTS keeps its planes in registers)
       r.waves = 4;
       break;
     case VIEW_ASSIGN:  // (the counts of 4 wavefronts fit for every W: orl_assign.h)

@@ -883,6 +883,69 @@ class BatchedOpticalEnv:
             return None
         return (out.copy(), tab) if table else out.copy()
 
+    # ---- core and spectrum rules and the (path, core) table (include/orl.h, orl_batch_route_cores): RMCSA ----------------------
+    CORE_RULES = {"first": 0, "last": 1, "best": 2, "exact": 3, "min_cuts": 6}
+    CORE_ROUTES = dict(ROUTES, ksp_best_core=3, ksp_least_loaded_core=4)
+
+    @classmethod
+    def core_route_ids(cls, rule, route):
+        """The (ORL_ASSIGN_*, ORL_ROUTE_*) ids of a rule's and a route's names for route_cores() (ints pass through: an unknown id is
+        the library's to refuse)."""
+        return cls._named_id("rule", cls.CORE_RULES, rule), cls._named_id("route", cls.CORE_ROUTES, route)
+
+    @staticmethod
+    def core_prefix(paths, cores, n_given, num_envs):
+        """(int32 [num_envs, g] or None, g) from the arguments of route_cores(); ValueError for a bad shape or dtype, or cores
+        without paths."""
+        if paths is None:
+            if cores is not None:
+                raise ValueError("cores without paths: the prefix is (path) or (path, core)")
+            return None, 0 if n_given is None else int(n_given)
+        cols = [np.asarray(paths)] + ([] if cores is None else [np.asarray(cores)])
+        for what, c in zip(("paths", "cores"), cols):
+            if c.ndim != 1 or c.shape[0] != num_envs or c.dtype.kind not in "iu":
+                raise ValueError("%s must be an int array of shape (%d,), got %s %r" % (what, num_envs, c.dtype, c.shape))
+        n = len(cols) if n_given is None else int(n_given)
+        if n != len(cols) and 1 <= n <= 2:  # (an n_given outside 1 .. 2 is the library's to refuse, with or without a prefix)
+            raise ValueError("n_given = %d, but %d prefix column(s) given" % (n, len(cols)))
+        return np.ascontiguousarray(np.stack(cols, axis=1), np.int32), n
+
+    def core_table_shape(self):
+        """(rows, width, pitch) of the (path, core) table: rows = k * cores blocks of width = 4 int32 per env, rows of the device
+        buffer pitch = 4 k cores int32 apart."""
+        r, w, p = C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self.lib.orl_batch_core_table_shape(self._h, C.byref(r), C.byref(w), C.byref(p)))
+        return r.value, w.value, p.value
+
+    def route_cores(self, rule="first", route="best", paths=None, cores=None, n_given=None, modulation=None, fetch=True, table=False):
+        """RMCSA: choose every env's path, core AND first slot on the device.  For every (path, core) pair the kernel computes the
+        winner (s*, c*) of `rule` — "first", "last", "best", "exact" or "min_cuts" (route_spectrum's; "most_used" and "least_used"
+        have no form over cores) — on the path's free slots in that core, for the slots of the path's modulation: `modulation`
+        None = each path's best within reach (complete_actions' choice), m in [0, M) = that modulation for every path, usable
+        only where it is within reach.  `route` picks among the pairs that fit: "ksp" the first path and its first core
+        (complete_actions' order), "best" the smallest cost c* over all pairs, "least_loaded" the pair with the most free slots,
+        "ksp_best_core" / "ksp_least_loaded_core" the first path with a fit and among its cores the smallest c* / the most free
+        slots.  `paths` (and `cores`): 1-D int arrays that fix the path (and the core) per env; paths=None with n_given = 1 or 2
+        reads them from columns 0 and 2 of device_array("actions"), where an agent on the GPU writes them.  Returns int32
+        [num_envs, 4] rows (path, modulation, core, slot), left in device_array("actions") for the next step(None); the reject
+        action (k, M, C, S) where no pair fits or a given column is out of range.  table=True: (actions, table), table int32
+        [num_envs, k * cores, 4] with row p * cores + c = (s*, c*, slots needed on p, free slots of p in core c) — (S, 0x7fffffff,
+        ., .) for a pair without a fit, (S, 0x7fffffff, 0, 0) for a path the service cannot use — always for every pair, whatever
+        the prefix; it stays on the device as device_array("core_table") ([num_envs, 4 k cores]).  Env state and flags are not
+        touched.  fetch=False only queues the launch on the batch's stream (returns None; graph-capturable with paths=None after
+        the first call)."""
+        rid, tid = self.core_route_ids(rule, route)
+        g, n = self.core_prefix(paths, cores, n_given, self.num_envs)
+        mod = -1 if modulation is None else int(modulation)
+        out = self._act if fetch else None
+        tab = np.empty((self.num_envs, self.k_paths * self.num_spatial_resources, 4), np.int32) if fetch and table else None
+        self._keep_given = g  # (alive until the call returns: the library copies it before it does)
+        self._ck(self.lib.orl_batch_route_cores(self._h, rid, tid, mod, n, None if g is None else g.ctypes.data,
+                                                None if out is None else out.ctypes.data, None if tab is None else tab.ctypes.data))
+        if out is None:
+            return None
+        return (out.copy(), tab) if table else out.copy()
+
     # ---- MatrixObservationWithPaths (include/orl.h, orl_batch_matrix_paths_observation): QoSConstrainedRA only ---------------
     def matrix_paths_obs_shape(self):
         """(dim, pitch): dim = links * S * (k + 1) + 1 columns per env, rows pitch bytes apart in the device buffer."""
@@ -949,7 +1012,7 @@ class BatchedOpticalEnv:
     _BUFFERS = {"actions": (0, "<i4", 4), "reward": (1, "<f8", 0), "done": (2, "|u1", 0), "info": (3, "<f8", -1),
                 "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0), "action_mask": (7, "|b1", None),
                 "matrix_paths_obs": (8, "|u1", None), "path_features": (9, "<f4", None),
-                "link_features": (10, "<f4", None), "assign_table": (11, "<i4", None)}
+                "link_features": (10, "<f4", None), "assign_table": (11, "<i4", None), "core_table": (12, "<i4", None)}
     # The views of the pending service: [num_envs, dim] rows of the last call at the device pitch.  name -> (the message while no
     # call has been made, (dim, pitch in items) of those rows, item size).  Every mask layout and every j of the path features has
     # a buffer of its own: a view taken after a "joint" call keeps showing the joint rows (as the last "joint" call left them)
@@ -963,7 +1026,9 @@ class BatchedOpticalEnv:
               "link_features": ("no link features yet: call link_features() (fetch=False only queues it) first",
                                 lambda self: self.link_features_shape()[::3], 4),
               "assign_table": ("no assignment table yet: call route_spectrum() (fetch=False only queues it) first",
-                               lambda self: (4 * self.assign_table_shape()[0], self.assign_table_shape()[2]), 4)}
+                               lambda self: (4 * self.assign_table_shape()[0], self.assign_table_shape()[2]), 4),
+              "core_table": ("no (path, core) table yet: call route_cores() (fetch=False only queues it) first",
+                             lambda self: (4 * self.core_table_shape()[0], self.core_table_shape()[2]), 4)}
 
     def device_array(self, name):
         """The batch's device-resident I/O array `name` as an object with `__cuda_array_interface__` (what

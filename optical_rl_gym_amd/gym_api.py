@@ -481,6 +481,14 @@ class RMCSAEnv(_SingleEnv):
         given = np.asarray(prefix, np.int32).reshape(1, len(prefix)) if prefix else None
         return tuple(int(v) for v in self.batch.complete_actions(given=given, n_given=len(prefix))[0])
 
+    def route_cores(self, rule="first", route="best", path=None, core=None, modulation=None):
+        """The action (path, modulation, core, first slot) the route `route` — "ksp", "best", "least_loaded", "ksp_best_core" or
+        "ksp_least_loaded_core" — picks among every (path, core) pair's winner under `rule` — "first", "last", "best", "exact" or
+        "min_cuts" (BatchedOpticalEnv.route_cores) — over all pairs, the cores of `path`, or the pair (`path`, `core`) alone; the
+        reject action (k, M, C, S) when the service fits on none."""
+        one = lambda v: None if v is None else np.array([int(v)], np.int32)
+        return self._decode(self.batch.route_cores(rule, route, paths=one(path), cores=one(core), modulation=modulation)[0])
+
     def _episode_hist(self, which):  # re-zeroed at every reset and never incremented (rmcsa_env.py:154-180, 391-407)
         return np.zeros((self.k_paths + 1, len(self.topo.modulations) + 1, self.num_spatial_resources + 1,
                          self.num_spectrum_resources + 1), dtype=int)

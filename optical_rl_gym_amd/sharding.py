@@ -374,6 +374,22 @@ class MultiDeviceBatch:
     def assign_table_shape(self):
         return self.shards[0].assign_table_shape()
 
+    def route_cores(self, rule="first", route="best", paths=None, cores=None, n_given=None, modulation=None, fetch=True, table=False):
+        """BatchedOpticalEnv.route_cores of every shard; `paths` and `cores` ([num_envs]) are cut by the shards' bounds, the shards'
+        action rows (and table rows) concatenated."""
+        from .envs import BatchedOpticalEnv
+
+        g, n = BatchedOpticalEnv.core_prefix(paths, cores, n_given, self.num_envs)
+        col = lambda r, i: None if g is None or g.shape[1] <= i else self._cut(np.ascontiguousarray(g[:, i]), r)
+        out = self._map(lambda r: self.shards[r].route_cores(rule, route, paths=col(r, 0), cores=col(r, 1), n_given=n, modulation=modulation,
+                                                             fetch=fetch, table=table))
+        if not fetch:
+            return None
+        return (self._cat([o[0] for o in out]), self._cat([o[1] for o in out])) if table else self._cat(out)
+
+    def core_table_shape(self):
+        return self.shards[0].core_table_shape()
+
     def path_features_shape(self, j=1):
         return self.shards[0].path_features_shape(j)
 

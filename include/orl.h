@@ -320,6 +320,11 @@ int orl_host_free(void* p);
 #define ORL_BUF_CORE_TABLE 12     /* int32 [n_envs][pitch]: RMCSA's (path, core) table of the last orl_batch_route_cores, row p C + c at
                                    * columns 4 (p C + c) .. + 3 (pitch of orl_batch_core_table_shape); allocated by the first call,
                                    * n_elements = 0 before it */
+#define ORL_BUF_BLOCK_TABLE 13    /* int32 [n_envs][pitch]: the block table of the last orl_batch_block_table, row r at columns
+                                   * (2 + 2j) r .. (pitch of orl_batch_block_table_shape for that call's j); each j has a buffer of its
+                                   * own, allocated by its first call; n_elements = 0 before any call */
+#define ORL_BUF_BLOCK_MASK 14     /* u8 [n_envs][pitch]: the mask of the block action space the same call left (mask pitch of
+                                   * orl_batch_block_table_shape); one per j beside the table */
 int orl_batch_device_buffer(orl_batch* b, int which, void** device_ptr, int64_t* n_elements);
 /* The HIP stream (hipStream_t) the batch queues its launches on.  An agent on the same GPU that queues ITS kernels on this
  * stream too (torch: `torch.cuda.ExternalStream(ptr)`) needs no synchronisation between its network and orl_batch_step: the
@@ -631,6 +636,48 @@ int orl_batch_route_cores(orl_batch* b, int rule, int route, int modulation /* -
                           const int32_t* given /* host [n_envs][n_given], or NULL = columns 0 and 2 of ORL_BUF_ACTIONS */,
                           int32_t* actions_out /* host [n_envs][4], or NULL */, int32_t* table_out /* host [n_envs][k C][4], or NULL */);
 int orl_batch_core_table_shape(const orl_batch* b, int32_t* rows, int32_t* width, int32_t* pitch);
+
+/* Block actions: DeepRMSA's (path, free block) action space for every slot-map family.  The rules above hand the agent a rule's
+ * single winner per row; the path features show it the first j free blocks that fit.  Here the agent ACTS in those terms: "row r,
+ * block b" = take the b-th fitting block of that row, a Discrete(R j + 1) space in which every set column provisions and the agent
+ * itself chooses where in the spectrum.  For the pending service of an env and every row r of orl_batch_path_features' row order —
+ * R = k rows, r = p, for RMSA, DeepRMSA and RWA; R = k C rows, r = p C + c, for RMCSA:
+ *   n(r), m(p), row(r), fits   those of orl_batch_route_spectrum (RMSA, DeepRMSA, RWA) and of orl_batch_route_cores (RMCSA:
+ *              modulation = -1 is m*(p), the best within reach; modulation = m is m where it is within both reach limits).  A path
+ *              without a usable modulation, or p >= n_paths[src, dst], makes its rows unusable;
+ *   blocks(r)  the maximal free runs of row(r) of length L >= n(r), in slot order: block b = (start_b, L_b).  A run that ends at slot
+ *              S - 1 counts, as everywhere in these rules.
+ * The table is int32 [n_envs][R][2 + 2 j] (ORL_BUF_BLOCK_TABLE): row r = (n(r), free(r), start_0, L_0, ..., start_{j-1}, L_{j-1}),
+ * columns (S, 0) for a block that does not exist, (0, 0, S, 0, ...) for an unusable row, which loads no link row.  The device pitch
+ * is round_up(R (2 + 2 j), 4) int32, the pad columns 0.
+ * The mask is uint8 [n_envs][R j + 1] (ORL_BUF_BLOCK_MASK) at a device pitch of round_up(R j + 1, 16): column r j + b = 1 iff block b
+ * of row r exists; the last column is the reject action, = allow_rejection; a row without a set column and allow_rejection == 0 gets
+ * every other column set (the fallback of orl_batch_action_mask).  On a DeepRMSA batch with its own j it is that batch's
+ * ORL_MASK_JOINT mask.
+ * Selection: a flat index a per env, r = a / j and b = a % j, and a placement of the service in the block: */
+#define ORL_BLOCK_FIRST 0 /* s = start_b: the block's lower end, DeepRMSA's decode */
+#define ORL_BLOCK_LAST 1  /* s = start_b + L_b - n: the block's upper end */
+/* The action written to the env's row of ORL_BUF_ACTIONS, where step(NULL) reads it: (p, s, 0, 0) for RMSA and RWA, (p, m(p), c, s) for
+ * RMCSA; the family's reject row — (k, S, 0, 0), (k, M, C, S) — for a < 0, a >= R j or a block that does not exist.  Stepping any
+ * other result provisions.  Selection recomputes from the slot maps; it does not read a table an earlier call left.
+ * orl_batch_block_table: one launch on the batch's stream into ORL_BUF_BLOCK_TABLE and ORL_BUF_BLOCK_MASK; no atomics.  Each j has a
+ * pair of buffers of its own, allocated by its first call.  orl_batch_select_blocks: one launch.  given == NULL: the index is column 0
+ * of ORL_BUF_ACTIONS, where an agent on the GPU writes it; a host `given` [n_envs] int32 goes through a page-locked buffer of the batch
+ * into a device buffer of the batch (both allocated by the first such call, this call's own), asynchronously on the batch's stream.
+ * With all output pointers NULL and after the first call for that j the calls neither synchronise nor allocate: graph-capturable.
+ * With an output pointer the rows are copied out densely and the call synchronises.  Env state, flags and snapshot bytes do not
+ * change.
+ * Families: the table and mask exist for RMSA, DeepRMSA, RWA and RMCSA; selection for RMSA, RWA and RMCSA (DeepRMSA steps block
+ * indices natively).  ORL_E_INVALID, before anything is queued or allocated: another family, j outside 1 .. 8, a modulation other than
+ * -1 outside RMCSA or outside -1 .. M - 1, a placement outside 0 .. 1, more rows than the kernel's LDS holds mask words for (R > 1534).
+ * orl_batch_block_table_shape: *rows = R, *width = 2 + 2 j, the table's device pitch in int32, the mask's dim R j + 1 and pitch. */
+int orl_batch_block_table_shape(const orl_batch* b, int j, int32_t* rows, int32_t* width /* 2 + 2j */, int32_t* table_pitch,
+                                int32_t* mask_dim, int32_t* mask_pitch);
+int orl_batch_block_table(orl_batch* b, int j, int modulation /* -1: each path's best */, int32_t* table_out /* host [n_envs][R][2 + 2j], or NULL */,
+                          uint8_t* mask_out /* host [n_envs][R j + 1], or NULL */);
+int orl_batch_select_blocks(orl_batch* b, int j, int modulation, int placement,
+                            const int32_t* given /* host [n_envs], or NULL = column 0 of ORL_BUF_ACTIONS */,
+                            int32_t* actions_out /* host [n_envs][4], or NULL */);
 
 /* Snapshot / restore of the complete simulation state of the batch (slot maps, pending releases, RNG, statistics,
  * counters).  The reference has no equivalent (no checkpointing); used for long PPO runs.  The per-env

@@ -138,6 +138,7 @@ __global__ void k_matrix_obs(DevParams P, unsigned char* out) {
 #include "orl_assign.h"
 #include "orl_route.h"
 #include "orl_route_cores.h"
+#include "orl_blocks.h"
 #include "orl_link_obs.h"
 #include "orl_view_plan.h"  // view_shape, view_plan: the shape of each view's rows and the geometry of its launch
 
@@ -1247,6 +1248,14 @@ extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_pt
       *device_ptr = b->core_table;
       *n_elements = b->core_table ? B * view_shape(b->P, VIEW_ROUTE_CORES, 0).pitch : 0;
       break;
+    case ORL_BUF_BLOCK_TABLE:
+      *device_ptr = b->bt_last ? b->bt_buf[b->bt_last] : nullptr;
+      *n_elements = b->bt_last ? B * view_shape(b->P, VIEW_BLOCKS, b->bt_last).pitch : 0;
+      break;
+    case ORL_BUF_BLOCK_MASK:
+      *device_ptr = b->bt_last ? b->bk_buf[b->bt_last] : nullptr;
+      *n_elements = b->bt_last ? B * view_blocks_mask(b->P, b->bt_last).pitch : 0;
+      break;
     default: return fail(ORL_E_INVALID, "unknown buffer %d", which);
   }
   return ORL_OK;
@@ -1481,6 +1490,66 @@ extern "C" int orl_batch_path_features(orl_batch* b, int j, int modulation, floa
   HIPCHK(hipGetLastError());
   b->pf_last = j;
   return view_rows_to_host(b, buf, sh, out);
+}
+ORL_ABI_CATCH_INT
+
+// block actions (orl_blocks.h): the table and mask of the (row, free block) action space, and an index's decode into an action
+static int blocks_check(const orl_batch* b, int j, int modulation) {
+  if (b->P.env_type == ENV_QOS) return fail(ORL_E_INVALID, "block actions are not available for QoSConstrainedRA, which has no slot maps (RMSA, DeepRMSA, RWA and RMCSA only)");
+  if (j < 1 || j > 8) return fail(ORL_E_INVALID, "block actions list j = 1 .. 8 free blocks per row, got j = %d", j);
+  if (modulation != -1 && b->P.env_type != ENV_RMCSA) return fail(ORL_E_INVALID, "a modulation for the block actions is defined for RMCSA only (pass -1)");
+  if (modulation < -1 || modulation >= b->P.M) return fail(ORL_E_INVALID, "modulation %d outside -1 (each path's best) .. %d", modulation, b->P.M - 1);
+  if (!view_plan(b->P, b->wt, VIEW_BLOCKS, j).ok)
+    return fail(ORL_E_INVALID, "block actions over %d rows exceed the kernel's LDS budget", view_shape(b->P, VIEW_BLOCKS, j).rows);
+  return ORL_OK;
+}
+
+extern "C" int orl_batch_block_table_shape(const orl_batch* b, int j, int32_t* rows, int32_t* width, int32_t* table_pitch, int32_t* mask_dim,
+                                           int32_t* mask_pitch) try {
+  if (!b || !rows || !width || !table_pitch || !mask_dim || !mask_pitch) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = blocks_check(b, j, -1)) return rc;
+  const ViewShape sh = view_shape(b->P, VIEW_BLOCKS, j), mk = view_blocks_mask(b->P, j);
+  *rows = sh.rows;
+  *width = sh.width;
+  *table_pitch = (int32_t)sh.pitch;
+  *mask_dim = (int32_t)mk.dim;
+  *mask_pitch = (int32_t)mk.pitch;
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+extern "C" int orl_batch_block_table(orl_batch* b, int j, int modulation, int32_t* table_out, uint8_t* mask_out) try {
+  if (!b) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = blocks_check(b, j, modulation)) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  const ViewShape sh = view_shape(b->P, VIEW_BLOCKS, j), mk = view_blocks_mask(b->P, j);
+  int32_t*& table = b->bt_buf[j];  // one pair of buffers per j: a device view of one j's rows never sees another's
+  unsigned char*& mask = b->bk_buf[j];
+  if (int rc = view_buffer(b, table, (size_t)(b->P.B * sh.pitch) * sizeof(int32_t), "block table")) return rc;
+  if (int rc = view_buffer(b, mask, (size_t)(b->P.B * mk.pitch), "block mask")) return rc;
+  ORL_LAUNCH(block_table, b, table, mask, j, modulation);
+  HIPCHK(hipGetLastError());
+  b->bt_last = j;
+  if (table_out)
+    HIPCHK(hipMemcpy2DAsync(table_out, (size_t)sh.dim * 4, table, (size_t)sh.pitch * 4, (size_t)sh.dim * 4, (size_t)b->P.B, hipMemcpyDeviceToHost, b->stream));
+  if (mask_out) return view_rows_to_host(b, mask, mk, mask_out);  // (waits: for the table's copy too)
+  if (table_out) HIPCHK(hipStreamSynchronize(b->stream));
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+extern "C" int orl_batch_select_blocks(orl_batch* b, int j, int modulation, int placement, const int32_t* given, int32_t* actions_out) try {
+  if (!b) return fail(ORL_E_INVALID, "null argument");
+  if (b->P.env_type == ENV_DEEPRMSA) return fail(ORL_E_INVALID, "DeepRMSA steps block indices natively: pass the index to orl_batch_step (block selection is for RMSA, RWA and RMCSA)");
+  if (int rc = blocks_check(b, j, modulation)) return rc;
+  if (placement != ORL_BLOCK_FIRST && placement != ORL_BLOCK_LAST) return fail(ORL_E_INVALID, "unknown block placement %d (ORL_BLOCK_FIRST = 0, ORL_BLOCK_LAST = 1)", placement);
+  HIPCHK(hipSetDevice(b->device));
+  const int* src;
+  int stride;
+  if (int rc = given_source(b, given, b->given[orl_batch::GIVEN_BLOCKS], 1, 1, "block selection", src, stride)) return rc;
+  ORL_LAUNCH(select_blocks, b, j, modulation, placement, src, stride);
+  HIPCHK(hipGetLastError());
+  return actions_to_host(b, actions_out);
 }
 ORL_ABI_CATCH_INT
 
@@ -2148,6 +2217,7 @@ extern "C" int orl_debug_view_plan(int env_type, int W, int64_t B, int N, int E,
       J < 1 || M < 1 || view < 0 || view >= VIEW_COUNT)
     return 0;
   if (view == VIEW_ROUTE_CORES && env_type != ORL_ENV_RMCSA) return 0;  // (no batch of another family has this view)
+  if (view == VIEW_BLOCKS && (env_type == ORL_ENV_QOS || arg < 1 || arg > 8)) return 0;  // (nor has any a block table of such a j)
   DevParams P;
   memset(&P, 0, sizeof P);
   P.env_type = env_type; P.B = B; P.N = N; P.E = E; P.K = K; P.C = C; P.S = S; P.J = J; P.M = M;

@@ -95,7 +95,8 @@ struct orl_batch {
   // host `given`s: [0] ORL_MASK_CORE_SLOT's (path, modulation) pairs [B][2], [1] orl_batch_complete_actions' prefixes [B][n_given <= 3]
   // (capacity [B][3]), [2] orl_batch_assign_spectrum's paths [B], [3] orl_batch_route_cores' (path, core) prefixes [B][n_given <= 2]
   // (capacity [B][2]).  One stage per call on purpose: each may refill its staging buffer without waiting for another's upload.
-  enum { GIVEN_MASK, GIVEN_COMPLETE, GIVEN_ASSIGN, GIVEN_ROUTE_CORES, GIVEN_STAGES };
+  // [4] orl_batch_select_blocks' block indices [B].
+  enum { GIVEN_MASK, GIVEN_COMPLETE, GIVEN_ASSIGN, GIVEN_ROUTE_CORES, GIVEN_BLOCKS, GIVEN_STAGES };
   GivenStage given[GIVEN_STAGES];
   int mask_last = -1;              // layout of the last launch: what ORL_BUF_ACTION_MASK hands out (-1: none yet)
   float* pf_buf[9] = {};           // path features per block count j (1 .. 8): [B][pitch] floats, allocated by the first
@@ -109,6 +110,9 @@ struct orl_batch {
                                    // ORL_BUF_ASSIGN_TABLE hands out
   int32_t* core_table = nullptr;   // RMCSA's (path, core) table: [B][4 K C] int32, allocated by the first orl_batch_route_cores; what
                                    // ORL_BUF_CORE_TABLE hands out
+  int32_t* bt_buf[9] = {};         // block tables per block count j (1 .. 8): [B][pitch] int32, and their masks [B][pitch] bytes, both allocated
+  unsigned char* bk_buf[9] = {};   // by the first orl_batch_block_table of that j (a view of one stays that j's)
+  int bt_last = 0;                 // j of the last launch: what ORL_BUF_BLOCK_TABLE and ORL_BUF_BLOCK_MASK hand out (0: none yet)
   // orl_batch_copy_envs (as the destination): the pair indices [2][n] on the device and in page-locked memory, grown on demand
   long long* copy_idx = nullptr;
   long long* h_copy_idx = nullptr;
@@ -161,6 +165,10 @@ template <int W> void route_spectrum(orl_batch* b, int rule, int route, int32_t*
 // the prefix admits (path at given[e * gstride], core at given[e * gstride + gcore]) into P.actions
 template <int W> void route_cores(orl_batch* b, int rule, int route, int modulation, int n_given, const int* given, int gstride, int gcore, int32_t* table);
 template <int W> void path_features(orl_batch* b, float* out, int j, int mod);  // k_path_features -> out [B][pitch] floats
+// k_block_table -> table [B][pitch] int32 and mask [B][pitch] bytes (device); k_select_blocks: the index of env e at given[e * gstride]
+// (device) -> its row of P.actions
+template <int W> void block_table(orl_batch* b, int32_t* table, unsigned char* mask, int j, int mod);
+template <int W> void select_blocks(orl_batch* b, int j, int mod, int placement, const int* given, int gstride);
 template <int W> void link_features(orl_batch* b, float* out);             // k_link_features -> out [B][pitch] floats
 // k_persist in the form `ch` (the run's choice for the whole batch; use_spec: made for the attached specialisation library) over the
 // env range of view VP up to step `target` of this run, then k_rel_tail, on stream st

@@ -15,6 +15,7 @@
 //   k_assign_spectrum spectrum-assignment rules for RMSA / RWA actions (orl_assign.h)  8 lanes per env, lane = path, then word of the row
 //   k_route_spectrum routing rules and the per-path assignment table (orl_route.h)      8 lanes per env, lane = path, every path
 //   k_route_cores core and spectrum rules and the (path, core) table of RMCSA (orl_route_cores.h)  8 lanes per env, lane = (path, core), every pair
+//   k_block_table, k_select_blocks  block actions: the first j fitting blocks of every row, their mask, an index -> an action (orl_blocks.h)  8 lanes per env
 //   k_path_features path-feature observation of the pending service (orl_path_obs.h)    8 lanes per env, rows striped over them
 //   k_link_features per-link feature observation of the pending service (orl_link_obs.h)  8 lanes per env, slot rows striped over them
 //               [what these three views share — and k_qos_matrix_obs of orl_api.hip with them — lives in orl_view.h]
@@ -2059,6 +2060,7 @@ __global__ void __launch_bounds__(256) k_obs8(DevParams P, int with_terminal) {
 #include "orl_assign.h"  // k_assign_spectrum: the first slot of an RMSA / RWA action under a named spectrum-assignment rule
 #include "orl_route.h"  // k_route_spectrum: every path's winner under a rule as a table, reduced to one action under a routing order
 #include "orl_route_cores.h"  // k_route_cores: RMCSA — every (path, core) pair's winner under a rule as a table, one action under a route
+#include "orl_blocks.h"  // k_block_table, k_select_blocks: DeepRMSA's (row, free block) action space for every slot-map family
 #include "orl_path_obs.h"  // k_path_features: the path-feature observation of the pending service (every slot-map family)
 #include "orl_link_obs.h"  // k_link_features: the per-link feature observation of the pending service (every slot-map family)
 #include "orl_qos_obs.h"  // (its kernel is the API unit's: here the LDS size of its wavefront alone)
@@ -2336,6 +2338,26 @@ template <int W> void path_features(orl_batch* b, float* out, int j, int mod) {
   ORL_TK(b, "k_path_features");
 }
 
+// k_block_table (orl_blocks.h): the first j blocks of every row into `table` ([B][pitch] int32 on the device) and the mask of the block
+// action space into `mask` ([B][pitch] bytes), RMCSA under modulation `mod` (-1: each path's best); staged or direct as the path features
+template <int W> void block_table(orl_batch* b, int32_t* table, unsigned char* mask, int j, int mod) {
+  const DevParams& VP = b->P;
+  const ViewPlan pl = view_plan(VP, W, VIEW_BLOCKS, j);
+  const ViewShape sh = view_shape(VP, VIEW_BLOCKS, j);
+  hipLaunchKernelGGL((k_block_table<W>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, table, mask, j, mod, (int)sh.dim, (int)sh.pitch,
+                     (int)view_blocks_mask(VP, j).pitch, pl.staged ? 1 : 0);
+  ORL_TK(b, "k_block_table");
+}
+
+// k_select_blocks (orl_blocks.h): the block index of env e at given[e * gstride] (device int32) decoded under `placement` into its row of
+// P.actions; the table's geometry, no LDS
+template <int W> void select_blocks(orl_batch* b, int j, int mod, int placement, const int* given, int gstride) {
+  const DevParams& VP = b->P;
+  const ViewPlan pl = view_plan(VP, W, VIEW_BLOCKS, j);
+  hipLaunchKernelGGL((k_select_blocks<W>), dim3(pl.grid), dim3(pl.block), 0, b->stream, VP, j, mod, placement, given, gstride);
+  ORL_TK(b, "k_select_blocks");
+}
+
 // k_link_features (orl_link_obs.h) into `out` ([B][pitch] floats on the device), the wavefront's rows staged whole in LDS or in rounds
 // of pl.chunk slot rows per env
 template <int W> void link_features(orl_batch* b, float* out) {
@@ -2503,6 +2525,8 @@ template void assign_spectrum<ORL_W>(orl_batch*, int, int, const int*, int);
 template void route_spectrum<ORL_W>(orl_batch*, int, int, int32_t*);
 template void route_cores<ORL_W>(orl_batch*, int, int, int, int, const int*, int, int, int32_t*);
 template void path_features<ORL_W>(orl_batch*, float*, int, int);
+template void block_table<ORL_W>(orl_batch*, int32_t*, unsigned char*, int, int);
+template void select_blocks<ORL_W>(orl_batch*, int, int, int, const int*, int);
 template void link_features<ORL_W>(orl_batch*, float*);
 template void persist<ORL_W>(orl_batch*, const DevParams&, const PersistChoice&, bool, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);
 template void step2<ORL_W>(orl_batch*, int);

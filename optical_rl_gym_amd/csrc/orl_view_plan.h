@@ -3,7 +3,7 @@
 //
 // Like the form choice (orl_persist_form.h) and the run plan (orl_run_plan.h) both are pure functions of the batch's sizes, pinned
 // without a device by tests/test_view_plan.py (orl_debug_view_plan).  No HIP call in here.  Included behind the views' headers
-// (orl_mask.h, orl_rmcsa_mask.h, orl_assign.h, orl_route.h, orl_route_cores.h, orl_link_obs.h, orl_qos_obs.h), which keep the LDS sizes of one env or wavefront
+// (orl_mask.h, orl_rmcsa_mask.h, orl_assign.h, orl_route.h, orl_route_cores.h, orl_blocks.h, orl_link_obs.h, orl_qos_obs.h), which keep the LDS sizes of one env or wavefront
 // next to the kernels that lay them out; orl_kernels.hip and orl_api.hip both see all of them, their kernels only where they are
 // launched.
 #pragma once
@@ -24,6 +24,7 @@ enum ViewKind {
   VIEW_MATRIX_PATHS_OBS,   // k_qos_matrix_obs
   VIEW_ROUTE,              // k_route_spectrum; arg: the rule
   VIEW_ROUTE_CORES,        // k_route_cores (RMCSA); arg: the rule
+  VIEW_BLOCKS,             // k_block_table, k_select_blocks; arg: j
   VIEW_COUNT
 };
 
@@ -78,9 +79,22 @@ inline ViewShape view_shape(const orl::DevParams& P, int view, int arg) {
       if (rmcsa) { s.rows = P.K * P.C; s.width = 4; s.dim = 4 * s.rows; }
       s.elem_bytes = 4;
       break;
+    case VIEW_BLOCKS:  // (orl_blocks.h) the block table: a row of (n, free, j (start, length) pairs) per row of the path features; its mask: view_blocks_mask
+      s.rows = rmcsa ? P.K * P.C : P.K; s.width = 2 + 2 * arg; s.elem_bytes = 4;
+      s.dim = (int64_t)s.rows * s.width;
+      break;
   }
   const int64_t per16 = 16 / s.elem_bytes;
   s.pitch = (s.dim + per16 - 1) / per16 * per16;
+  return s;
+}
+
+// the mask that goes with the block table of j blocks per row: one column per (row, block) and the reject column, bytes at a pitch of
+// round_up(dim, 16)
+inline ViewShape view_blocks_mask(const orl::DevParams& P, int j) {
+  ViewShape s = {0, P.env_type == orl::ENV_RMCSA ? P.K * P.C : P.K, j, 0, 1};
+  s.dim = (int64_t)s.rows * j + 1;
+  s.pitch = (s.dim + 15) / 16 * 16;
   return s;
 }
 
@@ -92,7 +106,7 @@ struct ViewPlan {
   int waves, block;   // wavefronts and threads per workgroup
   unsigned grid;
   size_t lds_bytes;   // dynamic LDS of a workgroup
-  bool staged;        // path features: the wavefront's rows are assembled in LDS (else every lane stores its own blocks)
+  bool staged;        // path features, block table: the wavefront's rows are assembled in LDS (else every lane stores its own blocks)
   int chunk;          // link features: slot rows per env and round through LDS (a multiple of 8); 0: the rows whole
   bool counted;       // spectrum assignment: the instantiation with the per-slot occupancy counts
 };
@@ -126,6 +140,15 @@ inline ViewPlan view_plan(const orl::DevParams& P, int W, int view, int arg) {
       r.staged = fit != 0;
       r.waves = fit ? fit : 4;
       if (!fit) wave = 0;
+    } break;
+    // (orl_blocks.h) as the path features, with the mask's bit rows beside the table rows in both forms; k_select_blocks takes the
+    // same geometry and no LDS of its own (the launcher passes 0)
+    case VIEW_BLOCKS: {
+      const size_t bits = (size_t)8 * blocks_mask_env_words(view_shape(P, view, arg).rows) * sizeof(uint32_t);
+      wave = bits + (size_t)8 * view_shape(P, view, arg).pitch * sizeof(int32_t);
+      r.staged = view_waves(wave) != 0;
+      if (!r.staged) wave = bits;
+      r.waves = view_waves(wave);
     } break;
     // the rows whole where 8 of them fit beside the 8 envs' link sets; else in rounds of `chunk` slot rows per env, the most (a
     // multiple of 8) that 4, 2 or 1 wavefronts' staging fits

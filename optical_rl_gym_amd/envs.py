@@ -946,6 +946,64 @@ class BatchedOpticalEnv:
             return None
         return (out.copy(), tab) if table else out.copy()
 
+    # ---- block actions (include/orl.h, orl_batch_block_table / orl_batch_select_blocks): RMSA, DeepRMSA, RWA and RMCSA --------
+    BLOCK_PLACEMENTS = {"first": 0, "last": 1}
+
+    def block_table_shape(self, j=1):
+        """(rows, width, table_pitch, mask_dim, mask_pitch) of the block table and its mask for `j` blocks per row: rows = k (RMCSA:
+        k * cores) rows of width = 2 + 2 j int32 per env, rows of the table's device buffer table_pitch int32 apart; the mask has
+        mask_dim = rows * j + 1 columns, its rows mask_pitch bytes apart."""
+        v = [C.c_int32() for _ in range(5)]
+        self._ck(self.lib.orl_batch_block_table_shape(self._h, int(j), *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def block_table(self, j=1, modulation=None, fetch=True):
+        """DeepRMSA's (row, free block) action space of every env's pending service, computed on the device: (table, mask).  table
+        int32 [num_envs, rows, 2 + 2 j], row r (the path, RMCSA: p * cores + c, the row order of path_features) = (slots needed,
+        free slots, start_0, length_0, ..., start_{j-1}, length_{j-1}): the first j maximal free runs that fit the service, in slot
+        order; (S, 0) for a block that does not exist, (0, 0, S, 0, ...) for a row the service cannot use.  mask bool [num_envs,
+        rows * j + 1]: column r * j + b is set iff block b of row r exists — the columns select_blocks() turns into an action that
+        provisions; the last column is the reject action (allow_rejection), and a row without a set column and no rejection gets
+        every other column set.  `j` in [1, 8]; on a DeepRMSA batch with its own j the mask is action_mask("joint").  `modulation`
+        (RMCSA only): None = each path's best within reach, m in [0, M) = that modulation where it is within reach.  fetch=False
+        only queues the launch on the batch's stream (returns None) — read the rows in place with device_array("block_table") /
+        device_tensor("block_mask")."""
+        j, mod = int(j), -1 if modulation is None else int(modulation)
+        tab = msk = None
+        if fetch:
+            rows, width, _, dim, _ = self.block_table_shape(j)
+            tab, msk = np.empty((self.num_envs, rows, width), np.int32), np.empty((self.num_envs, dim), np.uint8)
+        self._ck(self.lib.orl_batch_block_table(self._h, j, mod, None if tab is None else tab.ctypes.data, None if msk is None else msk.ctypes.data))
+        self._bt_j = j
+        return (tab, msk.view(np.bool_)) if fetch else None
+
+    @staticmethod
+    def block_indices(blocks, num_envs):
+        """int32 [num_envs] or None from the `blocks` of select_blocks(); ValueError for a bad shape or dtype."""
+        if blocks is None:
+            return None
+        a = np.asarray(blocks)
+        if a.ndim != 1 or a.shape[0] != num_envs or a.dtype.kind not in "iu":
+            raise ValueError("blocks must be an int array of shape (%d,), got %s %r" % (num_envs, a.dtype, a.shape))
+        return np.ascontiguousarray(a, np.int32)
+
+    def select_blocks(self, blocks=None, j=1, modulation=None, placement="first", fetch=True):
+        """RMSA / RWA / RMCSA: decode every env's block index — a column r * j + b of block_table(j)'s mask — into the env's action on
+        the device: the service goes into block b of row r, at the block's lower end (placement "first", DeepRMSA's decode) or its
+        upper end ("last").  Returns int32 [num_envs, 4] rows (path, slot, 0, 0), RMCSA (path, modulation, core, slot), left in
+        device_array("actions") for the next step(None); the family's reject action for an index < 0 or >= rows * j or a block that
+        does not exist.  `blocks`: a 1-D int array; None reads column 0 of device_array("actions"), where an agent on the GPU
+        writes its choice.  The kernel recomputes from the slot maps: no block_table() call is needed first, and `j` and
+        `modulation` must be those the index was chosen under.  Env state and flags are not touched.  fetch=False only queues the
+        launch on the batch's stream (returns None; graph-capturable with blocks=None)."""
+        a = self.block_indices(blocks, self.num_envs)
+        mod = -1 if modulation is None else int(modulation)
+        out = self._act if fetch else None
+        self._keep_given = a  # (alive until the call returns: the library copies it before it does)
+        self._ck(self.lib.orl_batch_select_blocks(self._h, int(j), mod, self._named_id("placement", self.BLOCK_PLACEMENTS, placement),
+                                                  None if a is None else a.ctypes.data, None if out is None else out.ctypes.data))
+        return None if out is None else out.copy()
+
     # ---- MatrixObservationWithPaths (include/orl.h, orl_batch_matrix_paths_observation): QoSConstrainedRA only ---------------
     def matrix_paths_obs_shape(self):
         """(dim, pitch): dim = links * S * (k + 1) + 1 columns per env, rows pitch bytes apart in the device buffer."""
@@ -1012,7 +1070,8 @@ class BatchedOpticalEnv:
     _BUFFERS = {"actions": (0, "<i4", 4), "reward": (1, "<f8", 0), "done": (2, "|u1", 0), "info": (3, "<f8", -1),
                 "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0), "action_mask": (7, "|b1", None),
                 "matrix_paths_obs": (8, "|u1", None), "path_features": (9, "<f4", None),
-                "link_features": (10, "<f4", None), "assign_table": (11, "<i4", None), "core_table": (12, "<i4", None)}
+                "link_features": (10, "<f4", None), "assign_table": (11, "<i4", None), "core_table": (12, "<i4", None),
+                "block_table": (13, "<i4", None), "block_mask": (14, "|b1", None)}
     # The views of the pending service: [num_envs, dim] rows of the last call at the device pitch.  name -> (the message while no
     # call has been made, (dim, pitch in items) of those rows, item size).  Every mask layout and every j of the path features has
     # a buffer of its own: a view taken after a "joint" call keeps showing the joint rows (as the last "joint" call left them)
@@ -1028,7 +1087,11 @@ class BatchedOpticalEnv:
               "assign_table": ("no assignment table yet: call route_spectrum() (fetch=False only queues it) first",
                                lambda self: (4 * self.assign_table_shape()[0], self.assign_table_shape()[2]), 4),
               "core_table": ("no (path, core) table yet: call route_cores() (fetch=False only queues it) first",
-                             lambda self: (4 * self.core_table_shape()[0], self.core_table_shape()[2]), 4)}
+                             lambda self: (4 * self.core_table_shape()[0], self.core_table_shape()[2]), 4),
+              "block_table": ("no block table yet: call block_table() (fetch=False only queues it) first",
+                              lambda self: (lambda sh: (sh[0] * sh[1], sh[2]))(self.block_table_shape(self._bt_j)), 4),
+              "block_mask": ("no block mask yet: call block_table() (fetch=False only queues it) first",
+                             lambda self: self.block_table_shape(self._bt_j)[3:], 1)}
 
     def device_array(self, name):
         """The batch's device-resident I/O array `name` as an object with `__cuda_array_interface__` (what

@@ -365,7 +365,22 @@ class _SpectrumRules:
         return self._decode(self.batch.route_spectrum(rule, route)[0])
 
 
-class RMSAEnv(_SpectrumRules, _SingleEnv):
+class _BlockActions:
+    """RMSAEnv, RWAEnv and RMCSAEnv: DeepRMSA's (row, free block) action space for the pending service."""
+
+    def block_action(self, action, j=1, modulation=None, placement="first"):
+        """The env's action for block index `action` = row * j + block (BatchedOpticalEnv.select_blocks): the service at the lower
+        ("first") or upper ("last") end of that block of the row's first j fitting free blocks — row = path, RMCSA path * cores +
+        core; the reject action for an index out of range or a block that does not exist."""
+        return self._decode(self.batch.select_blocks(np.array([int(action)], np.int32), j, modulation, placement)[0])
+
+    def block_mask(self, j=1, modulation=None):
+        """The env's row of the block mask (BatchedOpticalEnv.block_table): bool [rows * j + 1], the set columns are the indices
+        block_action() turns into an action that provisions; the last column is the reject action."""
+        return self.batch.block_table(j, modulation)[1][0]
+
+
+class RMSAEnv(_BlockActions, _SpectrumRules, _SingleEnv):
     BATCH_CLS = BatchedRMSAEnv
 
 
@@ -397,7 +412,7 @@ class DeepRMSAEnv(_SingleEnv):
         return action // self.j, action % self.j
 
 
-class RWAEnv(_SpectrumRules, _SingleEnv):
+class RWAEnv(_BlockActions, _SpectrumRules, _SingleEnv):
     BATCH_CLS = BatchedRWAEnv
     DEFAULT_SLOTS = 80
     DEFAULT_REJECTION = True
@@ -440,7 +455,7 @@ class RWAEnv(_SpectrumRules, _SingleEnv):
         return d
 
 
-class RMCSAEnv(_SingleEnv):
+class RMCSAEnv(_BlockActions, _SingleEnv):
     BATCH_CLS = BatchedRMCSAEnv
     POLICY_SAP = "SAP_BM_FC_FF"
 

@@ -390,6 +390,22 @@ class MultiDeviceBatch:
     def core_table_shape(self):
         return self.shards[0].core_table_shape()
 
+    def block_table_shape(self, j=1):
+        return self.shards[0].block_table_shape(j)
+
+    def block_table(self, j=1, modulation=None, fetch=True):
+        """BatchedOpticalEnv.block_table of every shard; the shards' table rows and mask rows concatenated."""
+        out = self._map(lambda r: self.shards[r].block_table(j, modulation, fetch=fetch))
+        return (self._cat([o[0] for o in out]), self._cat([o[1] for o in out])) if fetch else None
+
+    def select_blocks(self, blocks=None, j=1, modulation=None, placement="first", fetch=True):
+        """BatchedOpticalEnv.select_blocks of every shard; `blocks` ([num_envs]) is cut by the shards' bounds."""
+        from .envs import BatchedOpticalEnv
+
+        a = BatchedOpticalEnv.block_indices(blocks, self.num_envs)
+        out = self._map(lambda r: self.shards[r].select_blocks(self._cut(a, r), j, modulation, placement, fetch=fetch))
+        return self._cat(out) if fetch else None
+
     def path_features_shape(self, j=1):
         return self.shards[0].path_features_shape(j)
 

@@ -280,7 +280,8 @@ class OpticalVecEnv:
 
     def __init__(self, batch, info_keywords=("episode_service_blocking_rate", "episode_bit_rate_blocking_rate"),
                  obs_dtype=np.float64, observation="default", max_logged_episodes=1 << 20, monitor_spill_path=None,
-                 rates_only_info=False, path_features_j=1, action_completion=None, spectrum_assignment=None):
+                 rates_only_info=False, path_features_j=1, action_completion=None, spectrum_assignment=None, block_actions=None,
+                 block_placement="first"):
         """observation: "default" (DeepRMSA: its 1-D vector; other families: None, as their Dict observation holds live
         objects), "matrix" (SimpleMatrixObservation built on the device: uint8 [2N + C*E*S]) or "matrix_paths"
         (QoSConstrainedRA only: MatrixObservationWithPaths built on the device, uint8 [E*S*(k+1) + 1]) or "path_features" (RMSA,
@@ -300,6 +301,12 @@ class OpticalVecEnv:
         (Discrete(k + 1), the last action being reject) and the device picks the slot under the rule before it steps the action;
         `action_masks()` is then the batch's "joint" row reduced with any() over each path's S columns (not the "path" row, which
         leaves out s = S - n), plus the reject column.
+        block_actions (RMSA, RWA and RMCSA): None, or j in [1, 8] — DeepRMSA's action space for this family: a one-head agent
+        chooses "row r, block b" as the integer r * j + b of Discrete(rows * j + reject), rows = k (RMCSA: k * cores), and the device
+        places the service in the b-th free block of the row that fits it (batch.select_blocks, at the block's lower end or with
+        block_placement="last" its upper end) before it steps the action; `action_masks()` is then the mask of batch.block_table(j).
+        It excludes action_completion and spectrum_assignment and pairs with observation="path_features", path_features_j=j,
+        which lists the same blocks.
         Out of scope: `batch.copy_envs` under a VecEnv.  The host-side episode accumulators kept here (returns, lengths, the
         episode log) do not follow a copy of env states on the device."""
         self.batch = batch
@@ -326,6 +333,17 @@ class OpticalVecEnv:
 
             BatchedOpticalEnv.assignment_rule(spectrum_assignment)  # (ValueError for an unknown name)
             self.action_space = _space_module().Discrete(batch.k_paths + 1)
+        self.block_actions = None if block_actions is None else int(block_actions)
+        if block_actions is not None:
+            if action_completion is not None or spectrum_assignment is not None:
+                raise ValueError("block_actions excludes action_completion and spectrum_assignment")
+            if getattr(batch, "ENV_TYPE", None) not in (0, 2, 3) or not hasattr(batch, "select_blocks"):
+                raise ValueError("block_actions is defined for RMSA, RWA and RMCSA batches only (DeepRMSA steps block indices natively)")
+            from .envs import BatchedOpticalEnv
+
+            self._block_placement = BatchedOpticalEnv._named_id("placement", BatchedOpticalEnv.BLOCK_PLACEMENTS, block_placement)
+            self._block_cols = batch.block_table_shape(self.block_actions)[3] - 1  # (an error for a j outside 1 .. 8)
+            self.action_space = _space_module().Discrete(self._block_cols + (1 if batch.allow_rejection else 0))
         if observation == "matrix":
             t = batch.topology
             dim = 2 * t.n_nodes + batch.num_spatial_resources * t.n_links * batch.num_spectrum_resources
@@ -387,6 +405,10 @@ class OpticalVecEnv:
         elif self.spectrum_assignment is not None:  # the slot chosen on the device; reject becomes path k, which has no completion
             a = np.asarray(actions).reshape(self.num_envs).astype(np.int64)
             self.batch.assign_spectrum(self.spectrum_assignment, paths=np.minimum(a, self.batch.k_paths).astype(np.int32), fetch=False)
+            self._actions = None
+        elif self.block_actions is not None:  # the block decoded on the device; the reject action is an index beyond the blocks
+            a = np.asarray(actions).reshape(self.num_envs).astype(np.int64)
+            self.batch.select_blocks(np.clip(a, -1, self._block_cols).astype(np.int32), self.block_actions, placement=self._block_placement, fetch=False)
             self._actions = None
         if self._async:
             direct = self._direct()
@@ -600,6 +622,8 @@ class OpticalVecEnv:
             jm = self.batch.action_mask("joint")
             body = jm[:, :-1].reshape(self.num_envs, self.batch.k_paths, self.batch.num_spectrum_resources).any(axis=2)
             return np.concatenate([body, jm[:, -1:]], axis=1)
+        if self.block_actions is not None:
+            return sb3_action_masks(self.batch, self.batch.block_table(self.block_actions)[1], self.action_space)
         return sb3_action_masks(self.batch, self.batch.action_mask("joint"), self.action_space)
 
     def _env_action_masks(self, i):

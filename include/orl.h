@@ -325,6 +325,9 @@ int orl_host_free(void* p);
                                    * own, allocated by its first call; n_elements = 0 before any call */
 #define ORL_BUF_BLOCK_MASK 14     /* u8 [n_envs][pitch]: the mask of the block action space the same call left (mask pitch of
                                    * orl_batch_block_table_shape); one per j beside the table */
+#define ORL_BUF_RELEASE_HORIZONS 15 /* f32 [n_envs][pitch]: rows of the last orl_batch_release_horizons (pitch, in floats, of
+                                   * orl_batch_release_horizons_shape for that call's layout and j); allocated by the first call and
+                                   * replaced by a larger one when a later call needs more; n_elements = 0 before any call */
 int orl_batch_device_buffer(orl_batch* b, int which, void** device_ptr, int64_t* n_elements);
 /* The HIP stream (hipStream_t) the batch queues its launches on.  An agent on the same GPU that queues ITS kernels on this
  * stream too (torch: `torch.cuda.ExternalStream(ptr)`) needs no synchronisation between its network and orl_batch_step: the
@@ -679,6 +682,32 @@ int orl_batch_select_blocks(orl_batch* b, int j, int modulation, int placement,
                             const int32_t* given /* host [n_envs], or NULL = column 0 of ORL_BUF_ACTIONS */,
                             int32_t* actions_out /* host [n_envs][4], or NULL */);
 
+/* Release horizons: for how long each slot stays taken.  The views above describe where the spectrum is free; this one reads the other
+ * half of the state — the pending releases of the env (what orl_batch_get_pending reads back one env at a time) and the holding time
+ * of the pending service — on the device.  For env e with clock now (the arrival time of the pending service, column 0 of
+ * orl_batch_get_services), every row r of orl_batch_path_features' row order (r = p; RMCSA: r = p C + c) and slot s:
+ *   H[r][s] = float32(max over the pending releases v that cover (r, s) of release_time(v) - now), the subtraction in float64 and one
+ *             rounding; 0.0f when no pending release covers it; -1.0f throughout a row whose path does not exist (p >=
+ *             n_paths[src, dst])
+ * v covers (r, s) when its path shares at least one link with path p of the pending pair, its core is c (RMCSA only) and slot(v) <= s <
+ * slot(v) + max(n(v), 1) (an RWA record has n = 0 for its one wavelength).  H[r][s] is the time until slot s is free on every link of
+ * the path if nothing else is provisioned: > 0 exactly where the AND of the path's link rows has the slot taken. */
+#define ORL_HORIZON_SLOTS 0  /* float32 [n_envs][R S + 1]: row r at columns r S .. r S + S - 1; the last column is the pending service's
+                              * holding time as float32; j must be 1 and modulation -1 */
+#define ORL_HORIZON_BLOCKS 1 /* float32 [n_envs][R 2 j + 1]: for block b < j of row r of orl_batch_block_table(j, modulation) columns
+                              * r 2 j + 2 b and + 1 = (left, right) = (H[r][start_b - 1], H[r][start_b + L_b]); a neighbour beyond the
+                              * spectrum's edge (start_b == 0, start_b + L_b == S) is +inf; (-1, -1) for a block that does not exist,
+                              * -1 throughout a row the service cannot use; the last column is the holding time; j = 1 .. 8 */
+/* The device pitch is round_up(dim, 4) floats, the pad columns 0 (ORL_BUF_RELEASE_HORIZONS).  One launch on the batch's stream, LDS
+ * atomics only, no global atomics: with out == NULL and after a first call of at least that size the call neither synchronises nor
+ * allocates — graph-capturable; with `out` the rows are copied out densely and the call synchronises.  Env state, flags and snapshot
+ * bytes do not change.  ORL_E_INVALID, before anything is queued or allocated: QoSConstrainedRA (no slot maps), an unknown layout, j
+ * outside 1 .. 8, ORL_HORIZON_SLOTS with j != 1 or a modulation, a modulation other than -1 outside RMCSA or outside -1 .. M - 1, rows
+ * the kernel's LDS cannot hold.
+ * orl_batch_release_horizons_shape: *rows = R, *width = S or 2 j, *dim = R width + 1, the device pitch in floats. */
+int orl_batch_release_horizons_shape(const orl_batch* b, int layout, int j, int32_t* rows, int32_t* width, int64_t* dim, int64_t* pitch);
+int orl_batch_release_horizons(orl_batch* b, int layout, int j, int modulation, float* out /* host [n_envs][dim], or NULL: stays on the device, no synchronisation */);
+
 /* Snapshot / restore of the complete simulation state of the batch (slot maps, pending releases, RNG, statistics,
  * counters).  The reference has no equivalent (no checkpointing); used for long PPO runs.  The per-env
  * rates (orl_batch_set_rates) are configuration and not part of it. */
@@ -778,6 +807,14 @@ int orl_debug_run_plan(const orl_env_config* cfg, const orl_topology_desc* topo,
  * workgroup, grid, dynamic LDS bytes, path features staged in LDS, link features' slot rows per round (0: whole rows), assignment
  * with occupancy counts.  Returns 13, or 0 for arguments outside every batch. */
 int orl_debug_view_plan(int env_type, int W, int64_t B, int N, int E, int K, int C, int S, int J, int M, int view, int arg, int32_t* out);
+/* The same for the release horizons (csrc/orl_view_plan.h, horizon_plan; tests/test_release_horizons.py), which take a layout
+ * (ORL_HORIZON_*) and a j: out[0..3] = row length (0: no such rows), rows, values per row, device pitch in floats; out[4..9] = accepted
+ * (0: the call refuses the shape, the rest 0), wavefronts and threads per workgroup, grid, dynamic LDS bytes, rows of H per round.
+ * Returns 10, or 0 for arguments outside every batch. */
+int orl_debug_horizon_plan(int env_type, int W, int64_t B, int N, int E, int K, int C, int S, int M, int layout, int j, int32_t* out);
+/* Test aid: rows of H per round for the release horizons of this batch (0: what the plan says; more than the plan's: the plan's), so
+ * that a small shape runs in several rounds. */
+int orl_debug_set_horizon_rows(orl_batch* b, int rows);
 /* Which kernel orl_batch_step launches for this batch: 2 = k_agent (8 lanes per env, the persistent kernel's phases for one
  * step; QoSConstrainedRA: k_agent_qos, from 20 480 envs), 0 = k_step (one wavefront per env). */
 int orl_batch_debug_step_kernel(orl_batch* b);

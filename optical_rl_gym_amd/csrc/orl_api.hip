@@ -139,6 +139,7 @@ __global__ void k_matrix_obs(DevParams P, unsigned char* out) {
 #include "orl_route.h"
 #include "orl_route_cores.h"
 #include "orl_blocks.h"
+#include "orl_horizon.h"  // (and the decode of a release record, which orl_batch_get_pending shares with the kernel)
 #include "orl_link_obs.h"
 #include "orl_view_plan.h"  // view_shape, view_plan: the shape of each view's rows and the geometry of its launch
 
@@ -1256,6 +1257,10 @@ extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_pt
       *device_ptr = b->bt_last ? b->bk_buf[b->bt_last] : nullptr;
       *n_elements = b->bt_last ? B * view_blocks_mask(b->P, b->bt_last).pitch : 0;
       break;
+    case ORL_BUF_RELEASE_HORIZONS:
+      *device_ptr = b->rh_pitch ? b->rh_buf : nullptr;
+      *n_elements = B * b->rh_pitch;
+      break;
     default: return fail(ORL_E_INVALID, "unknown buffer %d", which);
   }
   return ORL_OK;
@@ -1550,6 +1555,51 @@ extern "C" int orl_batch_select_blocks(orl_batch* b, int j, int modulation, int 
   ORL_LAUNCH(select_blocks, b, j, modulation, placement, src, stride);
   HIPCHK(hipGetLastError());
   return actions_to_host(b, actions_out);
+}
+ORL_ABI_CATCH_INT
+
+// release horizons (orl_horizon.h): when each slot of the pending service's rows frees
+static int horizons_check(const orl_batch* b, int layout, int j, int modulation) {
+  if (b->P.env_type == ENV_QOS) return fail(ORL_E_INVALID, "release horizons are not available for QoSConstrainedRA, which has no slot maps (RMSA, DeepRMSA, RWA and RMCSA only)");
+  if (layout != ORL_HORIZON_SLOTS && layout != ORL_HORIZON_BLOCKS) return fail(ORL_E_INVALID, "unknown release-horizon layout %d (ORL_HORIZON_SLOTS = 0, ORL_HORIZON_BLOCKS = 1)", layout);
+  if (j < 1 || j > 8) return fail(ORL_E_INVALID, "release horizons list j = 1 .. 8 blocks per row, got j = %d", j);
+  if (layout == ORL_HORIZON_SLOTS && (j != 1 || modulation != -1))
+    return fail(ORL_E_INVALID, "ORL_HORIZON_SLOTS takes neither a block count nor a modulation (pass j = 1 and -1)");
+  if (modulation != -1 && b->P.env_type != ENV_RMCSA) return fail(ORL_E_INVALID, "a modulation for the release horizons is defined for RMCSA only (pass -1)");
+  if (modulation < -1 || modulation >= b->P.M) return fail(ORL_E_INVALID, "modulation %d outside -1 (each path's best) .. %d", modulation, b->P.M - 1);
+  if (!horizon_plan(b->P, b->wt, layout, j).ok)
+    return fail(ORL_E_INVALID, "release horizons over %d rows of %d slots exceed the kernel's LDS budget", horizon_shape(b->P, layout, j).rows, b->P.S);
+  return ORL_OK;
+}
+
+extern "C" int orl_batch_release_horizons_shape(const orl_batch* b, int layout, int j, int32_t* rows, int32_t* width, int64_t* dim, int64_t* pitch) try {
+  if (!b || !rows || !width || !dim || !pitch) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = horizons_check(b, layout, j, -1)) return rc;
+  const ViewShape sh = horizon_shape(b->P, layout, j);
+  *rows = sh.rows;
+  *width = sh.width;
+  *dim = sh.dim;
+  *pitch = sh.pitch;
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+extern "C" int orl_batch_release_horizons(orl_batch* b, int layout, int j, int modulation, float* out) try {
+  if (!b) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = horizons_check(b, layout, j, modulation)) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  const ViewShape sh = horizon_shape(b->P, layout, j);
+  const size_t bytes = (size_t)(b->P.B * sh.pitch) * sizeof(float);
+  if (bytes > b->rh_cap) {  // a larger buffer; the one it replaces lives on with the batch (a launch on it may still be queued or captured)
+    float* grown = nullptr;
+    if (int rc = view_buffer(b, grown, bytes, "release horizons")) return rc;
+    b->rh_buf = grown;
+    b->rh_cap = bytes;
+  }
+  ORL_LAUNCH(release_horizons, b, b->rh_buf, layout, j, modulation, b->rh_rows);
+  HIPCHK(hipGetLastError());
+  b->rh_pitch = sh.pitch;
+  return view_rows_to_host(b, b->rh_buf, sh, out);
 }
 ORL_ABI_CATCH_INT
 
@@ -2036,16 +2086,15 @@ extern "C" int orl_batch_get_pending(orl_batch* b, int64_t env, int32_t capacity
   for (int i = 0; i < hwm && i < cap; i++) {
     if (!(t[(size_t)i] < INFINITY)) continue;
     if (n < capacity && time_out && rec_out) {
-      const u64 v = inf[(size_t)i];
-      const int pidx = (int)(v & 0xffffffu);
+      const EvRec v = ev_rec_decode(inf[(size_t)i]);  // (orl_horizon.h: the decode k_release_horizons uses)
       time_out[n] = t[(size_t)i];
       int32_t* r = rec_out + 6 * n;
-      r[0] = pidx / b->P.K;                  // src * N + dst
-      r[1] = pidx % b->P.K;                  // path index within the pair
-      r[2] = (int)((v >> 24) & 0xfffu);      // initial slot
-      r[3] = (int)((v >> 36) & 0xffu);       // number of slots
-      r[4] = (int)((v >> 44) & 0x1fu);       // core
-      r[5] = (int)((v >> 49) & 0x7fffu);     // bit rate
+      r[0] = v.pidx / b->P.K;  // src * N + dst
+      r[1] = v.pidx % b->P.K;  // path index within the pair
+      r[2] = v.slot;           // initial slot
+      r[3] = v.n;              // number of slots
+      r[4] = v.core;
+      r[5] = v.bit_rate;
     }
     n++;
   }
@@ -2229,6 +2278,25 @@ extern "C" int orl_debug_view_plan(int env_type, int W, int64_t B, int N, int E,
   return 13;
 }
 catch (...) { return 0; }
+extern "C" int orl_debug_horizon_plan(int env_type, int W, int64_t B, int N, int E, int K, int C, int S, int M, int layout, int j, int32_t* out) try {
+  if (!out || env_type < 0 || env_type > ORL_ENV_QOS || (W != 1 && W != 2 && W != 5 && W != 8) || B < 1 || N < 1 || E < 1 || K < 1 || C < 1 || S < 1 || M < 1)
+    return 0;
+  DevParams P;
+  memset(&P, 0, sizeof P);
+  P.env_type = env_type; P.B = B; P.N = N; P.E = E; P.K = K; P.C = C; P.S = S; P.J = 1; P.M = M;
+  const ViewShape sh = horizon_shape(P, layout, j);
+  const HorizonPlan pl = horizon_plan(P, W, layout, j);
+  const int32_t v[10] = {(int32_t)sh.dim, sh.rows, sh.width, (int32_t)sh.pitch, pl.ok, pl.waves, pl.block, (int32_t)pl.grid, (int32_t)pl.lds_bytes, pl.rows};
+  memcpy(out, v, sizeof v);
+  return 10;
+}
+catch (...) { return 0; }
+extern "C" int orl_debug_set_horizon_rows(orl_batch* b, int rows) try {
+  if (!b || rows < 0) return fail(ORL_E_INVALID, "bad argument");
+  b->rh_rows = rows;
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
 extern "C" int orl_batch_load_spec(orl_batch* b, const char* so_path) try {
   if (!b || !so_path) return fail(ORL_E_INVALID, "null argument");
   if (!b->persist) return fail(ORL_E_INVALID, "this batch does not run the persistent kernel");

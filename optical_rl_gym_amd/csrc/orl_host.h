@@ -113,6 +113,10 @@ struct orl_batch {
   int32_t* bt_buf[9] = {};         // block tables per block count j (1 .. 8): [B][pitch] int32, and their masks [B][pitch] bytes, both allocated
   unsigned char* bk_buf[9] = {};   // by the first orl_batch_block_table of that j (a view of one stays that j's)
   int bt_last = 0;                 // j of the last launch: what ORL_BUF_BLOCK_TABLE and ORL_BUF_BLOCK_MASK hand out (0: none yet)
+  float* rh_buf = nullptr;         // release horizons: [B][pitch] floats of the last orl_batch_release_horizons, rh_cap bytes; allocated by
+  size_t rh_cap = 0;               // the first call, replaced by a larger one when a call needs more; what ORL_BUF_RELEASE_HORIZONS
+  int64_t rh_pitch = 0;            // hands out, at the last call's pitch (0: none yet)
+  int rh_rows = 0;                 // orl_debug_set_horizon_rows: rows of H per round (0: the plan's)
   // orl_batch_copy_envs (as the destination): the pair indices [2][n] on the device and in page-locked memory, grown on demand
   long long* copy_idx = nullptr;
   long long* h_copy_idx = nullptr;
@@ -170,6 +174,8 @@ template <int W> void path_features(orl_batch* b, float* out, int j, int mod);  
 template <int W> void block_table(orl_batch* b, int32_t* table, unsigned char* mask, int j, int mod);
 template <int W> void select_blocks(orl_batch* b, int j, int mod, int placement, const int* given, int gstride);
 template <int W> void link_features(orl_batch* b, float* out);             // k_link_features -> out [B][pitch] floats
+// k_release_horizons -> out [B][pitch] floats in `layout` (ORL_HORIZON_*), in rounds of min(rows, the plan's) rows (0: the plan's)
+template <int W> void release_horizons(orl_batch* b, float* out, int layout, int j, int mod, int rows);
 // k_persist in the form `ch` (the run's choice for the whole batch; use_spec: made for the attached specialisation library) over the
 // env range of view VP up to step `target` of this run, then k_rel_tail, on stream st
 template <int W> void persist(orl_batch* b, const orl::DevParams& VP, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,

@@ -16,6 +16,7 @@
 //   k_route_spectrum routing rules and the per-path assignment table (orl_route.h)      8 lanes per env, lane = path, every path
 //   k_route_cores core and spectrum rules and the (path, core) table of RMCSA (orl_route_cores.h)  8 lanes per env, lane = (path, core), every pair
 //   k_block_table, k_select_blocks  block actions: the first j fitting blocks of every row, their mask, an index -> an action (orl_blocks.h)  8 lanes per env
+//   k_release_horizons when each slot of the pending service's rows frees, from the release table (orl_horizon.h)  one wavefront per env, lanes over releases
 //   k_path_features path-feature observation of the pending service (orl_path_obs.h)    8 lanes per env, rows striped over them
 //   k_link_features per-link feature observation of the pending service (orl_link_obs.h)  8 lanes per env, slot rows striped over them
 //               [what these three views share — and k_qos_matrix_obs of orl_api.hip with them — lives in orl_view.h]
@@ -2061,6 +2062,7 @@ __global__ void __launch_bounds__(256) k_obs8(DevParams P, int with_terminal) {
 #include "orl_route.h"  // k_route_spectrum: every path's winner under a rule as a table, reduced to one action under a routing order
 #include "orl_route_cores.h"  // k_route_cores: RMCSA — every (path, core) pair's winner under a rule as a table, one action under a route
 #include "orl_blocks.h"  // k_block_table, k_select_blocks: DeepRMSA's (row, free block) action space for every slot-map family
+#include "orl_horizon.h"  // k_release_horizons: when each slot of the pending service's rows frees, per slot or per listed block
 #include "orl_path_obs.h"  // k_path_features: the path-feature observation of the pending service (every slot-map family)
 #include "orl_link_obs.h"  // k_link_features: the per-link feature observation of the pending service (every slot-map family)
 #include "orl_qos_obs.h"  // (its kernel is the API unit's: here the LDS size of its wavefront alone)
@@ -2368,6 +2370,18 @@ template <int W> void link_features(orl_batch* b, float* out) {
   ORL_TK(b, "k_link_features");
 }
 
+// k_release_horizons (orl_horizon.h) into `out` ([B][pitch] floats on the device): one wavefront per env, what horizon_plan says, in
+// rounds of the plan's rows of H or of `rows` where that is fewer (orl_debug_set_horizon_rows; the LDS stays the plan's)
+template <int W> void release_horizons(orl_batch* b, float* out, int layout, int j, int mod, int rows) {
+  const DevParams& VP = b->P;
+  const HorizonPlan pl = horizon_plan(VP, W, layout, j);
+  const ViewShape sh = horizon_shape(VP, layout, j);
+  const int per_round = rows > 0 && rows < pl.rows ? rows : pl.rows;
+  hipLaunchKernelGGL((k_release_horizons<W>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, out, layout, j, mod, (int)sh.dim, (int)sh.pitch,
+                     per_round, pl.wave_bytes);
+  ORL_TK(b, "k_release_horizons");
+}
+
 // The persistent kernel in the form `ch` — what persist_choose (orl_persist_form.h) took for the whole batch when the run began:
 // a run in two halves launches the same kernel on both views — over the env range of view VP0.
 template <int W> void persist(orl_batch* b, const DevParams& VP0, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,
@@ -2528,6 +2542,7 @@ template void path_features<ORL_W>(orl_batch*, float*, int, int);
 template void block_table<ORL_W>(orl_batch*, int32_t*, unsigned char*, int, int);
 template void select_blocks<ORL_W>(orl_batch*, int, int, int, const int*, int);
 template void link_features<ORL_W>(orl_batch*, float*);
+template void release_horizons<ORL_W>(orl_batch*, float*, int, int, int, int);
 template void persist<ORL_W>(orl_batch*, const DevParams&, const PersistChoice&, bool, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);
 template void step2<ORL_W>(orl_batch*, int);
 template void agent_step<ORL_W>(orl_batch*, int, int);

@@ -3,7 +3,7 @@
 //
 // Like the form choice (orl_persist_form.h) and the run plan (orl_run_plan.h) both are pure functions of the batch's sizes, pinned
 // without a device by tests/test_view_plan.py (orl_debug_view_plan).  No HIP call in here.  Included behind the views' headers
-// (orl_mask.h, orl_rmcsa_mask.h, orl_assign.h, orl_route.h, orl_route_cores.h, orl_blocks.h, orl_link_obs.h, orl_qos_obs.h), which keep the LDS sizes of one env or wavefront
+// (orl_mask.h, orl_rmcsa_mask.h, orl_assign.h, orl_route.h, orl_route_cores.h, orl_blocks.h, orl_horizon.h, orl_link_obs.h, orl_qos_obs.h), which keep the LDS sizes of one env or wavefront
 // next to the kernels that lay them out; orl_kernels.hip and orl_api.hip both see all of them, their kernels only where they are
 // launched.
 #pragma once
@@ -172,5 +172,55 @@ inline ViewPlan view_plan(const orl::DevParams& P, int W, int view, int arg) {
   r.block = 64 * r.waves;
   r.grid = (unsigned)((P.B + per_wave * r.waves - 1) / (per_wave * r.waves));
   r.lds_bytes = r.waves * wave;
+  return r;
+}
+
+// The release horizons (orl_horizon.h) are planned apart from view_plan: the view takes two arguments (layout, j), and one wavefront
+// serves one env.  dim = rows x (S | 2 j) + 1 float32 (the last column: the pending service's holding time).  dim == 0: no such rows
+// (QoSConstrainedRA; a layout or j out of range; ORL_HORIZON_SLOTS with j != 1).
+inline ViewShape horizon_shape(const orl::DevParams& P, int layout, int j) {
+  ViewShape s = {0, 0, 0, 0, 4};
+  if (P.env_type == orl::ENV_QOS || j < 1 || j > 8 || (layout != ORL_HORIZON_SLOTS && layout != ORL_HORIZON_BLOCKS)) return s;
+  if (layout == ORL_HORIZON_SLOTS && j != 1) return s;
+  s.rows = P.env_type == orl::ENV_RMCSA ? P.K * P.C : P.K;
+  s.width = layout == ORL_HORIZON_SLOTS ? P.S : 2 * j;
+  s.dim = (int64_t)s.rows * s.width + 1;
+  s.pitch = (s.dim + 3) / 4 * 4;
+  return s;
+}
+
+// The launch of k_release_horizons: the most wavefronts per workgroup of 4, 2, 1 whose LDS shares hold all R rows of H beside the link
+// table and (BLOCKS) the output row — one round; where not even one wavefront's 48 KiB do, one wavefront and rounds of the most rows
+// that fit (every round re-reads the env's release table, so fewer rounds come before more wavefronts).  ok == 0: refused — no such
+// rows, or not one row fits beside the rest.
+struct HorizonPlan {
+  bool ok;
+  int waves, block;
+  unsigned grid;
+  size_t lds_bytes;  // dynamic LDS of a workgroup
+  int rows;          // rows of H per round
+  int wave_bytes;    // LDS of one wavefront
+};
+inline HorizonPlan horizon_plan(const orl::DevParams& P, int W, int layout, int j) {
+  (void)W;  // (the kernel is compiled per row width for the block walk; its LDS does not depend on it)
+  HorizonPlan r = {};
+  const ViewShape sh = horizon_shape(P, layout, j);
+  if (!sh.dim) return r;
+  const int64_t stage = layout == ORL_HORIZON_BLOCKS ? sh.pitch : 0;
+  if (stage > (int64_t)(kViewLdsDefault / sizeof(float))) return r;
+  r.waves = view_waves(horizon_wave_lds(P.E, P.S, sh.rows, (int)stage));
+  r.rows = sh.rows;
+  if (!r.waves) {
+    const int64_t left = (int64_t)kViewLdsDefault - (int64_t)horizon_wave_lds(P.E, P.S, 0, (int)stage);
+    r.rows = left < 0 ? 0 : (int)(left / ((int64_t)sizeof(float) * P.S));
+    while (r.rows > 0 && horizon_wave_lds(P.E, P.S, r.rows, (int)stage) > kViewLdsDefault) r.rows--;
+    if (r.rows < 1) return HorizonPlan{};
+    r.waves = 1;
+  }
+  r.ok = true;
+  r.block = 64 * r.waves;
+  r.grid = (unsigned)((P.B + r.waves - 1) / r.waves);
+  r.wave_bytes = (int)horizon_wave_lds(P.E, P.S, r.rows, (int)stage);
+  r.lds_bytes = (size_t)r.waves * r.wave_bytes;
   return r;
 }

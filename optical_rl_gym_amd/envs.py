@@ -1044,6 +1044,46 @@ class BatchedOpticalEnv:
         self._pf_j = j
         return out
 
+    # ---- release horizons (include/orl.h, orl_batch_release_horizons): RMSA, DeepRMSA, RWA and RMCSA --------------------------
+    HORIZON_LAYOUTS = {"slots": 0, "blocks": 1}
+
+    @classmethod
+    def horizon_args(cls, layout, j=1, modulation=None):
+        """(layout id, j, modulation or -1) of release_horizons(); ValueError for an unknown layout name, a j outside 1 .. 8, and
+        layout "slots" with j != 1 or a modulation."""
+        lay, j = cls._named_id("layout", cls.HORIZON_LAYOUTS, layout), int(j)
+        if not 1 <= j <= 8:
+            raise ValueError("release horizons list j = 1 .. 8 blocks per row, got j = %d" % j)
+        if lay == 0 and (j != 1 or modulation is not None):
+            raise ValueError('layout "slots" takes neither a block count j nor a modulation')
+        return lay, j, -1 if modulation is None else int(modulation)
+
+    def release_horizons_shape(self, layout="slots", j=1):
+        """(rows, width, dim, pitch) of the release-horizon rows: rows = k (RMCSA: k * cores), width = S ("slots") or 2 j
+        ("blocks"), dim = rows * width + 1 float32 columns per env, rows of the device buffer pitch FLOATS apart."""
+        lay, j, _ = self.horizon_args(layout, j)
+        r, w, d, p = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        self._ck(self.lib.orl_batch_release_horizons_shape(self._h, lay, j, C.byref(r), C.byref(w), C.byref(d), C.byref(p)))
+        return r.value, w.value, d.value, p.value
+
+    def release_horizons(self, layout="slots", j=1, modulation=None, fetch=True, out=None):
+        """When each slot frees, for every env's pending service, computed on the device from the env's pending releases (what
+        pending(env) reads back one env at a time): float32 [num_envs, dim].  With now = the service's arrival time
+        (services()[:, 0]) and the rows of path_features (r = p; RMCSA: r = p * cores + c), H[r, s] = the largest release_time -
+        now over the running services that hold slot s (RMCSA: in core c) on a link of candidate path p; 0.0 where none does —
+        exactly the free slots of the path's AND-row; -1.0 throughout a row whose path does not exist.  layout "slots": H row by
+        row, dim = rows * S + 1.  layout "blocks": for block b < j of row r of block_table(j, modulation) the pair (H[r, start -
+        1], H[r, start + length]) at columns r * 2 j + 2 b and + 1 — +inf for a neighbour beyond the spectrum's edge, (-1, -1)
+        for a block that does not exist or a row the service cannot use; dim = rows * 2 j + 1.  The last column of both is the
+        pending service's holding time.  `out` (a C-contiguous float32 [num_envs, dim] array) receives the rows instead of a fresh
+        array.  fetch=False only queues the launch on the batch's stream — read the rows in place with
+        device_array("release_horizons") / device_tensor("release_horizons")."""
+        lay, j, mod = self.horizon_args(layout, j, modulation)
+        out = self._view_rows(lambda p: self._ck(self.lib.orl_batch_release_horizons(self._h, lay, j, mod, p)),
+                              lambda: self.release_horizons_shape(lay, j)[2], np.float32, fetch, out)
+        self._rh = (lay, j)
+        return out
+
     # ---- link features (include/orl.h, orl_batch_link_features): RMSA, DeepRMSA, RWA and RMCSA --------------------------------
     def link_features_shape(self):
         """(dim, rows, width, pitch) of the link-feature rows: dim = 1 + 2 N + rows * width float32 columns per env, rows = links
@@ -1071,7 +1111,7 @@ class BatchedOpticalEnv:
                 "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0), "action_mask": (7, "|b1", None),
                 "matrix_paths_obs": (8, "|u1", None), "path_features": (9, "<f4", None),
                 "link_features": (10, "<f4", None), "assign_table": (11, "<i4", None), "core_table": (12, "<i4", None),
-                "block_table": (13, "<i4", None), "block_mask": (14, "|b1", None)}
+                "block_table": (13, "<i4", None), "block_mask": (14, "|b1", None), "release_horizons": (15, "<f4", None)}
     # The views of the pending service: [num_envs, dim] rows of the last call at the device pitch.  name -> (the message while no
     # call has been made, (dim, pitch in items) of those rows, item size).  Every mask layout and every j of the path features has
     # a buffer of its own: a view taken after a "joint" call keeps showing the joint rows (as the last "joint" call left them)
@@ -1091,7 +1131,9 @@ class BatchedOpticalEnv:
               "block_table": ("no block table yet: call block_table() (fetch=False only queues it) first",
                               lambda self: (lambda sh: (sh[0] * sh[1], sh[2]))(self.block_table_shape(self._bt_j)), 4),
               "block_mask": ("no block mask yet: call block_table() (fetch=False only queues it) first",
-                             lambda self: self.block_table_shape(self._bt_j)[3:], 1)}
+                             lambda self: self.block_table_shape(self._bt_j)[3:], 1),
+              "release_horizons": ("no release horizons yet: call release_horizons() (fetch=False only queues it) first",
+                                   lambda self: self.release_horizons_shape(*self._rh)[2:], 4)}
 
     def device_array(self, name):
         """The batch's device-resident I/O array `name` as an object with `__cuda_array_interface__` (what

@@ -380,11 +380,25 @@ class _BlockActions:
         return self.batch.block_table(j, modulation)[1][0]
 
 
-class RMSAEnv(_BlockActions, _SpectrumRules, _SingleEnv):
+class _ReleaseHorizons:
+    """RMSAEnv, DeepRMSAEnv, RWAEnv and RMCSAEnv: when each slot of the pending service's candidate rows frees."""
+
+    def release_horizons(self, layout="slots", j=1, modulation=None):
+        """The env's row of the batch's release horizons (BatchedOpticalEnv.release_horizons), computed on the device, as (H,
+        holding_time): H float32 [rows, S] for layout "slots" — the time until slot s of row r (the path, RMCSA path * cores +
+        core) is free on every link of the path, 0.0 where it is free now, -1.0 for a path that does not exist — or float32 [rows,
+        j, 2] for layout "blocks": (left, right) neighbour horizons of the row's first j fitting free blocks."""
+        rows, width, _, _ = self.batch.release_horizons_shape(layout, j)
+        row = self.batch.release_horizons(layout, j, modulation)[0]
+        blocks = self.batch.horizon_args(layout, j)[0] == 1
+        return row[:-1].reshape((rows, int(j), 2) if blocks else (rows, width)), float(row[-1])
+
+
+class RMSAEnv(_ReleaseHorizons, _BlockActions, _SpectrumRules, _SingleEnv):
     BATCH_CLS = BatchedRMSAEnv
 
 
-class DeepRMSAEnv(_SingleEnv):
+class DeepRMSAEnv(_ReleaseHorizons, _SingleEnv):
     BATCH_CLS = BatchedDeepRMSAEnv
     POLICY_SAP = "SAP"
 
@@ -412,7 +426,7 @@ class DeepRMSAEnv(_SingleEnv):
         return action // self.j, action % self.j
 
 
-class RWAEnv(_BlockActions, _SpectrumRules, _SingleEnv):
+class RWAEnv(_ReleaseHorizons, _BlockActions, _SpectrumRules, _SingleEnv):
     BATCH_CLS = BatchedRWAEnv
     DEFAULT_SLOTS = 80
     DEFAULT_REJECTION = True
@@ -455,7 +469,7 @@ class RWAEnv(_BlockActions, _SpectrumRules, _SingleEnv):
         return d
 
 
-class RMCSAEnv(_BlockActions, _SingleEnv):
+class RMCSAEnv(_ReleaseHorizons, _BlockActions, _SingleEnv):
     BATCH_CLS = BatchedRMCSAEnv
     POLICY_SAP = "SAP_BM_FC_FF"
 

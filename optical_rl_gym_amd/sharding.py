@@ -414,6 +414,14 @@ class MultiDeviceBatch:
         every shard writes its own rows."""
         return self._view_rows(lambda r, **kw: self.shards[r].path_features(j, modulation, **kw), fetch, out)
 
+    def release_horizons_shape(self, layout="slots", j=1):
+        return self.shards[0].release_horizons_shape(layout, j)
+
+    def release_horizons(self, layout="slots", j=1, modulation=None, fetch=True, out=None):
+        """BatchedOpticalEnv.release_horizons of every shard, rows in env order; with `out` ([num_envs, dim] float32, C-contiguous)
+        every shard writes its own rows."""
+        return self._view_rows(lambda r, **kw: self.shards[r].release_horizons(layout, j, modulation, **kw), fetch, out)
+
     def link_features_shape(self):
         return self.shards[0].link_features_shape()
 

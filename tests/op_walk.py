@@ -22,7 +22,11 @@ holding time).  copy_envs gives the destination a copy of the source's list; set
 (cutting it to the snapshot's length would not do once a copy has replaced the list in between); in both cases the oracle env is
 rebuilt by replaying its list from construction.  Rates are configuration: they do not travel with a copy or a restore, so the
 rebuilt env gets its own current rates back as one more entry.  copy_envs(keep_rng=True) cannot be modelled by replay — the
-destination keeps the position of its own streams — and stays with tests/test_copy_envs_gpu.py."""
+destination keeps the position of its own streams — and stays with tests/test_copy_envs_gpu.py.
+
+Two more walks per family, the "view walks" (further down), put the device choosers, the block table and the release horizons into
+the same scheme: as queries, and — "step_device" — as a stepping kind whose action the device chose and left in its actions buffer.
+The model restates the chooser's answer from the oracle's state and steps the oracle with it; the entry it records is a plain step."""
 import functools
 from collections import namedtuple
 
@@ -306,7 +310,7 @@ class Walk(namedtuple("Walk", "name fresh items")):
         return [it["kind"] for what, it in self.items if what == "op"]
 
     def steps(self):
-        return sum(it.get("n", 1) for what, it in self.items if what == "op" and it["kind"] in STEPPING)
+        return sum(it.get("n", 1) for what, it in self.items if what == "op" and it["kind"] in STEPPING + ("step_device",))
 
 
 def _seeded_kinds():
@@ -349,10 +353,312 @@ def walks_of(name, segments=None):
 
 
 def walk_of(name, walk, segments=None):
-    return next(w for w in walks_of(name, segments) if w.name == walk)
+    return next(w for w in walks_of(name, segments) + (view_walks_of(name, segments) if walk in VIEW_WALK_NAMES else ()) if w.name == walk)
 
 
 WALK_NAMES = ("fresh0", "fresh1", "fresh2", "seeded", "named")
+
+
+# ---- the device choosers, the block table and the release horizons inside the walks ---------------------------------------------------
+# Two more walks per family that has them (every family but QoSConstrainedRA), built by a builder of their own — its own generator
+# and counters, so that the five walks above stay what they are (tests/test_op_walk.py pins their digests).  The five newer device calls
+# are QUERIES here (view_queries_of: one after every op, rotating per preceding kind, beside the two of the rotation above), and the
+# choosers that leave an action on the device also make a stepping kind: "step_device" — the chooser call(s) with fetch=False, then
+# step(None) or step_async(None) + step_wait().  A walk is  run 37, run 37, F, F,  then  k, F  for every kind k (so that F immediately
+# precedes and follows every kind, a device-resident run and itself included), then the kinds again without F until every view query
+# has followed every kind.  F = step_device; on DeepRMSA, which has no chooser that writes an action, F = step_agent.
+VIEW_WALK_NAMES = ("views_fresh", "views_seeded")
+ENV_TYPE = {"RMSA": 0, "DeepRMSA": 1, "RWA": 2, "RMCSA": 3}
+HORIZON_J, TABLE_J = (1, 3, 8), (1, 2, 4, 8)
+SPECTRUM_VARIANTS = ("route_spectrum", "assign_host", "policy_assign", "select_host", "select_buffer")
+CORE_VARIANTS = ("route_cores_host", "complete_route_cores", "select_host", "select_buffer")
+PAIRS_PER_QUERY = 3  # (rule, route) pairs one route_spectrum / route_cores query asks: a walk has fewer such queries than there are pairs
+FIXED = "fixed"      # RMCSA modulation: route_cores_cases.fixed_modulation of the state the call is made on
+
+
+def view_queries_of(f):
+    """the view query kinds of the family, in the order they rotate"""
+    if f.fam == QOS:
+        return []
+    q = ["release_horizons", "block_table"]
+    if f.fam in ("RMSA", "RWA"):
+        q += ["assign_spectrum", "route_spectrum", "select_blocks"]
+    if f.fam == "RMCSA":
+        q += ["route_cores", "select_blocks"]
+    return q
+
+
+def chooser_variants_of(f):
+    """the ways the family's step_device chooses its action on the device"""
+    return {"RMSA": SPECTRUM_VARIANTS, "RWA": SPECTRUM_VARIANTS, "RMCSA": CORE_VARIANTS}.get(f.fam, ())
+
+
+def view_walk_names(name):
+    return VIEW_WALK_NAMES if view_queries_of(FAMILIES[name]) else ()
+
+
+def rule_route_pairs(f):
+    from tests import route_cores_restate, route_restate
+
+    m = route_cores_restate if f.fam == "RMCSA" else route_restate
+    return [(rule, route) for rule in m.RULES for route in m.ROUTES]
+
+
+class Restated:
+    """The restatements of the choosers and the block table on ONE state (slot maps and pending services, the oracle's or the device's
+    read-back), each prepared once however many queries of the state ask for it."""
+
+    def __init__(self, f, slots_packed, services):
+        from tests.rmcsa_mask_restate import unpack_cores
+
+        self.f, self.topo, self.services = f, slot_agent.topology(), services
+        self.S, self.C = f.kw["num_spectrum_resources"], f.kw.get("num_spatial_resources", 1)
+        self.K, self.n = self.topo.k_paths, len(services)
+        self.env_type = ENV_TYPE[f.fam]
+        self.avail = unpack_cores(slots_packed, self.C, self.topo.n_links, self.S)  # bool [n, C, links, S]
+        self.tab = slot_agent.rmcsa_tables(AGENTS[f.fam]) if f.fam == "RMCSA" else None
+        self._made = {}
+
+    def once(self, key, make):
+        if key not in self._made:
+            self._made[key] = make()
+        return self._made[key]
+
+    def modulation(self, mod):
+        from tests import route_cores_cases
+
+        if mod != FIXED:
+            return mod
+        return self.once("fixed", lambda: int(route_cores_cases.fixed_modulation(self.services, self.topo, self.tab)))
+
+    # -- RMSA / RWA
+    def prep(self):
+        from tests import assign_restate
+
+        return self.once("prep", lambda: assign_restate.Prepared(self.env_type, self.avail[:, 0], self.services, self.topo, self.K, self.S))
+
+    def assign(self, rule, paths):
+        from tests import assign_restate
+
+        return assign_restate.assign(self.prep(), rule, 0 if paths is None else 1, paths)
+
+    def route_spectrum(self, rule, route):
+        """(action, table)"""
+        from tests import route_restate
+
+        links = self.once("links", lambda: route_restate.Links(self.avail[:, 0], self.services, self.topo))
+        tab = self.once(("route_table", rule), lambda: route_restate.table(self.prep(), links, rule))
+        return route_restate.route(tab, route, self.K, self.S), tab
+
+    # -- RMCSA
+    def pv(self):
+        from tests.rmcsa_mask_restate import prov_all
+
+        return self.once("pv", lambda: prov_all(self.avail, self.services, self.topo, self.tab))
+
+    def complete(self, g, given):
+        from tests import complete_restate
+
+        return complete_restate.complete(self.pv(), self.services, self.topo, self.tab, g, given)
+
+    def route_cores(self, rule, route, given, mod):
+        """(action, table); given: int [n, g] or None; mod: None, FIXED or a modulation"""
+        from tests import route_cores_restate as rc
+
+        mod = self.modulation(mod)
+        prep = self.once(("core_prep", mod), lambda: rc.Prepared(self.avail, self.services, self.topo, self.tab, modulation=mod, pv=self.pv()))
+        tab = self.once(("core_table", rule, mod), lambda: rc.table(prep, rule))
+        return rc.route(prep, tab, route, given), tab
+
+    # -- block actions
+    def rows(self, mod=None):
+        from tests import block_restate
+
+        mod = self.modulation(mod)
+        return self.once(("rows", mod), lambda: block_restate.Rows(self.env_type, self.avail, self.services, self.topo, self.tab, mod))
+
+    def block_table(self, j, mod=None):
+        """(table, mask)"""
+        from tests import block_restate
+
+        rows = self.rows(mod)
+        return block_restate.table(rows, j), block_restate.mask(rows, j, bool(self.f.kw.get("allow_rejection")))
+
+    def select(self, it):
+        """(indices, actions) of a select_blocks query or step_device variant: the indices are drawn on THIS state"""
+        from tests import block_restate
+
+        rows = self.rows(it["mod"])
+        idx = block_restate.draw_indices(rows, it["j"], np.random.default_rng(it["seed"]))
+        return idx, block_restate.select(rows, it["j"], idx, it["placement"])
+
+    def chosen(self, op, policy):
+        """-> (the restated action int32 [n, 4] of a step_device op, what the device side needs beside the op: indices, modulation);
+        policy(name) -> the heuristic's actions on the same state"""
+        v, extra = op["variant"], {}
+        if v == "route_spectrum":
+            a = self.route_spectrum(op["rule"], op["route"])[0]
+        elif v == "assign_host":
+            a = self.assign(op["rule"], op["paths"])
+        elif v == "policy_assign":  # column 0 of the heuristic's action is the path
+            a = self.assign(op["rule"], policy(op["policy"])[:, 0])
+        elif v in ("select_host", "select_buffer"):
+            extra["indices"], a = self.select(op)
+            extra["modulation"] = self.modulation(op["mod"])
+        elif v == "route_cores_host":
+            a = self.route_cores(op["rule"], op["route"], op["given"], op["mod"])[0]
+            extra["modulation"] = self.modulation(op["mod"])
+        else:
+            assert v == "complete_route_cores"  # columns 0 and 2 of the completion: (path, core)
+            done = self.complete(2, op["given"])
+            a = self.route_cores(op["rule"], op["route"], done[:, [0, 2]], None)[0]
+        return a.astype(np.int32), extra
+
+    @property
+    def reject(self):
+        return (self.K, len(self.tab["lmax_xt"]), self.C, self.S) if self.f.fam == "RMCSA" else (self.K, self.S, 0, 0)
+
+
+class _ViewBuilder(_Builder):
+    """The arguments of the view walks: a generator and counters of its own"""
+
+    def __init__(self, f, seed, segments=None):
+        super().__init__(f, seed, segments)
+        self.qcount["step_device"] = 0
+        self.views = view_queries_of(f)
+        self.vcount = {k: 0 for k in self.qcount}
+        self.pairs = rule_route_pairs(f)
+        self.filler = "step_device" if chooser_variants_of(f) else "step_agent"
+
+    def mod(self, what):
+        return (None, FIXED)[self.turn(what, 2)] if self.f.fam == "RMCSA" else None
+
+    def given(self, what):
+        """a prefix of route_cores_cases.draw_given, g = 0, 1, 2 in rotation (g = 0: None)"""
+        from tests import route_cores_cases
+
+        g = self.turn(what, 3)
+        return route_cores_cases.draw_given(self.n, 5, self.f.kw["num_spatial_resources"], g, shift=self.turn(what + "_shift", 1 << 30)) if g else None
+
+    def host_paths(self):
+        """a path per env in [0, k); k itself, a negative one and an in-range one at three envs drawn for it"""
+        p = self.rng.integers(0, 5, self.n).astype(np.int32)
+        at = self.rng.choice(self.n, 3, replace=False)
+        p[at] = (5, -1 - int(self.rng.integers(3)), int(self.rng.integers(5)))
+        return p
+
+    def blocks(self, what):
+        c = self.turn(what, 1 << 30)  # every (placement, modulation) pair, j moving against them
+        return dict(j=TABLE_J[(c // 4 + c) % 4], placement=("first", "last")[c % 2], mod=(None, FIXED)[(c // 2) % 2] if self.f.fam == "RMCSA" else None,
+                    seed=int(self.rng.integers(1 << 31)))
+
+    def op(self, kind, walk_state, **fixed):
+        if kind == "set_state" and "snapshot" not in fixed:
+            fixed["snapshot"] = walk_state["snapshots"] - 1
+        if kind != "step_device":
+            return super().op(kind, walk_state, **fixed)
+        from tests import assign_restate
+
+        f, variants = self.f, chooser_variants_of(self.f)
+        c = self.turn("step_device", 1 << 30)  # every variant under both forms of the step
+        v = variants[c % len(variants)]
+        op = dict(kind=kind, variant=v, form=("step", "step_async")[(c // len(variants)) % 2], policy=f.policy)
+        if v in ("route_spectrum", "route_cores_host", "complete_route_cores"):
+            op["rule"], op["route"] = self.pairs[(4 * self.turn("sd_pair", 1 << 30)) % len(self.pairs)]  # (4: coprime to 21 and 25)
+        if v in ("assign_host", "policy_assign"):
+            op["rule"] = assign_restate.RULES[self.turn("sd_rule", len(assign_restate.RULES))]
+        if v == "assign_host":
+            op["paths"] = self.host_paths()
+        elif v == "policy_assign":
+            op["policy"] = f.policies[self.turn("sd_policy", len(f.policies))]
+        elif v in ("select_host", "select_buffer"):
+            op.update(self.blocks("sd_blocks"))
+        elif v == "route_cores_host":
+            op["given"], op["mod"] = self.given("sd_given"), self.mod("sd_mod")
+        elif v == "complete_route_cores":
+            op["given"] = np.stack([self.rng.integers(0, 5, self.n), self.rng.integers(0, 6, self.n)], axis=1).astype(np.int32)
+        return op
+
+    def view_query(self, name):
+        from tests import assign_restate
+
+        q = dict(q=name)
+        if name == "release_horizons":
+            q["j"], q["mod"] = HORIZON_J[self.turn("rh_j", 3)], self.mod("rh_mod")
+        elif name == "block_table":
+            c = self.turn("bt", 1 << 30)
+            q["j"], q["mod"] = TABLE_J[c % 4], (None, FIXED)[(c // 4) % 2] if self.f.fam == "RMCSA" else None
+        elif name == "assign_spectrum":
+            q["rule"] = assign_restate.RULES[self.turn("as_rule", len(assign_restate.RULES))]
+            q["source"] = ("none", "host", "buffer")[self.turn("as_source", 3)]
+            q["paths"] = None if q["source"] == "none" else self.host_paths()
+        elif name in ("route_spectrum", "route_cores"):
+            c = self.turn("pairs", 1 << 30)
+            q["pairs"] = [self.pairs[(PAIRS_PER_QUERY * c + i) % len(self.pairs)] for i in range(PAIRS_PER_QUERY)]
+            if name == "route_cores":
+                q["given"], q["mod"] = self.given("rc_given"), self.mod("rc_mod")
+        else:
+            assert name == "select_blocks"
+            q.update(self.blocks("sb"))
+        return q
+
+    def walk(self, name, kinds, fresh, fixed=None):
+        """as _Builder.walk, with one query of the view rotation after the two of the other"""
+        w = super().walk(name, kinds, fresh, fixed)
+        items, last = [], None
+        for k, (what, it) in enumerate(w.items):
+            items.append((what, it))
+            if what == "op":
+                last = it["kind"]
+            closes = k + 1 == len(w.items) or w.items[k + 1][0] == "op"
+            if what == "q" and closes and last is not None and not (last == "seed" and k == 1):  # (not after the opening snapshot)
+                items.append(("q", self.view_query(self.views[self.vcount[last] % len(self.views)])))
+                self.vcount[last] += 1
+        return Walk(name, fresh, items)
+
+
+def _view_kinds(b, fresh):
+    """-> (kinds, fixed) of a view walk"""
+    n = b.n
+    F, Q = b.filler, len(b.views)
+    kinds = FRESH_KINDS if fresh else FRESH_KINDS + ("seed",)
+    first = ["run", "run", F, F]
+    fixed = {0: dict(n=37), 1: dict(n=37)}
+    for k in kinds:
+        first += [k, F]
+    again = []
+    if fresh:  # twice more without the filler: with the seeded walk's two, five of every kind
+        again = list(kinds) * 2
+    else:      # once more — "run" closes the walk instead —, and seed until it has been followed by every view query
+        rest = [k for k in kinds if k not in ("run", "seed")]
+        for i, k in enumerate(rest):
+            again += [k] + (["seed"] if i % 2 == 0 and again.count("seed") < max(Q - 1, 1) else [])
+        again += ["run"] * 4  # across episode ends
+    seq = first + again
+    at = lambda kind: [i for i, k in enumerate(seq) if k == kind]
+    # the first restore goes back to the walk's first snapshot, across episode ends; the later ones to the latest, which loses least
+    fixed[at("set_state")[0]] = dict(snapshot=0)
+    # the first resets by a mask that selects some envs and spares others
+    fixed[at("reset_soft")[0]] = dict(mask=b.mask("group"))
+    fixed[at("reset_full")[0]] = dict(mask=b.mask("half_group"))
+    if not fresh:
+        for i in at("run")[-4:]:
+            fixed[i] = dict(n=20)
+    return seq, fixed
+
+
+@functools.lru_cache(maxsize=None)
+def view_walks_of(name, segments=None):
+    """the family's view walks: views_fresh (no seed op), views_seeded (opens with seed(mask = 0); seed among the kinds)"""
+    f = FAMILIES[name]
+    if not view_queries_of(f):
+        return ()
+    b = _ViewBuilder(f, 5000 + len(name) + 17 * f.batch, segments)
+    walks = []
+    for wname, fresh in zip(VIEW_WALK_NAMES, (True, False)):
+        kinds, fixed = _view_kinds(b, fresh)
+        walks.append(b.walk(wname, kinds, fresh, fixed))
+    return tuple(walks)
 
 
 # ---- the model ----------------------------------------------------------------------------------------------------------------
@@ -385,6 +691,11 @@ class Model:
         self.episodes = np.zeros(self.n, np.int64)   # finished in the env's present history (ledger); travels with the list
         self.blocked = np.zeros(self.n, bool)        # a heuristic found no room for a service of the env at some op of the walk
         self.reach = dict(copy_into_pending=0, copy_from_64=0, restore_across_episode=0, set_load_on_pending=0)
+        # what the step_device ops and the view queries of the view walks reach (counted by op / query)
+        self.reach.update(chooser_provisions=0, chooser_rejects=0, chooser_differs_from_loop=0, chooser_after_copy=0, chooser_after_masked_reset=0,
+                          chooser_after_new_rates=0, chooser_after_restore_across_episode=0, table_row_of_0_blocks=0, table_row_of_j_blocks=0,
+                          horizon_over_64_pending=0)
+        self.prev = {}  # what the previous op did to some env: copy, masked_reset, new_rates, restore_across_episode
 
     # -- one entry on one oracle env: the only way an oracle env is ever changed
     def do(self, o, e, replay=True):
@@ -440,7 +751,20 @@ class Model:
     def apply(self, op):
         kind, rec = op["kind"], dict(op)
         refused = self._refused() if kind in HEURISTIC else None
-        if kind == "run":
+        prev, self.prev = self.prev, {}
+        if kind == "step_device":
+            R = self.restated()
+            a, extra = R.chosen(op, self.policy)
+            loop = self.policy(self.f.policy).astype(np.int32)
+            rec.update(extra)
+            rec["actions"], rec["out"] = a, self._step(a)
+            width = len(self.bounds)
+            self.reach["chooser_provisions"] += bool((rec["out"][1] > 0).any())
+            self.reach["chooser_rejects"] += bool((a == np.array(R.reject, np.int32)).all(axis=1).any())
+            self.reach["chooser_differs_from_loop"] += bool((a[:, :width] != loop[:, :width]).any())
+            for what in ("copy", "masked_reset", "new_rates", "restore_across_episode"):
+                self.reach["chooser_after_" + what] += bool(prev.get(what))
+        elif kind == "run":
             for i in range(self.n):
                 self.add(i, ("run", op["policy"], op["n"]))
         elif kind in STEPPING:
@@ -455,6 +779,7 @@ class Model:
         elif kind in ("reset_soft", "reset_full"):
             for i in self.selected(op["mask"]):
                 self.add(i, ("reset", kind == "reset_full"))
+            self.prev["masked_reset"] = op["mask"] is not None and 0 < int(np.sum(op["mask"])) < self.n
         elif kind == "seed":
             for i in self.selected(op["mask"]):
                 self.add(i, ("seed", op["seeds"][i]))
@@ -468,11 +793,13 @@ class Model:
                 self.rates[i] = new
                 self.add(i, ("rates",) + new)
             self.reach["set_load_on_pending"] += changed > 0
+            self.prev["new_rates"] = changed > 0
         elif kind == "set_state":
             lists, episodes = self.snaps[op["snapshot"]]
             # back across an episode end: the snapshot is the env's own past (a prefix of its list) and an episode has ended since
             own = [tuple(self.lists[i][:len(lists[i])]) == lists[i] for i in range(self.n)]
-            self.reach["restore_across_episode"] += any(own[i] and self.episodes[i] > episodes[i] for i in range(self.n))
+            self.prev["restore_across_episode"] = any(own[i] and self.episodes[i] > episodes[i] for i in range(self.n))
+            self.reach["restore_across_episode"] += self.prev["restore_across_episode"]
             for i in range(self.n):
                 if tuple(self.lists[i]) != lists[i]:
                     self.lists[i] = list(lists[i])
@@ -488,6 +815,7 @@ class Model:
                 self.lists[d] = lst
                 self._rebuilt(d)
             self.episodes[op["dst"]] = self.episodes[op["src"]]
+            self.prev["copy"] = len(op["dst"]) > 0
         if refused is not None:
             self.blocked |= self._refused() > refused
         return rec
@@ -499,6 +827,23 @@ class Model:
     def _rebuilt(self, i):
         self.envs[i] = self.rebuild(i)
         self.add(i, ("rates",) + self.rates[i])
+
+    def restated(self):
+        """the restatements on the oracle's present state"""
+        state = self.readback()
+        return Restated(self.f, state["slots_packed"], state["services"])
+
+    def view_reach(self, q):
+        """counts what a view query of a view walk finds in the oracle's present state"""
+        from tests import block_restate
+
+        if q["q"] == "block_table":
+            rows = self.restated().rows(q["mod"])
+            blocks = [len(block_restate.blocks_of(rows, i, r)) for i in range(rows.n) for r in range(rows.R)]  # (a row the service cannot use: 0)
+            self.reach["table_row_of_0_blocks"] += any(b == 0 for b in blocks)
+            self.reach["table_row_of_j_blocks"] += any(b >= q["j"] for b in blocks)
+        elif q["q"] == "release_horizons":
+            self.reach["horizon_over_64_pending"] += bool((self.readback()["active"] > 64).any())
 
     def snapshot(self):
         self.snaps.append(([tuple(lst) for lst in self.lists], self.episodes.copy()))
@@ -531,4 +876,6 @@ def drive_oracle(name, walk, ledger=True):
             m.apply(it)
         elif it["q"] == "get_state":
             m.snapshot()
+        elif it["q"] in ("block_table", "release_horizons"):
+            m.view_reach(it)
     return m

@@ -328,6 +328,11 @@ int orl_host_free(void* p);
 #define ORL_BUF_RELEASE_HORIZONS 15 /* f32 [n_envs][pitch]: rows of the last orl_batch_release_horizons (pitch, in floats, of
                                    * orl_batch_release_horizons_shape for that call's layout and j); allocated by the first call and
                                    * replaced by a larger one when a later call needs more; n_elements = 0 before any call */
+#define ORL_BUF_PATH_CAPACITY 16   /* i32 [n_envs][pitch]: rows of the last orl_batch_network_capacity(ORL_CAPACITY_PATHS) */
+#define ORL_BUF_SERVICEABLE 17     /* u8 [n_envs][pitch]: rows of the last orl_batch_network_capacity(ORL_CAPACITY_SERVICEABLE) */
+#define ORL_BUF_CAPACITY_COUNTS 18 /* i32 [n_envs][pitch]: rows of the last orl_batch_network_capacity(ORL_CAPACITY_COUNTS); each of
+                                    * the three is a buffer of its own at its layout's pitch (orl_batch_network_capacity_shape),
+                                    * allocated by that layout's first call; n_elements = 0 before it */
 int orl_batch_device_buffer(orl_batch* b, int which, void** device_ptr, int64_t* n_elements);
 /* The HIP stream (hipStream_t) the batch queues its launches on.  An agent on the same GPU that queues ITS kernels on this
  * stream too (torch: `torch.cuda.ExternalStream(ptr)`) needs no synchronisation between its network and orl_batch_step: the
@@ -708,6 +713,43 @@ int orl_batch_select_blocks(orl_batch* b, int j, int modulation, int placement,
 int orl_batch_release_horizons_shape(const orl_batch* b, int layout, int j, int32_t* rows, int32_t* width, int64_t* dim, int64_t* pitch);
 int orl_batch_release_horizons(orl_batch* b, int layout, int j, int modulation, float* out /* host [n_envs][dim], or NULL: stays on the device, no synchronisation */);
 
+/* Network capacity: what the network of an env can still carry.  Every view above describes the pending service on the k candidate
+ * paths of its own node pair; this one describes the env's whole slot map, for every ordered node pair and every bit-rate class.
+ * RMSA, DeepRMSA, RWA and RMCSA.  For env e:
+ *   pairs    an ordered pair (src, dst); its path p < n_paths[src, dst] has index pidx = (src N + dst) K + p, the index of the
+ *            topology's path tables
+ *   cores    C' = C for RMCSA, else 1
+ *   m(pidx, c)  the AND of the path's link rows in core c, bits >= S clear; L(pidx, c) = its longest free run, F(pidx, c) = its
+ *            number of free slots
+ *   classes  RWA: n_cls = 1.  The others: n_cls = n_bit_rates, the rows of the batch's bit-rate table that br_idx of the pending
+ *            service indexes (25 .. 100 Gb/s in the uniform mode, bit_rates in the discrete mode)
+ *   need(pidx, r)  the slots a service of class r needs on the path: RWA 1; RMSA / DeepRMSA n_slots[r][the path's best modulation]
+ *            (get_number_slots); RMCSA n_slots[r][m*], m* the modulation within both reach limits for the path's length and class
+ *            r that needs the fewest slots, ties to the lowest index — the modulation orl_batch_complete_actions and
+ *            orl_batch_route_cores use; no modulation within reach: the path cannot carry the class
+ *   serviceable(pair, r)  some existing path p of the pair, in some core c, has need >= 1 and L(pidx, c) >= need(pidx, r) — the
+ *            rule of the action masks (a start at S - n counts), not the off-by-one of the reference's first-fit loop */
+#define ORL_CAPACITY_PATHS 0        /* int32 [n_envs][N N K C' 2]: row q = pidx C' + c (path-major within a pair, like every other
+                                     * (path, core) table) at columns 2 q, 2 q + 1 = (L, F); (-1, -1) where the path does not exist
+                                     * (p >= n_paths, the diagonal included) */
+#define ORL_CAPACITY_SERVICEABLE 1  /* u8 0/1 [n_envs][N N n_cls]: column (src N + dst) n_cls + r = serviceable((src, dst), r); a pair
+                                     * without paths has 0 in every class column */
+#define ORL_CAPACITY_COUNTS 2       /* int32 [n_envs][n_cls + N N]: the first n_cls columns = per class the number of ordered pairs
+                                     * with n_paths > 0 that are NOT serviceable; the next N N = per pair the number of serviceable
+                                     * classes — the two marginals of the matrix above */
+/* The device pitch is round_up(dim, 4) int32 or round_up(dim, 16) bytes, the pad columns 0.  Each layout has a device buffer of
+ * its own (ORL_BUF_PATH_CAPACITY, ORL_BUF_SERVICEABLE, ORL_BUF_CAPACITY_COUNTS), allocated by its first call: a pointer taken after
+ * one layout's call keeps showing that layout's rows.  One launch on the batch's stream (the first call of layout 1 or 2 also
+ * builds the batch's static need table), one wavefront per env, no atomics: with out == NULL after a first call of that layout the
+ * call neither allocates nor synchronises — graph-capturable; with `out` ([n_envs][dim] of the layout's type) the rows are copied
+ * out densely and the call synchronises.  Env state, flags and snapshot bytes do not change.  ORL_E_INVALID, before anything is
+ * queued or allocated: QoSConstrainedRA (no slot maps), an unknown layout, a topology whose N N K per-path array exceeds the
+ * kernel's LDS.
+ * orl_batch_network_capacity_shape: *rows, *width = (N N K C', 2), (N N, n_cls), (1, n_cls + N N); *dim = rows x width; the device
+ * pitch in items. */
+int orl_batch_network_capacity_shape(const orl_batch* b, int layout, int32_t* rows, int32_t* width, int64_t* dim, int64_t* pitch);
+int orl_batch_network_capacity(orl_batch* b, int layout, void* out /* host [n_envs][dim] of the layout's type, or NULL */);
+
 /* Snapshot / restore of the complete simulation state of the batch (slot maps, pending releases, RNG, statistics,
  * counters).  The reference has no equivalent (no checkpointing); used for long PPO runs.  The per-env
  * rates (orl_batch_set_rates) are configuration and not part of it. */
@@ -812,6 +854,11 @@ int orl_debug_view_plan(int env_type, int W, int64_t B, int N, int E, int K, int
  * (0: the call refuses the shape, the rest 0), wavefronts and threads per workgroup, grid, dynamic LDS bytes, rows of H per round.
  * Returns 10, or 0 for arguments outside every batch. */
 int orl_debug_horizon_plan(int env_type, int W, int64_t B, int N, int E, int K, int C, int S, int M, int layout, int j, int32_t* out);
+/* The same for the network capacity (csrc/orl_view_plan.h, capacity_plan; tests/test_network_capacity.py): out[0..3] = row length
+ * (0: no such rows), rows, width, device pitch in items; out[4..10] = accepted (0: the call refuses the shape), wavefronts and threads
+ * per workgroup, grid, dynamic LDS bytes of a workgroup, slot maps staged in LDS, LDS bytes of one wavefront (= one env).  Returns
+ * 11, or 0 for arguments outside every batch. */
+int orl_debug_capacity_plan(int env_type, int W, int64_t B, int N, int E, int K, int C, int S, int M, int n_br, int layout, int32_t* out);
 /* Test aid: rows of H per round for the release horizons of this batch (0: what the plan says; more than the plan's: the plan's), so
  * that a small shape runs in several rounds. */
 int orl_debug_set_horizon_rows(orl_batch* b, int rows);

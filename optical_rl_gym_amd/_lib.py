@@ -102,6 +102,10 @@ EXPORTS = {
     "orl_batch_release_horizons": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "orl_debug_horizon_plan": (C.c_int, [C.c_int, C.c_int, C.c_int64] + [C.c_int] * 8 + [C.POINTER(C.c_int32)]),
     "orl_debug_set_horizon_rows": (C.c_int, [C.c_void_p, C.c_int]),
+    "orl_batch_network_capacity_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64),
+                                                   C.POINTER(C.c_int64)]),
+    "orl_batch_network_capacity": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "orl_debug_capacity_plan": (C.c_int, [C.c_int, C.c_int, C.c_int64] + [C.c_int] * 8 + [C.POINTER(C.c_int32)]),
     "orl_batch_path_features_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "orl_batch_path_features": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "orl_batch_link_features_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -140,6 +140,7 @@ __global__ void k_matrix_obs(DevParams P, unsigned char* out) {
 #include "orl_route_cores.h"
 #include "orl_blocks.h"
 #include "orl_horizon.h"  // (and the decode of a release record, which orl_batch_get_pending shares with the kernel)
+#include "orl_capacity.h"
 #include "orl_link_obs.h"
 #include "orl_view_plan.h"  // view_shape, view_plan: the shape of each view's rows and the geometry of its launch
 
@@ -1261,6 +1262,13 @@ extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_pt
       *device_ptr = b->rh_pitch ? b->rh_buf : nullptr;
       *n_elements = B * b->rh_pitch;
       break;
+    case ORL_BUF_PATH_CAPACITY:
+    case ORL_BUF_SERVICEABLE:
+    case ORL_BUF_CAPACITY_COUNTS: {
+      const int layout = which - ORL_BUF_PATH_CAPACITY;
+      *device_ptr = b->cap_buf[layout];
+      *n_elements = b->cap_buf[layout] ? B * capacity_shape(b->P, layout).pitch : 0;
+    } break;
     default: return fail(ORL_E_INVALID, "unknown buffer %d", which);
   }
   return ORL_OK;
@@ -1600,6 +1608,48 @@ extern "C" int orl_batch_release_horizons(orl_batch* b, int layout, int j, int m
   HIPCHK(hipGetLastError());
   b->rh_pitch = sh.pitch;
   return view_rows_to_host(b, b->rh_buf, sh, out);
+}
+ORL_ABI_CATCH_INT
+
+// network capacity (orl_capacity.h): every pair's paths on the env's slot maps, and which (pair, class) cells still fit
+static int capacity_check(const orl_batch* b, int layout) {
+  if (b->P.env_type == ENV_QOS) return fail(ORL_E_INVALID, "the network capacity is not available for QoSConstrainedRA, which has no slot maps (RMSA, DeepRMSA, RWA and RMCSA only)");
+  if (layout != ORL_CAPACITY_PATHS && layout != ORL_CAPACITY_SERVICEABLE && layout != ORL_CAPACITY_COUNTS)
+    return fail(ORL_E_INVALID, "unknown network-capacity layout %d (ORL_CAPACITY_PATHS = 0, ORL_CAPACITY_SERVICEABLE = 1, ORL_CAPACITY_COUNTS = 2)", layout);
+  if (!capacity_plan(b->P, b->wt, layout).ok)
+    return fail(ORL_E_INVALID, "the network capacity's per-path array of %d x %d pairs x %d paths (8 bytes per pair and 8 paths; \"counts\": and %d int32) exceeds the kernel's LDS limit of %zu bytes",
+                b->P.N, b->P.N, b->P.K, capacity_classes(b->P) + b->P.N * b->P.N, kViewLdsMax);
+  return ORL_OK;
+}
+
+extern "C" int orl_batch_network_capacity_shape(const orl_batch* b, int layout, int32_t* rows, int32_t* width, int64_t* dim, int64_t* pitch) try {
+  if (!b || !rows || !width || !dim || !pitch) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = capacity_check(b, layout)) return rc;
+  const ViewShape sh = capacity_shape(b->P, layout);
+  *rows = sh.rows;
+  *width = sh.width;
+  *dim = sh.dim;
+  *pitch = sh.pitch;
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+extern "C" int orl_batch_network_capacity(orl_batch* b, int layout, void* out) try {
+  if (!b) return fail(ORL_E_INVALID, "null argument");
+  if (int rc = capacity_check(b, layout)) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  const DevParams& P = b->P;
+  const ViewShape sh = capacity_shape(P, layout);
+  if (layout != ORL_CAPACITY_PATHS && !b->cap_need) {  // static per batch: once; RMCSA's by the one device definition of the reach rule
+    if (int rc = view_buffer(b, b->cap_need, capacity_need_bytes(P.N, P.K, capacity_classes(P)), "network capacity (slots per pair, class and path)")) return rc;
+    ORL_LAUNCH(capacity_need, b, b->cap_need);
+    HIPCHK(hipGetLastError());
+  }
+  const unsigned char* need = layout == ORL_CAPACITY_PATHS ? nullptr : b->cap_need;
+  if (int rc = view_buffer(b, b->cap_buf[layout], (size_t)(P.B * sh.pitch) * sh.elem_bytes, "network capacity")) return rc;
+  ORL_LAUNCH(network_capacity, b, b->cap_buf[layout], need, layout);
+  HIPCHK(hipGetLastError());
+  return view_rows_to_host(b, b->cap_buf[layout], sh, out);
 }
 ORL_ABI_CATCH_INT
 
@@ -2289,6 +2339,19 @@ extern "C" int orl_debug_horizon_plan(int env_type, int W, int64_t B, int N, int
   const int32_t v[10] = {(int32_t)sh.dim, sh.rows, sh.width, (int32_t)sh.pitch, pl.ok, pl.waves, pl.block, (int32_t)pl.grid, (int32_t)pl.lds_bytes, pl.rows};
   memcpy(out, v, sizeof v);
   return 10;
+}
+catch (...) { return 0; }
+extern "C" int orl_debug_capacity_plan(int env_type, int W, int64_t B, int N, int E, int K, int C, int S, int M, int n_br, int layout, int32_t* out) try {
+  if (!out || env_type < 0 || env_type > ORL_ENV_QOS || (W != 1 && W != 2 && W != 5 && W != 8) || B < 1 || N < 1 || E < 1 || K < 1 || C < 1 || S < 1 || M < 1 || n_br < 1)
+    return 0;
+  DevParams P;
+  memset(&P, 0, sizeof P);
+  P.env_type = env_type; P.B = B; P.N = N; P.E = E; P.K = K; P.C = C; P.S = S; P.J = 1; P.M = M; P.n_br = n_br;
+  const ViewShape sh = capacity_shape(P, layout);
+  const CapacityPlan pl = capacity_plan(P, W, layout);
+  const int32_t v[11] = {(int32_t)sh.dim, sh.rows, sh.width, (int32_t)sh.pitch, pl.ok, pl.waves, pl.block, (int32_t)pl.grid, (int32_t)pl.lds_bytes, pl.staged, pl.wave_bytes};
+  memcpy(out, v, sizeof v);
+  return 11;
 }
 catch (...) { return 0; }
 extern "C" int orl_debug_set_horizon_rows(orl_batch* b, int rows) try {

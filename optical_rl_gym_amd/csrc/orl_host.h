@@ -117,6 +117,8 @@ struct orl_batch {
   size_t rh_cap = 0;               // the first call, replaced by a larger one when a call needs more; what ORL_BUF_RELEASE_HORIZONS
   int64_t rh_pitch = 0;            // hands out, at the last call's pitch (0: none yet)
   int rh_rows = 0;                 // orl_debug_set_horizon_rows: rows of H per round (0: the plan's)
+  void* cap_buf[3] = {};           // network capacity: [B][pitch] rows per layout (ORL_CAPACITY_*), each allocated by that layout's first call
+  unsigned char* cap_need = nullptr;  // need(pidx, r), static per batch: [N N][n_cls][round_up(K, 8)] bytes, built by the first call that reads it
   // orl_batch_copy_envs (as the destination): the pair indices [2][n] on the device and in page-locked memory, grown on demand
   long long* copy_idx = nullptr;
   long long* h_copy_idx = nullptr;
@@ -176,6 +178,9 @@ template <int W> void select_blocks(orl_batch* b, int j, int mod, int placement,
 template <int W> void link_features(orl_batch* b, float* out);             // k_link_features -> out [B][pitch] floats
 // k_release_horizons -> out [B][pitch] floats in `layout` (ORL_HORIZON_*), in rounds of min(rows, the plan's) rows (0: the plan's)
 template <int W> void release_horizons(orl_batch* b, float* out, int layout, int j, int mod, int rows);
+// k_network_capacity -> out [B][pitch] of the layout's type (ORL_CAPACITY_*); need: the batch's need table (null for ORL_CAPACITY_PATHS)
+template <int W> void network_capacity(orl_batch* b, void* out, const unsigned char* need, int layout);
+template <int W> void capacity_need(orl_batch* b, unsigned char* need);  // k_capacity_need -> need [N N][n_cls][round_up(K, 8)]
 // k_persist in the form `ch` (the run's choice for the whole batch; use_spec: made for the attached specialisation library) over the
 // env range of view VP up to step `target` of this run, then k_rel_tail, on stream st
 template <int W> void persist(orl_batch* b, const orl::DevParams& VP, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,

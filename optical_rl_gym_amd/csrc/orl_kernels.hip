@@ -17,6 +17,7 @@
 //   k_route_cores core and spectrum rules and the (path, core) table of RMCSA (orl_route_cores.h)  8 lanes per env, lane = (path, core), every pair
 //   k_block_table, k_select_blocks  block actions: the first j fitting blocks of every row, their mask, an index -> an action (orl_blocks.h)  8 lanes per env
 //   k_release_horizons when each slot of the pending service's rows frees, from the release table (orl_horizon.h)  one wavefront per env, lanes over releases
+//   k_network_capacity (L, F) of every pair's paths, which (pair, class) cells fit, their marginals (orl_capacity.h)  one wavefront per env, lanes over all paths of one slot map
 //   k_path_features path-feature observation of the pending service (orl_path_obs.h)    8 lanes per env, rows striped over them
 //   k_link_features per-link feature observation of the pending service (orl_link_obs.h)  8 lanes per env, slot rows striped over them
 //               [what these three views share — and k_qos_matrix_obs of orl_api.hip with them — lives in orl_view.h]
@@ -2063,6 +2064,7 @@ __global__ void __launch_bounds__(256) k_obs8(DevParams P, int with_terminal) {
 #include "orl_route_cores.h"  // k_route_cores: RMCSA — every (path, core) pair's winner under a rule as a table, one action under a route
 #include "orl_blocks.h"  // k_block_table, k_select_blocks: DeepRMSA's (row, free block) action space for every slot-map family
 #include "orl_horizon.h"  // k_release_horizons: when each slot of the pending service's rows frees, per slot or per listed block
+#include "orl_capacity.h"  // k_network_capacity: every pair's paths on the env's whole slot map, and what still fits
 #include "orl_path_obs.h"  // k_path_features: the path-feature observation of the pending service (every slot-map family)
 #include "orl_link_obs.h"  // k_link_features: the per-link feature observation of the pending service (every slot-map family)
 #include "orl_qos_obs.h"  // (its kernel is the API unit's: here the LDS size of its wavefront alone)
@@ -2382,6 +2384,32 @@ template <int W> void release_horizons(orl_batch* b, float* out, int layout, int
   ORL_TK(b, "k_release_horizons");
 }
 
+// k_network_capacity (orl_capacity.h) into `out` ([B][pitch] of the layout's type on the device): one wavefront per env, what
+// capacity_plan says; the one geometry that may ask for more than the default LDS
+template <int W> void network_capacity(orl_batch* b, void* out, const unsigned char* need, int layout) {
+  const DevParams& VP = b->P;
+  const CapacityPlan pl = capacity_plan(VP, W, layout);
+  const ViewShape sh = capacity_shape(VP, layout);
+  if (pl.staged) {
+    if (pl.lds_bytes > kViewLdsDefault)
+      hipFuncSetAttribute((const void*)k_network_capacity<W, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+    hipLaunchKernelGGL((k_network_capacity<W, true>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, out, need, layout, capacity_classes(VP),
+                       (int)sh.pitch, pl.wave_bytes);
+  } else {
+    if (pl.lds_bytes > kViewLdsDefault)
+      hipFuncSetAttribute((const void*)k_network_capacity<W, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+    hipLaunchKernelGGL((k_network_capacity<W, false>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, out, need, layout, capacity_classes(VP),
+                       (int)sh.pitch, pl.wave_bytes);
+  }
+  ORL_TK(b, "k_network_capacity");
+}
+template <int W> void capacity_need(orl_batch* b, unsigned char* need) {
+  const DevParams& VP = b->P;
+  const i64 n = (i64)capacity_need_bytes(VP.N, VP.K, capacity_classes(VP));
+  hipLaunchKernelGGL((k_capacity_need<W>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->stream, VP, need, capacity_classes(VP));
+  ORL_TK(b, "k_capacity_need");
+}
+
 // The persistent kernel in the form `ch` — what persist_choose (orl_persist_form.h) took for the whole batch when the run began:
 // a run in two halves launches the same kernel on both views — over the env range of view VP0.
 template <int W> void persist(orl_batch* b, const DevParams& VP0, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,
@@ -2543,6 +2571,8 @@ template void block_table<ORL_W>(orl_batch*, int32_t*, unsigned char*, int, int)
 template void select_blocks<ORL_W>(orl_batch*, int, int, int, const int*, int);
 template void link_features<ORL_W>(orl_batch*, float*);
 template void release_horizons<ORL_W>(orl_batch*, float*, int, int, int, int);
+template void network_capacity<ORL_W>(orl_batch*, void*, const unsigned char*, int);
+template void capacity_need<ORL_W>(orl_batch*, unsigned char*);
 template void persist<ORL_W>(orl_batch*, const DevParams&, const PersistChoice&, bool, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);
 template void step2<ORL_W>(orl_batch*, int);
 template void agent_step<ORL_W>(orl_batch*, int, int);

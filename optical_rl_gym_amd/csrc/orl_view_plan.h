@@ -3,7 +3,7 @@
 //
 // Like the form choice (orl_persist_form.h) and the run plan (orl_run_plan.h) both are pure functions of the batch's sizes, pinned
 // without a device by tests/test_view_plan.py (orl_debug_view_plan).  No HIP call in here.  Included behind the views' headers
-// (orl_mask.h, orl_rmcsa_mask.h, orl_assign.h, orl_route.h, orl_route_cores.h, orl_blocks.h, orl_horizon.h, orl_link_obs.h, orl_qos_obs.h), which keep the LDS sizes of one env or wavefront
+// (orl_mask.h, orl_rmcsa_mask.h, orl_assign.h, orl_route.h, orl_route_cores.h, orl_blocks.h, orl_horizon.h, orl_capacity.h, orl_link_obs.h, orl_qos_obs.h), which keep the LDS sizes of one env or wavefront
 // next to the kernels that lay them out; orl_kernels.hip and orl_api.hip both see all of them, their kernels only where they are
 // launched.
 #pragma once
@@ -221,6 +221,57 @@ inline HorizonPlan horizon_plan(const orl::DevParams& P, int W, int layout, int 
   r.block = 64 * r.waves;
   r.grid = (unsigned)((P.B + r.waves - 1) / r.waves);
   r.wave_bytes = (int)horizon_wave_lds(P.E, P.S, r.rows, (int)stage);
+  r.lds_bytes = (size_t)r.waves * r.wave_bytes;
+  return r;
+}
+
+// The network capacity view (orl_capacity.h) is planned apart as well: one wavefront serves one env and walks the path tables of
+// every pair.  n_cls: the classes of the family (RWA: one; else the rows of the bit-rate table).  dim == 0: no such rows
+// (QoSConstrainedRA, which has no slot maps; an unknown layout).
+inline int capacity_classes(const orl::DevParams& P) { return P.env_type == orl::ENV_RWA ? 1 : P.n_br; }
+inline ViewShape capacity_shape(const orl::DevParams& P, int layout) {
+  ViewShape s = {0, 0, 0, 0, 4};
+  if (P.env_type == orl::ENV_QOS) return s;
+  const int64_t NN = (int64_t)P.N * P.N, cores = P.env_type == orl::ENV_RMCSA ? P.C : 1, n_cls = capacity_classes(P);
+  switch (layout) {
+    case ORL_CAPACITY_PATHS: s.rows = (int)(NN * P.K * cores); s.width = 2; s.dim = 2 * NN * P.K * cores; break;
+    case ORL_CAPACITY_SERVICEABLE: s.rows = (int)NN; s.width = (int)n_cls; s.dim = NN * n_cls; s.elem_bytes = 1; break;
+    case ORL_CAPACITY_COUNTS: s.rows = 1; s.width = (int)(n_cls + NN); s.dim = n_cls + NN; break;
+    default: return s;
+  }
+  const int64_t per16 = 16 / s.elem_bytes;
+  s.pitch = (s.dim + per16 - 1) / per16 * per16;
+  return s;
+}
+
+// The launch of k_network_capacity.  A wavefront keeps in LDS the per-path longest runs (SERVICEABLE, COUNTS), its output row (COUNTS) and,
+// where they fit beside them, the env's slot maps (staged): the most wavefronts per workgroup of 4, 2, 1 whose shares hold all of it
+// within kViewLdsDefault; else one wavefront with all of it within kViewLdsMax; else the maps stay in global memory and the same two
+// rules go for the rest.  ok == 0: refused — no such rows, or one env's per-path array and bit matrix exceed kViewLdsMax.
+struct CapacityPlan {
+  bool ok;
+  int waves, block;
+  unsigned grid;
+  size_t lds_bytes;  // dynamic LDS of a workgroup
+  bool staged;       // the env's slot maps are copied into LDS
+  int wave_bytes;    // LDS of one wavefront
+};
+inline CapacityPlan capacity_plan(const orl::DevParams& P, int W, int layout) {
+  CapacityPlan r = {};
+  const ViewShape sh = capacity_shape(P, layout);
+  if (!sh.dim) return r;
+  const size_t fixed = layout == ORL_CAPACITY_PATHS ? 0 : capacity_path_bytes(P.N, P.K) + (layout == ORL_CAPACITY_COUNTS ? (size_t)sh.pitch * 4 : 0);
+  if (fixed > kViewLdsMax) return r;
+  const size_t maps = capacity_map_bytes(W, P.env_type == orl::ENV_RMCSA ? P.C : 1, P.E);
+  r.waves = view_waves(fixed + maps);
+  r.staged = r.waves != 0;
+  if (!r.waves && fixed + maps <= kViewLdsMax) { r.waves = 1; r.staged = true; }
+  if (!r.waves) r.waves = view_waves(fixed);
+  if (!r.waves) r.waves = 1;
+  r.ok = true;
+  r.block = 64 * r.waves;
+  r.grid = (unsigned)((P.B + r.waves - 1) / r.waves);
+  r.wave_bytes = (int)(fixed + (r.staged ? maps : 0));
   r.lds_bytes = (size_t)r.waves * r.wave_bytes;
   return r;
 }

@@ -1106,12 +1106,46 @@ class BatchedOpticalEnv:
         return self._view_rows(lambda p: self._ck(self.lib.orl_batch_link_features(self._h, p)),
                                lambda: self.link_features_shape()[0], np.float32, fetch, out)
 
+    # ---- network capacity (include/orl.h, orl_batch_network_capacity): RMSA, DeepRMSA, RWA and RMCSA --------------------------
+    CAPACITY_LAYOUTS = {"paths": 0, "serviceable": 1, "counts": 2}
+
+    def network_capacity_shape(self, layout="paths"):
+        """(rows, width, dim, pitch) of the network-capacity rows of `layout`: (N N k C', 2) for "paths", (N N, n_cls) for
+        "serviceable", (1, n_cls + N N) for "counts"; dim = rows * width columns per env, rows of the device buffer pitch ITEMS
+        apart.  C' = cores for RMCSA, else 1; n_cls = 1 for RWA, else the rows of the batch's bit-rate table."""
+        lay = self._named_id("layout", self.CAPACITY_LAYOUTS, layout)
+        r, w, d, p = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        self._ck(self.lib.orl_batch_network_capacity_shape(self._h, lay, C.byref(r), C.byref(w), C.byref(d), C.byref(p)))
+        return r.value, w.value, d.value, p.value
+
+    def network_capacity(self, layout="paths", fetch=True, out=None):
+        """What every env's network can still carry, computed on the device from its slot maps, for EVERY ordered node pair (not the
+        pending one alone): [num_envs, dim].  With pidx = (src * N + dst) * k + p the index of the topology's path tables, C' =
+        cores for RMCSA, else 1, and n_cls classes (RWA: one; else the rows of the bit-rate table, what the pending service's br_idx
+        indexes):
+        "paths"        int32; reshape(num_envs, N, N, k, C', 2): (longest free run, free slots) of the AND of the path's link rows
+                       in core c; (-1, -1) where the path does not exist (p >= n_paths[src, dst], the diagonal included)
+        "serviceable"  bool; reshape(num_envs, N, N, n_cls): True where a service of class r between (src, dst) finds room now —
+                       some path of the pair, in some core, has a free run of the slots class r needs on it (its best modulation;
+                       RMCSA: the fewest-slots modulation within reach, as complete_actions takes it; RWA: one wavelength)
+        "counts"       int32; [:, :n_cls]: per class the ordered pairs with paths that are NOT serviceable; [:, n_cls:].reshape(
+                       num_envs, N, N): per pair its serviceable classes — the marginals of "serviceable"
+        `out` (a C-contiguous [num_envs, dim] array of that type; uint8 for "serviceable") receives the rows instead of a fresh
+        array.  fetch=False only queues the launch on the batch's stream — read the rows in place with device_array / device_tensor
+        ("path_capacity", "serviceable", "capacity_counts"); every layout has a buffer of its own."""
+        lay = self._named_id("layout", self.CAPACITY_LAYOUTS, layout)
+        out = self._view_rows(lambda p: self._ck(self.lib.orl_batch_network_capacity(self._h, lay, p)),
+                              lambda: self.network_capacity_shape(lay)[2], np.uint8 if lay == 1 else np.int32, fetch, out)
+        return out.view(np.bool_) if out is not None and lay == 1 else out
+
     # ---- zero-copy device views (an agent on the same GPU: no PCIe in the loop) -------------------------
     _BUFFERS = {"actions": (0, "<i4", 4), "reward": (1, "<f8", 0), "done": (2, "|u1", 0), "info": (3, "<f8", -1),
                 "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0), "action_mask": (7, "|b1", None),
                 "matrix_paths_obs": (8, "|u1", None), "path_features": (9, "<f4", None),
                 "link_features": (10, "<f4", None), "assign_table": (11, "<i4", None), "core_table": (12, "<i4", None),
                 "block_table": (13, "<i4", None), "block_mask": (14, "|b1", None), "release_horizons": (15, "<f4", None)}
+    # the network capacity's rows, one buffer per layout (a table of their own beside the I/O arrays and the pending service's views)
+    _CAPACITY_BUFFERS = {"path_capacity": (16, "<i4", None), "serviceable": (17, "|b1", None), "capacity_counts": (18, "<i4", None)}
     # The views of the pending service: [num_envs, dim] rows of the last call at the device pitch.  name -> (the message while no
     # call has been made, (dim, pitch in items) of those rows, item size).  Every mask layout and every j of the path features has
     # a buffer of its own: a view taken after a "joint" call keeps showing the joint rows (as the last "joint" call left them)
@@ -1133,13 +1167,19 @@ class BatchedOpticalEnv:
               "block_mask": ("no block mask yet: call block_table() (fetch=False only queues it) first",
                              lambda self: self.block_table_shape(self._bt_j)[3:], 1),
               "release_horizons": ("no release horizons yet: call release_horizons() (fetch=False only queues it) first",
-                                   lambda self: self.release_horizons_shape(*self._rh)[2:], 4)}
+                                   lambda self: self.release_horizons_shape(*self._rh)[2:], 4),
+              "path_capacity": ("no path capacity yet: call network_capacity(\"paths\") (fetch=False only queues it) first",
+                                lambda self: self.network_capacity_shape(0)[2:], 4),
+              "serviceable": ("no serviceable matrix yet: call network_capacity(\"serviceable\") (fetch=False only queues it) first",
+                              lambda self: self.network_capacity_shape(1)[2:], 1),
+              "capacity_counts": ("no capacity counts yet: call network_capacity(\"counts\") (fetch=False only queues it) first",
+                                  lambda self: self.network_capacity_shape(2)[2:], 4)}
 
     def device_array(self, name):
         """The batch's device-resident I/O array `name` as an object with `__cuda_array_interface__` (what
         `torch.as_tensor(x, device="cuda")` and CuPy consume without a copy).  Write actions into "actions", call
         `step(None, fetch=False)`, `sync()`, read "reward" / "done" / "info" / "obs" in place."""
-        which, typestr, cols = self._BUFFERS[name]
+        which, typestr, cols = self._BUFFERS[name] if name in self._BUFFERS else self._CAPACITY_BUFFERS[name]
         ptr, n = C.c_void_p(), C.c_int64()
         self._ck(self.lib.orl_batch_device_buffer(self._h, which, C.byref(ptr), C.byref(n)))
         strides = None

@@ -394,11 +394,30 @@ class _ReleaseHorizons:
         return row[:-1].reshape((rows, int(j), 2) if blocks else (rows, width)), float(row[-1])
 
 
-class RMSAEnv(_ReleaseHorizons, _BlockActions, _SpectrumRules, _SingleEnv):
+class _NetworkCapacity:
+    """RMSAEnv, DeepRMSAEnv, RWAEnv and RMCSAEnv: what the env's network can still carry, for every node pair and class."""
+
+    def network_capacity(self, layout="paths"):
+        """The env's row of the batch's network capacity (BatchedOpticalEnv.network_capacity), computed on the device: "paths" int32
+        [N, N, k, C', 2] of (longest free run, free slots) per path and core, (-1, -1) for a path that does not exist;
+        "serviceable" bool [N, N, n_cls]; "counts" the pair (blocked_pairs int32 [n_cls], serviceable_classes int32 [N, N])."""
+        b = self.batch
+        lay = b._named_id("layout", b.CAPACITY_LAYOUTS, layout)
+        rows, width, _, _ = b.network_capacity_shape(lay)
+        row = b.network_capacity(lay)[0]
+        n, k = b.topology.n_nodes, b.k_paths
+        if lay == 0:
+            return row.reshape(n, n, k, rows // (n * n * k), 2)
+        if lay == 1:
+            return row.reshape(n, n, width)
+        return row[:width - n * n].copy(), row[width - n * n:].reshape(n, n)
+
+
+class RMSAEnv(_NetworkCapacity, _ReleaseHorizons, _BlockActions, _SpectrumRules, _SingleEnv):
     BATCH_CLS = BatchedRMSAEnv
 
 
-class DeepRMSAEnv(_ReleaseHorizons, _SingleEnv):
+class DeepRMSAEnv(_NetworkCapacity, _ReleaseHorizons, _SingleEnv):
     BATCH_CLS = BatchedDeepRMSAEnv
     POLICY_SAP = "SAP"
 
@@ -426,7 +445,7 @@ class DeepRMSAEnv(_ReleaseHorizons, _SingleEnv):
         return action // self.j, action % self.j
 
 
-class RWAEnv(_ReleaseHorizons, _BlockActions, _SpectrumRules, _SingleEnv):
+class RWAEnv(_NetworkCapacity, _ReleaseHorizons, _BlockActions, _SpectrumRules, _SingleEnv):
     BATCH_CLS = BatchedRWAEnv
     DEFAULT_SLOTS = 80
     DEFAULT_REJECTION = True
@@ -469,7 +488,7 @@ class RWAEnv(_ReleaseHorizons, _BlockActions, _SpectrumRules, _SingleEnv):
         return d
 
 
-class RMCSAEnv(_ReleaseHorizons, _BlockActions, _SingleEnv):
+class RMCSAEnv(_NetworkCapacity, _ReleaseHorizons, _BlockActions, _SingleEnv):
     BATCH_CLS = BatchedRMCSAEnv
     POLICY_SAP = "SAP_BM_FC_FF"
 

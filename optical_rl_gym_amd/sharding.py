@@ -422,6 +422,14 @@ class MultiDeviceBatch:
         every shard writes its own rows."""
         return self._view_rows(lambda r, **kw: self.shards[r].release_horizons(layout, j, modulation, **kw), fetch, out)
 
+    def network_capacity_shape(self, layout="paths"):
+        return self.shards[0].network_capacity_shape(layout)
+
+    def network_capacity(self, layout="paths", fetch=True, out=None):
+        """BatchedOpticalEnv.network_capacity of every shard, rows in env order; with `out` ([num_envs, dim] of the layout's type,
+        C-contiguous) every shard writes its own rows."""
+        return self._view_rows(lambda r, **kw: self.shards[r].network_capacity(layout, **kw), fetch, out)
+
     def link_features_shape(self):
         return self.shards[0].link_features_shape()
 

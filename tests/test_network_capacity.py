@@ -1,0 +1,302 @@
+"""The network capacity view (include/orl.h, orl_batch_network_capacity) without a GPU: the launch plan (csrc/orl_view_plan.h,
+capacity_plan) pinned through orl_debug_capacity_plan, the numpy restatement the GPU test compares with (tests/capacity_restate.py)
+against the oracle on the walks of tests/horizon_model.py, the ABI surface and the facades, and the kernel's registers.
+
+Seeds: env e of every walk is seeded horizon_model.SEED0 + e = 4100 + e; loads and steps: horizon_model.WALKS."""
+import ctypes
+import functools
+import os
+import re
+import shutil
+import sys
+
+import numpy as np
+import pytest
+
+from optical_rl_gym_amd import _lib
+from tests import capacity_restate as cap
+from tests import complete_restate as cr
+from tests import horizon_model as hm
+from tests import mask_restate as mr
+from tests import rmcsa_mask_restate as rr
+from tests import slot_agent
+from tests.oracle_backend import OracleBackend
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+needs_hipcc = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+ENV_TYPE = {"RMSA": 0, "DeepRMSA": 1, "RWA": 2, "RMCSA": 3}
+PLAN_FIELDS = ("dim", "rows", "width", "pitch", "ok", "waves", "block", "grid", "lds_bytes", "staged", "wave_bytes")
+N_CHECK = hm.N_ENVS  # envs of a walk the restatement is compared on: all 24
+ROW_STRIDE = {1: 1, 2: 3, 5: 5, 8: 9}  # 64-bit words from one link row to the next in the LDS copy of the slot maps: W | 1
+
+
+def r16(x):
+    return (x + 15) // 16 * 16
+
+
+def plan(lib, *args):
+    out = (ctypes.c_int32 * len(PLAN_FIELDS))()
+    assert lib.orl_debug_capacity_plan(*args, out) == len(PLAN_FIELDS), args
+    return dict(zip(PLAN_FIELDS, out))
+
+
+def expected_plan(env, W, B, N, E, K, C, n_br, layout):
+    """The plan as orl_view_plan.h words it, from the sizes alone"""
+    cores, n_cls, NN = (C if env == 3 else 1), (1 if env == 2 else n_br), N * N
+    dim = (2 * NN * K * cores, NN * n_cls, n_cls + NN)[layout]
+    rows, width = ((NN * K * cores, 2), (NN, n_cls), (1, n_cls + NN))[layout]
+    pitch = r16(dim) if layout == 1 else (dim + 3) // 4 * 4
+    fixed = (0, r16(NN * ((K + 7) // 8 * 8)), r16(NN * ((K + 7) // 8 * 8)) + 4 * pitch)[layout]
+    if fixed > 64 * 1024:
+        return dict(dim=dim, rows=rows, width=width, pitch=pitch, ok=0, waves=0, block=0, grid=0, lds_bytes=0, staged=0, wave_bytes=0)
+    maps = r16(cores * E * ROW_STRIDE[W] * 8)
+    fit = lambda b: next((w for w in (4, 2, 1) if w * b <= 48 * 1024), 0)
+    waves, staged = fit(fixed + maps), 1
+    if not waves and fixed + maps <= 64 * 1024:
+        waves = 1
+    if not waves:
+        waves, staged = fit(fixed) or 1, 0
+    wave = fixed + (maps if staged else 0)
+    return dict(dim=dim, rows=rows, width=width, pitch=pitch, ok=1, waves=waves, block=64 * waves, grid=-(-B // waves), lds_bytes=waves * wave,
+                staged=staged, wave_bytes=wave)
+
+
+@needs_hipcc
+def test_plan_and_shape(golden_dir):
+    """orl_debug_capacity_plan pinned: NSFNET (14 nodes, 22 slot rows, k = 5, 76 classes) at S = 64, 65, 129, 320, 512; germany50 at S = 128;
+    tests/golden/tiny5_k3.npz; RMCSA with 2, 7 and 31 cores; a size that must be refused; QoSConstrainedRA and an unknown layout."""
+    from optical_rl_gym_amd.topology import Topology
+
+    lib = _lib.lib()
+    nsf, ger, tiny = Topology.load("nsfnet_chen"), Topology.load("germany50"), Topology.load(os.path.join(golden_dir, "tiny5_k3.npz"))
+    assert (nsf.n_nodes, nsf.n_links, nsf.k_paths) == (14, 22, 5) and (ger.n_nodes, ger.n_links) == (50, 88) and (tiny.n_nodes, tiny.k_paths) == (5, 3)
+    # the per-env LDS of NSFNET's three layouts at W = 1: the maps alone; the maps and 196 x 8 longest runs (k = 5 padded to 8); and the 272 counts
+    B = 24
+    p0, p1, p2 = (plan(lib, 0, 1, B, 14, 22, 5, 1, 64, 6, 76, lay) for lay in (0, 1, 2))
+    assert p0 == dict(dim=1960, rows=980, width=2, pitch=1960, ok=1, waves=4, block=256, grid=6, lds_bytes=4 * 176, staged=1, wave_bytes=176)
+    assert p1 == dict(dim=14896, rows=196, width=76, pitch=14896, ok=1, waves=4, block=256, grid=6, lds_bytes=4 * 1744, staged=1, wave_bytes=1744)
+    assert p2 == dict(dim=272, rows=1, width=272, pitch=272, ok=1, waves=4, block=256, grid=6, lds_bytes=4 * 2832, staged=1, wave_bytes=2832)
+    seen_waves, seen_staged = set(), set()
+    for env, W, S, topo, C, n_br in ([(0, 1, 64, nsf, 1, 76), (0, 2, 65, nsf, 1, 76), (0, 5, 129, nsf, 1, 76), (0, 5, 320, nsf, 1, 76), (0, 8, 512, nsf, 1, 3),
+                                      (1, 5, 129, nsf, 1, 76), (2, 5, 129, nsf, 1, 1), (2, 8, 512, nsf, 1, 1), (0, 2, 128, ger, 1, 76), (0, 1, 64, tiny, 1, 76),
+                                      (3, 1, 64, nsf, 7, 76), (3, 5, 129, nsf, 2, 76), (3, 1, 64, nsf, 31, 76), (3, 2, 128, nsf, 31, 76), (3, 8, 512, nsf, 31, 76),
+                                      (3, 8, 512, ger, 31, 76)]):  # (the last: 196 kB of slot maps stay in global memory)
+        for layout in (0, 1, 2):
+            for B in (1, 9, 24, 65536):
+                got = plan(lib, env, W, B, topo.n_nodes, topo.n_links, topo.k_paths, C, S, 6, n_br, layout)
+                assert got == expected_plan(env, W, B, topo.n_nodes, topo.n_links, topo.k_paths, C, n_br, layout), (env, W, S, C, layout, B)
+                assert got["ok"] == 1 and got["lds_bytes"] <= 64 * 1024 and got["wave_bytes"] % 16 == 0
+                assert (got["grid"] - 1) * got["waves"] < B <= got["grid"] * got["waves"]
+                seen_waves.add(got["waves"])
+                seen_staged.add(got["staged"])
+    assert seen_waves == {1, 2, 4} and seen_staged == {0, 1}
+    # germany50: 2 500 x 8 longest runs beside 88 rows of 3 words leave room for two wavefronts; with the 2 576 counts, for one
+    g = plan(lib, 0, 2, 4, 50, 88, 5, 1, 128, 6, 76, 1)
+    assert g["waves"] == 2 and g["staged"] == 1 and g["lds_bytes"] == 2 * (20000 + 88 * 3 * 8)
+    g = plan(lib, 0, 2, 4, 50, 88, 5, 1, 128, 6, 76, 2)
+    assert g["waves"] == 1 and g["staged"] == 1 and g["lds_bytes"] == 20000 + 4 * 2576 + 88 * 3 * 8
+    # 31 cores of 22 rows of 9 words: one wavefront, beyond the default 48 KiB
+    g = plan(lib, 3, 8, 4, 14, 22, 5, 31, 512, 6, 76, 1)
+    assert g["waves"] == 1 and g["staged"] == 1 and 48 * 1024 < g["lds_bytes"] == 1568 + 31 * 22 * 9 * 8 <= 64 * 1024
+    # 150 nodes at k = 5: 22 500 x 8 longest runs exceed the 64 KiB a workgroup can ask for; "paths" keeps none and is accepted
+    for layout in (1, 2):
+        r = plan(lib, 0, 1, 8, 150, 400, 5, 1, 64, 6, 76, layout)
+        assert r["ok"] == 0 and r["waves"] == 0 and r["lds_bytes"] == 0 and r["dim"] > 0
+    assert plan(lib, 0, 1, 8, 150, 400, 5, 1, 64, 6, 76, 0)["ok"] == 1
+    zero = dict.fromkeys(PLAN_FIELDS, 0)
+    assert plan(lib, 4, 1, 8, 14, 22, 5, 1, 64, 6, 76, 1) == zero  # QoSConstrainedRA
+    assert plan(lib, 0, 1, 8, 14, 22, 5, 1, 64, 6, 76, 3) == zero and plan(lib, 0, 1, 8, 14, 22, 5, 1, 64, 6, 76, -1) == zero
+    out = (ctypes.c_int32 * len(PLAN_FIELDS))()
+    assert lib.orl_debug_capacity_plan(0, 3, 8, 14, 22, 5, 1, 64, 6, 76, 0, out) == 0  # no row width 3
+
+
+def test_header_and_binding_declare_the_exports():
+    h = open(os.path.join(ROOT, "include", "orl.h")).read()
+    assert re.search(r"int orl_batch_network_capacity_shape\(const orl_batch\* b, int layout, int32_t\* rows, int32_t\* width, int64_t\* dim, int64_t\* pitch\);", h)
+    assert re.search(r"int orl_batch_network_capacity\(orl_batch\* b, int layout, void\* out[^;]*\);", h)
+    assert re.search(r"int orl_debug_capacity_plan\(int env_type, int W, int64_t B, int N, int E, int K, int C, int S, int M, int n_br, int layout, int32_t\* out\);", h)
+    for name, value in (("ORL_BUF_PATH_CAPACITY", "16"), ("ORL_BUF_SERVICEABLE", "17"), ("ORL_BUF_CAPACITY_COUNTS", "18"), ("ORL_CAPACITY_PATHS", "0"),
+                        ("ORL_CAPACITY_SERVICEABLE", "1"), ("ORL_CAPACITY_COUNTS", "2"), ("ORL_BUF_RELEASE_HORIZONS", "15")):
+        assert re.search(r"#define %s\s+%s\b" % (name, value), h), name
+    assert [len(_lib.EXPORTS[n][1]) for n in ("orl_batch_network_capacity_shape", "orl_batch_network_capacity", "orl_debug_capacity_plan")] == [6, 3, 12]
+    from optical_rl_gym_amd import gym_api
+    from optical_rl_gym_amd.envs import BatchedOpticalEnv as B
+    from optical_rl_gym_amd.qos import QoSConstrainedRA
+    from optical_rl_gym_amd.sharding import MultiDeviceBatch
+
+    assert B.CAPACITY_LAYOUTS == {"paths": 0, "serviceable": 1, "counts": 2}
+    assert B._CAPACITY_BUFFERS == {"path_capacity": (16, "<i4", None), "serviceable": (17, "|b1", None), "capacity_counts": (18, "<i4", None)}
+    for name in ("path_capacity", "serviceable", "capacity_counts"):
+        assert re.match(r"no .* yet: call network_capacity\(", B._VIEWS[name][0]), name
+    assert B._BUFFERS["release_horizons"][0] == 15 and not set(B._BUFFERS) & set(B._CAPACITY_BUFFERS)  # what was there stays
+    for cls in (B, MultiDeviceBatch):
+        assert hasattr(cls, "network_capacity") and hasattr(cls, "network_capacity_shape"), cls
+    for cls in (gym_api.RMSAEnv, gym_api.DeepRMSAEnv, gym_api.RWAEnv, gym_api.RMCSAEnv):
+        assert hasattr(cls, "network_capacity"), cls
+    assert not hasattr(QoSConstrainedRA, "network_capacity")
+    with pytest.raises(ValueError, match="layout must be one of"):
+        B._named_id("layout", B.CAPACITY_LAYOUTS, "cells")
+
+
+def test_restatement_on_a_hand_made_state(golden_dir):
+    """tiny5_k3, S = 8: one link of path 0 of a pair busy but for slots 1 - 2 and 5 - 7: L = 3, F = 5 on the paths over it; a class that
+    needs 3 slots is served there, one that needs 4 only over the pair's other path; rows of (-1, -1) for the paths that do not exist"""
+    from optical_rl_gym_amd.topology import Topology
+
+    topo = Topology.load(os.path.join(golden_dir, "tiny5_k3.npz"))
+    N, K, S = topo.n_nodes, topo.k_paths, 8
+    pairs = [(s, d) for s in range(N) for d in range(N) if topo.n_paths[s, d] == 1]
+    src, dst = pairs[0]
+    link = int(topo.path_links[src, dst, 0, 0])
+    avail = np.ones((1, 1, topo.n_links, S), bool)
+    avail[0, 0, link] = [False, True, True, False, False, True, True, True]
+    need = np.ones((N, N, K, 3), np.int64) * np.array([3, 4, 0])
+    paths, svc, counts = cap.restate(avail, topo, need)
+    P = paths.reshape(N, N, K, 1, 2)
+    assert tuple(P[src, dst, 0, 0]) == (3, 5) and tuple(P[src, dst, 1, 0]) == (-1, -1) and (P[np.arange(N), np.arange(N)] == -1).all()
+    over = [(s, d, p) for s in range(N) for d in range(N) for p in range(topo.n_paths[s, d]) if link in topo.path_links[s, d, p, :topo.path_hops[s, d, p]]]
+    assert len(over) > 1 and all(tuple(P[s, d, p, 0]) == (3, 5) for s, d, p in over)
+    free = (P[..., 0, 0] == S) & (P[..., 0, 1] == S)
+    assert free.sum() == topo.n_paths.sum() - len(over)
+    M = svc.reshape(N, N, 3)
+    assert list(M[src, dst]) == [True, False, False] and not M[np.arange(N), np.arange(N)].any() and not M[..., 2].any()
+    blocked = sum(1 for s in range(N) for d in range(N) if topo.n_paths[s, d] > 0 and not M[s, d, 1])
+    assert blocked >= 1 and list(counts[0, :3]) == [0, blocked, int((topo.n_paths > 0).sum())]
+    assert np.array_equal(counts[0, 3:].reshape(N, N), M.sum(axis=2))
+    assert cap.first_fit(avail[0], topo, need, src, dst, 0) == (0, 0, 5, 3) and cap.first_fit(avail[0], topo, need, src, dst, 1) is None
+    assert list(cap.longest_runs(np.array([[1, 1, 0, 1], [0, 0, 0, 0], [1, 1, 1, 1], [0, 1, 1, 1]], bool))) == [2, 0, 4, 3]
+
+
+def pending_cell(fam, services, rates):
+    """(pair index base [n], class [n]) of every env's pending service"""
+    r = np.zeros(len(services), np.int64) if fam == "RWA" else np.array([rates.index(int(b)) for b in services[:, 4]], np.int64)
+    return services[:, 2].astype(np.int64), services[:, 3].astype(np.int64), r
+
+
+def mask_says(fam, tab, avail, services, topo, S):
+    """bool [n]: the family's path-level mask of the pending service has a provisioning column"""
+    if fam == "RMCSA":
+        return rr.restate_rmcsa_fast(avail, services, topo, tab, "path_modulation", allow_rejection=True, fallback=False)[:, :-1].any(axis=1)
+    return mr.restate_fast(ENV_TYPE[fam], avail[:, 0], services, topo, topo.k_paths, S, allow_rejection=True, layout="path", fallback=False)[:, :-1].any(axis=1)
+
+
+@functools.lru_cache(maxsize=None)
+def walked(name):
+    """The named walk on the oracle; at every checkpoint, on every env: the pending pair's cell of "serviceable" is what the
+    family's path-level mask says; "counts" are the marginals; and one more step — the restatement's first fit where the cell is 1, the
+    family's heuristic where it is 0 — is accepted exactly where the cell is 1.  Returns what was seen."""
+    fam, kw, S, n, seeds = hm.walk_config(name)
+    C = kw.get("num_spatial_resources", 1)
+    ora = OracleBackend(fam, slot_agent.TOPOLOGY, seeds, **kw)
+    topo = ora.topology
+    tab = slot_agent.rmcsa_tables(name) if fam == "RMCSA" else None
+    rates = cap.class_rates(fam, kw)
+    need = cap.need_table(fam, topo, rates, tab)
+    model = hm.Model(fam, topo, n, tab)
+    N, n_cls = topo.n_nodes, len(rates)
+    has = topo.n_paths.reshape(-1) > 0
+    seen = dict(checkpoints=0, cell_1=0, cell_0=0, blocked=[], served=[], last_start=0)
+
+    def checkpoint(tag):
+        avail, services = hm.avail_of(ora, C, S), ora.services()
+        k = N_CHECK
+        paths, svc, counts = cap.restate(avail[:k], topo, need)
+        M = svc.reshape(k, N * N, n_cls)
+        assert np.array_equal(counts[:, :n_cls], (has[None, :, None] & ~M).sum(axis=1)) and np.array_equal(counts[:, n_cls:], M.sum(axis=2)), (name, tag)
+        assert not M[:, ~has].any()
+        src, dst, r = pending_cell(fam, services[:k], rates)
+        cell = M[np.arange(k), src * N + dst, r]
+        says = mask_says(fam, tab, avail[:k], services[:k], topo, S)
+        acts = np.array(ora.policy(hm.HEURISTIC[fam]), np.int32).reshape(n, -1).copy()
+        mstar = cr.best_in_reach(services[:k], topo, tab) if fam == "RMCSA" else None
+        for e in range(k):
+            fit = cap.first_fit(avail[e], topo, need, int(src[e]), int(dst[e]), int(r[e]))
+            assert (fit is not None) == bool(cell[e]), (name, tag, e)
+            # RMSA's path mask is the wrapper's first fit over range(0, S - n) (include/orl.h, ORL_MASK_PATH): a service whose only room is
+            # the last n slots is serviceable and has no column there; everywhere else the two are equal
+            only_last = fam == "RMSA" and fit is not None and fit[2] == S - fit[3] and not says[e]
+            seen["last_start"] += int(only_last)
+            assert bool(cell[e]) == bool(says[e]) or only_last, (name, tag, e, fit)
+            if fit is not None:
+                p, c, s, _ = fit
+                acts[e, :] = 0
+                acts[e, :4 if fam == "RMCSA" else 2] = (p, int(mstar[e, p]), c, s) if fam == "RMCSA" else (p, s)
+        rew = hm.step(ora, model, acts)
+        assert np.array_equal(rew[:k] > 0, cell), (name, tag, rew[:k], cell)
+        seen["cell_1"] += int(cell.sum())
+        seen["cell_0"] += int((~cell).sum())
+        seen["blocked"].append(counts[:, :n_cls].sum(axis=1))
+        seen["served"].append(counts[:, n_cls:].sum(axis=1))
+        seen["checkpoints"] += 1
+
+    hm.walk(name, ora, model, checkpoint)
+    return seen, int(has.sum()) * n_cls
+
+
+@pytest.mark.parametrize("name", ["rmsa_nsf_s65", "rwa_nsf_s129", "rmcsa_c7_s64"])
+def test_restatement_against_the_oracle_on_the_walks(name):
+    seen, cells = walked(name)
+    print(name, cells, {k: v for k, v in seen.items() if k not in ("blocked", "served")}, [list(b) for b in seen["blocked"]])
+    assert seen["checkpoints"] >= 6 and seen["cell_1"] > 0
+    if name == "rmsa_nsf_s65":  # (a pending service that finds no room; the other two walks block other pairs' cells, counted below)
+        assert seen["cell_0"] > 0
+
+
+def test_the_walked_states_are_not_trivial():
+    """Conditions on the inputs: after rmsa_nsf_s65's 150 warm-up steps each of the envs seeded 4100 .. 4107 has blocked and serviceable
+    cells (on the oracle: 280 to 1 766 of 13 832, 280 to 1 640 after this test's two extra steps; env 11 of the 24 has none blocked); on
+    rwa_nsf_s129 at 1 500 Erlang after the 1 100 warm-up steps at least one env has a blocked pair; on rmcsa_c7_s64 the reach rule
+    blocks cells in every env."""
+    seen, cells = walked("rmsa_nsf_s65")
+    assert cells == 182 * 76
+    blocked, served = seen["blocked"][2], seen["served"][2]  # the checkpoint at the warm-up's end
+    print("rmsa_nsf_s65", list(blocked), list(served))
+    assert (blocked[:8] > 0).all() and (served > 0).all() and (blocked + served == cells).all()
+    seen, cells = walked("rwa_nsf_s129")
+    blocked = seen["blocked"][2]
+    print("rwa_nsf_s129", list(blocked))
+    assert cells == 182 and (blocked > 0).any() and (seen["served"][2] > 0).all()
+    seen, cells = walked("rmcsa_c7_s64")
+    print("rmcsa_c7_s64", list(seen["blocked"][2]))
+    assert (seen["blocked"][2] > 0).all() and (seen["served"][2] > 0).all()
+
+
+def test_denser_rmsa_state_has_both_kinds_of_cell():
+    """rmsa_nsf_s129 at 220 Erlang after 700 steps under the heuristic (seeds 4100 .. 4107 on the oracle: 2 260 to 4 846 of 13 832 cells
+    blocked): the restatement's counts, and the pending cells against the mask"""
+    fam, kw, S, n, seeds = hm.walk_config("rmsa_nsf_s129")
+    ora = OracleBackend(fam, slot_agent.TOPOLOGY, seeds[:8], **kw)
+    ora.run("SAP_FF", 700)
+    topo, rates = ora.topology, cap.class_rates(fam, kw)
+    need = cap.need_table(fam, topo, rates)
+    avail, services = hm.avail_of(ora, 1, S), ora.services()
+    _, svc, counts = cap.restate(avail, topo, need)
+    blocked = counts[:, :76].sum(axis=1)
+    print("rmsa_nsf_s129", list(blocked))
+    assert (blocked > 0).all() and (blocked < 13832).all() and (blocked + counts[:, 76:].sum(axis=1) == 13832).all()
+    src, dst, r = pending_cell(fam, services, rates)
+    cell = svc.reshape(8, 196, 76)[np.arange(8), src * 14 + dst, r]
+    says = mask_says(fam, None, avail, services, topo, S)
+    for e in np.flatnonzero(cell != says):  # (only the last-start case of ORL_MASK_PATH may differ)
+        fit = cap.first_fit(avail[e], topo, need, int(src[e]), int(dst[e]), int(r[e]))
+        assert cell[e] and fit[2] == S - fit[3], e
+
+
+@needs_hipcc
+def test_kernel_exists_for_every_row_width_without_scratch_or_vgpr_spills():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_regs
+
+    from optical_rl_gym_amd import _build
+
+    found = {}
+    for k in kernel_regs.kernels(_build.build()):
+        m = re.match(r"(?:void )?k_network_capacity<(\d+), (true|false)>", kernel_regs.demangle(k["name"]))
+        if m:
+            found[int(m.group(1)), m.group(2) == "true"] = k
+    assert sorted(found) == sorted((w, s) for w in _build.ROW_WIDTHS for s in (False, True))
+    for key, k in sorted(found.items()):
+        print(key, {x: k[x] for x in ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size")})
+        assert int(k["vgpr_spill_count"]) == 0 and int(k["private_segment_fixed_size"]) == 0, key
+        assert int(k["group_segment_fixed_size"]) == 0, key  # (its LDS is the launch's: capacity_plan)
+        assert int(k["vgpr_count"]) <= 128, key  # four wavefronts of a workgroup per SIMD pair without losing occupancy to registers

@@ -14,8 +14,10 @@ import numpy as np
 import pytest
 
 from optical_rl_gym_amd import _lib
+from tests import capacity_cases as cc
 from tests import capacity_restate as cap
 from tests import complete_restate as cr
+from tests import envelope
 from tests import horizon_model as hm
 from tests import mask_restate as mr
 from tests import rmcsa_mask_restate as rr
@@ -300,3 +302,223 @@ def test_kernel_exists_for_every_row_width_without_scratch_or_vgpr_spills():
         assert int(k["vgpr_spill_count"]) == 0 and int(k["private_segment_fixed_size"]) == 0, key
         assert int(k["group_segment_fixed_size"]) == 0, key  # (its LDS is the launch's: capacity_plan)
         assert int(k["vgpr_count"]) <= 128, key  # four wavefronts of a workgroup per SIMD pair without losing occupancy to registers
+
+
+# ---- the restatement against its definition on the envelope topologies ------------------------------------------------------------
+DEFINITION_RATES = [25, 100, 250]  # on BPSK 3, 9 and 21 slots: within S = 24 and S = 70
+# (golden topology, k, S)
+DEFINITION_CASES = (("ring10c8", 9, 24), ("k6full", 64, 24), ("star129", 5, 24), ("ring31", 2, 70))
+
+
+def plain_run_and_free(link_rows):
+    """(longest free run, free slots) of the AND of the link rows (lists of bool), slot by slot"""
+    L = F = run = 0
+    for s in range(len(link_rows[0])):
+        if all(row[s] for row in link_rows):
+            run += 1
+            F += 1
+            L = max(L, run)
+        else:
+            run = 0
+    return L, F
+
+
+def plain_need(topo, s, d, p, rate):
+    """Slots of a service of `rate` Gb/s on path p of (s, d): its best modulation's, plus the guard band"""
+    se = topo.modulations[int(topo.path_best_mod[s, d, p])].spectral_efficiency
+    return int(np.ceil(rate / (se * 12.5))) + 1
+
+
+def definition_maps(E, S, seed):
+    """bool [5, 1, E, S]: about 30 %, 60 % and 90 % of the slots taken, an empty network and a full one; in the first three one link
+    row all free and one all taken"""
+    rng = np.random.RandomState(seed)
+    avail = np.stack([rng.rand(E, S) >= occ for occ in (0.3, 0.6, 0.9, 0.0, 1.0)])[:, None]
+    for e in range(3):
+        avail[e, 0, (5 * e + 2) % E] = True
+        avail[e, 0, (5 * e + 3) % E] = False
+    assert avail[3].all() and not avail[4].any()
+    return avail
+
+
+@pytest.mark.parametrize("name,k,S", DEFINITION_CASES)
+def test_restatement_equals_the_definition_on_the_envelope_topologies(name, k, S, golden_dir):
+    """cap.restate and cap.need_table at k = 9, 64 and 2 and with n_paths < k, cell by cell against loops over slots, paths and classes:
+    (L, F) of at least 200 rows per topology, all rows of ring31's 30-hop paths among them; "serviceable" by cap.first_fit; "counts"
+    summed from the two.  star129: the pairs of nodes 0, 63, 64 and 128 and 200 random ones, the counts per class over all pairs."""
+    from optical_rl_gym_amd.topology import Topology
+
+    topo = Topology.load(os.path.join(golden_dir, "topo_%s_k%d.npz" % (name, k)))
+    N, K, n_cls = topo.n_nodes, topo.k_paths, len(DEFINITION_RATES)
+    assert K == k and (K != slot_agent.K or name == "star129")
+    rng = np.random.RandomState(N * K)
+    need = cap.need_table("RMSA", topo, DEFINITION_RATES)
+    assert need.shape == (N, N, K, n_cls)
+    avail = definition_maps(topo.n_links, S, 7 * N + K)
+    n = len(avail)
+    paths, svc, counts = cap.restate(avail, topo, need)
+    assert paths.shape == (n, N * N * K * 2) and svc.shape == (n, N * N * n_cls) and counts.shape == (n, n_cls + N * N)
+    P, M = paths.reshape(n, N, N, K, 2), svc.reshape(n, N, N, n_cls)
+    exists = np.arange(K)[None, None, :] < topo.n_paths[:, :, None]
+    assert (P[:, ~exists] == -1).all() and (P[:, exists] >= 0).all()
+    if name == "star129":
+        assert set(np.unique(topo.n_paths)) == {0, 1}
+    rows = [tuple(r) for r in np.argwhere(exists)]
+    must = [r for r in rows if topo.path_hops[r] == 30] if name == "ring31" else []
+    assert name != "ring31" or len(must) >= 31
+    sample = sorted(set(must) | {rows[i] for i in rng.choice(len(rows), min(len(rows), 200), replace=False)})
+    assert len(sample) >= 200
+    lists = avail[:, 0].tolist()
+    for s, d, p in sample:
+        links = [int(l) for l in topo.path_links[s, d, p, :int(topo.path_hops[s, d, p])]]
+        for r, rate in enumerate(DEFINITION_RATES):
+            assert need[s, d, p, r] == plain_need(topo, s, d, p, rate), (name, s, d, p, rate)
+        for e in range(n):
+            assert tuple(P[e, s, d, p]) == plain_run_and_free([lists[e][l] for l in links]), (name, e, s, d, p)
+    if name == "star129":
+        picked = {(s, d) for a in (0, 63, 64, 128) for b in range(N) for s, d in ((a, b), (b, a))}
+        picked |= {(int(i) // N, int(i) % N) for i in rng.choice(N * N, 200, replace=False)}
+    else:
+        picked = {(s, d) for s in range(N) for d in range(N)}
+    fit = np.zeros((n, N, N, n_cls), bool)
+    for s, d in sorted(picked):
+        for e in range(n):
+            for r in range(n_cls):
+                fit[e, s, d, r] = cap.first_fit(avail[e], topo, need, s, d, r) is not None
+            assert list(M[e, s, d]) == list(fit[e, s, d]), (name, e, s, d)
+            assert counts[e, n_cls + s * N + d] == fit[e, s, d].sum(), (name, e, s, d)
+    if name == "star129":  # the counts per class need every pair: the one path of a pair, slot by slot
+        for e in range(n):
+            for s, d in np.argwhere(topo.n_paths > 0):
+                L, _ = plain_run_and_free([lists[e][int(l)] for l in topo.path_links[s, d, 0, :int(topo.path_hops[s, d, 0])]])
+                fit[e, s, d] = [1 <= plain_need(topo, s, d, 0, rate) <= L for rate in DEFINITION_RATES]
+        assert np.array_equal(fit, M)
+    has = topo.n_paths > 0
+    assert np.array_equal(counts[:, :n_cls], (has[None, :, :, None] & ~fit).sum(axis=(1, 2)))
+    assert (counts[3, :n_cls] == 0).all() and (counts[4, :n_cls] == has.sum()).all()  # the empty network and the full one
+    assert (0 < counts[:3, :n_cls].sum(axis=1)).all() and (counts[:3, n_cls:].sum(axis=1) > 0).all()
+
+
+# ---- the shapes of tests/capacity_cases.py: plans pinned, and the oracle's conditions ------------------------------------------------
+@pytest.fixture(scope="module")
+def topo_dir(tmp_path_factory):
+    return tmp_path_factory.mktemp("capacity_topologies")
+
+
+def window_of(shape, topo):
+    """The per-env LDS window of derive_sizes (csrc/orl_api.hip) from the shape's sizes; where the persistent kernel serves the
+    configuration, checked against the sizes the library derives itself (window_from_the_library)"""
+    _, W, N, E, K, C, S, _ = cc.plan_sizes(shape, topo)
+    obs_dim = 1 + 2 * N + (2 * shape.kw["j"] + 3) * K if shape.fam == "DeepRMSA" else 0
+    return max(r16(((C * E * W + 1) // 2 * 2 + 5 * E + obs_dim) * 8 + r16(4 * C) * 4), 624 * 4)
+
+
+def window_from_the_library(shape, topo_path):
+    """The same window from the sizes the library derives itself, without a device: the flags of the configuration's specialisation,
+    None where the persistent kernel does not serve it (k > 8, a 64-slot service).  Asked at 100 Erlang at the most: the window does not
+    depend on the load, the event capacity, which the persistent kernel serves up to 2 048, does."""
+    from optical_rl_gym_amd import envs
+
+    kw = dict(shape.kw, load=min(shape.kw["load"], 100)) if "load" in shape.kw else shape.kw
+    flags = envs.ENV_CLASSES[shape.fam].spec_flags(batch=shape.envs, topology=topo_path, **kw)
+    return None if flags is None else cc.window_bytes(flags)
+
+
+@needs_hipcc
+@pytest.mark.parametrize("name", list(cc.PLANS))
+def test_plan_of_every_envelope_shape(name, topo_dir):
+    """orl_debug_capacity_plan of every shape the GPU test runs == expected_plan == the literal of tests/capacity_cases.py, and in
+    numbers what the shape is there for"""
+    lib = _lib.lib()
+    shape = cc.SHAPE_BY_NAME[name]
+    topo_path = envelope.topology_npz(shape.topo, shape.k, topo_dir)
+    topo = envelope.topology_of(topo_path)
+    env, W, N, E, K, C, S, n_br = cc.plan_sizes(shape, topo)
+    got = {}
+    for layout in (0, 1, 2):
+        for B in (1, 2, 3, shape.envs, 65536):
+            p = plan(lib, env, W, B, N, E, K, C, S, 6, n_br, layout)
+            assert p == expected_plan(env, W, B, N, E, K, C, n_br, layout), (name, layout, B)
+            assert (p["ok"], p["staged"], p["waves"], p["lds_bytes"]) == cc.PLANS[name][layout], (name, layout, B)
+            assert p["lds_bytes"] <= 64 * 1024 and (not p["ok"] or (p["grid"] - 1) * p["waves"] < B <= p["grid"] * p["waves"])
+        got[layout] = p
+    window = window_of(shape, topo)
+    from_lib = window_from_the_library(shape, topo_path)
+    assert window <= 64 * 1024 and from_lib in (None, window) and (from_lib is not None or K > 8 or name == "s512_w64_rmsa"), (name, window, from_lib)
+    maps = got[0]["wave_bytes"]
+    k8 = {2: 8, 5: 8, 8: 8, 9: 16, 16: 16, 64: 64}[K]
+    if got[1]["ok"] and got[1]["staged"]:
+        assert got[1]["wave_bytes"] - maps == r16(N * N * k8), name
+    if name.startswith("ring10c8") or name.startswith("k6full"):
+        assert (K, k8 // 8) in ((8, 1), (9, 2), (16, 2), (64, 8)) and N * N * k8 == {(10, 8): 800, (10, 16): 1600, (6, 64): 2304}[N, k8]
+    if name in ("star65_rmsa", "star66_rmsa"):  # the COUNTS row is what takes the wavefront above the default 48 KiB
+        pairs = {65: 4225, 66: 4356}[N]
+        assert r16(8 * pairs) == {65: 33808, 66: 34848}[N] and got[2]["pitch"] == {65: 4304, 66: 4432}[N] == (76 + pairs + 3) // 4 * 4
+        assert got[1]["lds_bytes"] == r16(8 * pairs) + maps <= 48 * 1024 < got[2]["lds_bytes"] == got[1]["lds_bytes"] + 4 * got[2]["pitch"]
+        assert got[1]["waves"] == got[2]["waves"] == 1 and 4 * got[2]["pitch"] > maps == {65: 512, 66: 528}[N]
+    if name == "star129_rmsa":
+        assert got[0]["ok"] == 1 and got[0]["rows"] == 83205 and got[0]["dim"] == 166410
+        assert got[1]["ok"] == got[2]["ok"] == 0 and r16(129 * 129 * 8) == 133136 > 64 * 1024 and got[1]["dim"] == 16641 * 76
+    if name == "ring31_rmsa":
+        assert topo.max_hops == 30 and got[2]["waves"] == 2
+    if name.startswith("s512_w6"):
+        assert W == 8 and n_br == 2 and got[2]["width"] == 2 + 196
+    if name == "one_rate_rmsa":
+        assert n_br == 1 and got[1]["width"] == 1
+    if name.startswith("nsf_s64_r"):
+        assert n_br == int(name[9:]) in (63, 64, 65) and got[2]["width"] == n_br + 196 and got[1]["dim"] == 196 * n_br
+    if name == "rmcsa_c31_s512":
+        assert window == 53136 and all(got[lay]["staged"] == 1 and got[lay]["waves"] == 1 and got[lay]["lds_bytes"] > 48 * 1024 for lay in (0, 1, 2))
+        assert maps == 31 * 26 * 9 * 8
+    if name == cc.UNSTAGED:  # germany50, 10 cores of 512 slots: accepted, and the maps do not fit beside the longest runs
+        assert (W, N, E, C) == (8, 50, 88, 10) and window == 60032 == from_lib and 10 * 88 * 8 == 7040
+        assert (got[0]["staged"], got[0]["waves"], got[0]["lds_bytes"]) == (1, 1, 63360) and 63360 == 10 * 88 * 9 * 8
+        assert (got[1]["staged"], got[1]["waves"], got[1]["wave_bytes"], got[1]["lds_bytes"]) == (0, 2, 20000, 40000)
+        assert (got[2]["staged"], got[2]["waves"], got[2]["wave_bytes"], got[2]["lds_bytes"]) == (0, 1, 30304, 30304)
+        assert [plan(lib, env, W, B, N, E, K, C, S, 6, n_br, 1)["grid"] for B in (1, 2, 3)] == [1, 1, 2]  # 3 envs: a half-empty workgroup
+
+
+@needs_hipcc
+def test_both_values_of_staged_occur_among_accepted_configurations(topo_dir):
+    """test_plan_and_shape sees staged == 0 only in germany50 at 31 cores of 512 slots, which batch_create_impl refuses (a per-env
+    window of 178 624 B); over the shapes of tests/capacity_cases.py, all of them accepted, both values occur"""
+    lib = _lib.lib()
+    seen = set()
+    for shape in cc.SHAPES:
+        topo_path = envelope.topology_npz(shape.topo, shape.k, topo_dir)
+        topo = envelope.topology_of(topo_path)
+        window, from_lib = window_of(shape, topo), window_from_the_library(shape, topo_path)
+        assert window <= 64 * 1024 and from_lib in (None, window), shape.name
+        env, W, N, E, K, C, S, n_br = cc.plan_sizes(shape, topo)
+        for layout in (0, 1, 2):
+            p = plan(lib, env, W, shape.envs, N, E, K, C, S, 6, n_br, layout)
+            if p["ok"]:
+                seen.add(p["staged"])
+    assert seen == {0, 1}
+    refused = cc.SHAPE_BY_NAME[cc.UNSTAGED]
+    refused = refused._replace(kw=dict(refused.kw, num_spatial_resources=31))
+    assert window_of(refused, envelope.topology_of("germany50")) == 178624 > 64 * 1024
+    assert window_from_the_library(refused, "germany50") == 178624
+
+
+@pytest.mark.parametrize("name", list(cc.SHAPE_BY_NAME))
+def test_conditions_of_the_envelope_shapes_hold_on_the_oracle(name, topo_dir):
+    """After the shape's warm-up on the oracle (the seeds, envs, heuristic and steps of the GPU test) some env has a blocked cell of a
+    pair with paths and every env a serviceable one — the range of tests/capacity_cases.py — and at k > 8 some pair is serviceable
+    only through a path of index >= 8: a cell the need table's and the longest runs' second 8-byte word decides."""
+    shape = cc.SHAPE_BY_NAME[name]
+    topo_path = envelope.topology_npz(shape.topo, shape.k, topo_dir)
+    need, _ = cc.need_of(shape, topo_path)
+    ora = OracleBackend(shape.fam, topo_path, cc.seeds_of(shape), **envelope.oracle_kwargs(shape))
+    ora.run(shape.policy, shape.warm)
+    topo, n_cls = ora.topology, need.shape[3]
+    paths, svc, counts = cc.restate_each(hm.avail_of(ora, cc.cores_of(shape), cc.spectrum_of(shape)), topo, need)
+    blocked, served = cc.blocked_of(counts, n_cls), counts[:, n_cls:].sum(axis=1)
+    print(name, "blocked", blocked.min(), blocked.max(), "served at least", served.min(), "of", int((topo.n_paths > 0).sum()) * n_cls)
+    assert (blocked > 0).any() and (served > 0).all()
+    assert (int(blocked.min()), int(blocked.max())) == shape.blocked
+    assert (shape.k > 8) == (name in cc.K_ABOVE_8) == (shape.second_word is not None)
+    if shape.k > 8:
+        second = cc.only_through_second_word(paths, need, topo, shape.envs)
+        print(name, "cells only a path >= 8 serves:", int(second.sum()), "in", int(second.any(axis=(1, 2, 3)).sum()), "envs")
+        assert int(second.any(axis=(1, 2, 3)).sum()) == shape.second_word > 0

@@ -2,7 +2,9 @@
 the numpy restatement (tests/capacity_restate.py, pinned to the oracle in tests/test_network_capacity.py): all three layouts on every env
 with ==, from slots_packed() of that moment — at construction, after a warm-up under the family's heuristic and after slot_agent's
 boundary-seeking agent steps, over the row widths, core counts and topologies at which the kernel can go wrong; against the existing
-views on the same state; after every way of stepping; under graph capture; over two shards; the facades; and the refusals."""
+views on the same state; after every way of stepping; under graph capture; over two shards; the facades; and the refusals.  The shapes of
+tests/capacity_cases.py add k = 8 / 9 / 16 / 64, the stars (N > 64, n_paths < k), 30 hops, 1 / 2 / 63 / 64 / 65 classes, the slot maps left
+in global memory (germany50 RMCSA, 10 cores of 512 slots) and the refusal of the per-path array on a real batch (star129)."""
 import functools
 import os
 
@@ -10,7 +12,9 @@ import numpy as np
 import pytest
 
 from tests import assign_cases as ac
+from tests import capacity_cases as cc
 from tests import capacity_restate as cap
+from tests import envelope
 from tests import horizon_model as hm
 from tests import slot_agent
 
@@ -23,6 +27,10 @@ SHAPES = {"rmsa_nsf_s64": (24, 150, None), "rmsa_nsf_s65": (24, 150, None), "rms
           "rmsa_nsf_s512": (24, 500, 600), "rwa_nsf_s129": (24, 1100, 1500), "rwa_nsf_s512": (24, 1500, 1500), "rmsa_ger_s128": (4, 600, 500),
           "rmcsa_c7_s64": (24, 200, None), "rmcsa_c2_s129": (20, 900, 1200), "rmcsa_c31_s64": (24, 300, None), "tiny5_k3": (24, 200, None)}
 AGENT_STEPS = 6
+# the shapes at the edges of the accepted range and the unstaged one: name -> tests/capacity_cases.py's (family, topology, k, keywords,
+# envs, heuristic, warm-up steps, what it is there for, the blocked cells the oracle showed)
+ENVELOPE_SHAPES = cc.SHAPE_BY_NAME
+LAYOUTS = ("paths", "serviceable", "counts")
 
 
 def config(name):
@@ -68,11 +76,29 @@ def shape_of(env, fam, C, need):
     return {"paths": (N * N * K * cores, 2), "serviceable": (N * N, n_cls), "counts": (1, n_cls + N * N)}
 
 
-def compare(env, fam, C, S, need, what, state_untouched=False):
+_ONE_ENV = {}  # restatements of single envs by their packed maps (germany50 at 10 cores of 512 slots: most of a second each)
+
+
+def restate_each(env, C, S, need):
+    """cap.restate one env at a time, each distinct slot map once"""
+    packed, avail = env.slots_packed(), hm.avail_of(env, C, S)
+    parts = []
+    for e in range(env.num_envs):
+        key = (id(need), packed[e].tobytes())
+        if key not in _ONE_ENV:
+            _ONE_ENV[key] = cap.restate(avail[e:e + 1], env.topology, need)
+        parts.append(_ONE_ENV[key])
+    return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
+
+
+def compare(env, fam, C, S, need, what, state_untouched=False, layouts=LAYOUTS, each=False):
     """All three layouts of the present state against the restatement from slots_packed(), on every env, with ==; the shapes as defined"""
-    want = dict(zip(("paths", "serviceable", "counts"), cap.restate(hm.avail_of(env, C if fam == "RMCSA" else 1, S), env.topology, need)))
+    cores = C if fam == "RMCSA" else 1
+    want = dict(zip(LAYOUTS, restate_each(env, cores, S, need) if each else cap.restate(hm.avail_of(env, cores, S), env.topology, need)))
     before = (env.get_state(), env.flags().copy()) if state_untouched else None
     for layout, (rows, width) in shape_of(env, fam, C, need).items():
+        if layout not in layouts:
+            continue
         dim = rows * width
         pitch = (dim + 15) // 16 * 16 if layout == "serviceable" else (dim + 3) // 4 * 4
         assert env.network_capacity_shape(layout) == (rows, width, dim, pitch), (what, layout)
@@ -155,6 +181,97 @@ def test_one_wavefront_with_more_than_the_default_lds():
     env.close()
 
 
+def make_envelope(shape, tmp_path, n=None):
+    """A batch of a shape of tests/capacity_cases.py -> (env, need, C, S)"""
+    import optical_rl_gym_amd as orl
+
+    topo = envelope.topology_npz(shape.topo, shape.k, tmp_path)
+    env = orl.make(shape.fam, topology=topo, num_envs=shape.envs if n is None else n, seeds=cc.seeds_of(shape, n), **shape.kw)
+    return env, cc.need_of(shape, topo)[0], cc.cores_of(shape), cc.spectrum_of(shape)
+
+
+def assert_a_path_of_index_8_or_more_decides(shape, env, need, want):
+    """k > 8: some pair's "serviceable" row has a 1 that only a path of index >= 8 explains — every row of paths 0 .. 7 of the pair has
+    L < need (want: what compare() found the device's rows equal to)"""
+    second = cc.only_through_second_word(want["paths"], need, env.topology, env.num_envs)
+    M = want["serviceable"].reshape(second.shape)
+    assert second.any() and M[second].all(), shape.name
+    print(shape.name, "cells only a path >= 8 serves:", int(second.sum()), "in", int(second.any(axis=(1, 2, 3)).sum()), "envs")
+    assert int(second.any(axis=(1, 2, 3)).sum()) == shape.second_word  # (what the oracle showed)
+
+
+@pytest.mark.parametrize("name", list(ENVELOPE_SHAPES))
+def test_envelope_shapes_equal_the_restatement_at_three_moments(name, tmp_path):
+    """Every shape of tests/capacity_cases.py at construction, after its warm-up under its heuristic and after a few policy_steps; the
+    blocked cells after the warm-up are the oracle's (tests/test_network_capacity.py); star129 in "paths" alone, the other two layouts
+    being refused for it (test_the_per_path_array_is_refused_on_a_real_batch)."""
+    shape = ENVELOPE_SHAPES[name]
+    env, need, C, S = make_envelope(shape, tmp_path)
+    fam, n_cls = cc.need_family(shape), need.shape[3]
+    kw = dict(layouts=("paths",) if name == "star129_rmsa" else LAYOUTS, each=name == cc.UNSTAGED)
+    want = compare(env, fam, C, S, need, name + ", construction", state_untouched=True, **kw)
+    got = want["paths"].reshape(env.num_envs, -1, 2)
+    assert ((got == S) | (got == -1)).all() and (got == S).any()
+    env.run(shape.policy, shape.warm)
+    want = compare(env, fam, C, S, need, name + ", warm-up", state_untouched=True, **kw)
+    blocked, served = cc.blocked_of(want["counts"], n_cls), want["counts"][:, n_cls:].sum(axis=1)
+    assert (int(blocked.min()), int(blocked.max())) == shape.blocked and (blocked > 0).any() and (served > 0).all(), (name, blocked)
+    if shape.k > 8:
+        assert_a_path_of_index_8_or_more_decides(shape, env, need, want)
+    if name == "ring31_rmsa":  # rows of 30-hop paths that the warm-up has changed
+        assert (want["paths"].reshape(env.num_envs, -1, 2)[:, env.topology.path_hops.reshape(-1) == 30, 1] < S).any()
+    for _ in range(cc.AFTER_STEPS):
+        env.policy_step(shape.policy, auto_reset=True, fetch=False)
+    later = compare(env, fam, C, S, need, name + ", policy_steps", **kw)
+    assert not np.array_equal(later["paths"], want["paths"])
+    assert not (env.flags() & 2).any()
+    env.check()
+    env.close()
+
+
+@pytest.mark.parametrize("n", [1, 3])
+def test_slot_maps_left_in_global_memory_at_batch_sizes_with_a_partly_empty_workgroup(n, tmp_path):
+    """germany50 RMCSA at 10 cores of 512 slots: "serviceable" runs two wavefronts per workgroup on the maps in global memory — one env
+    is half a workgroup, three are one and a half — and "counts" one; "paths" stages them.  Then the layouts in alternation on
+    junk-filled buffers: each keeps its own rows and zero pad columns."""
+    shape = ENVELOPE_SHAPES[cc.UNSTAGED]
+    env, need, C, S = make_envelope(shape, tmp_path, n=n)
+    env.run(shape.policy, shape.warm)
+    want = compare(env, "RMCSA", C, S, need, "%s, %d envs" % (shape.name, n), state_untouched=True, each=True)
+    views = {lay: env.device_tensor(dev) for lay, dev in (("paths", "path_capacity"), ("serviceable", "serviceable"), ("counts", "capacity_counts"))}
+    junk_then_alternate(env, views, want, order=("counts", "serviceable", "paths", "serviceable", "counts"))
+    assert (want["paths"].reshape(n, -1, 2)[:, :, 1] < S)[want["paths"].reshape(n, -1, 2)[:, :, 0] >= 0].any()
+    env.check()
+    env.close()
+
+
+def test_the_per_path_array_is_refused_on_a_real_batch(tmp_path):
+    """star129: 129 x 129 pairs x 8 bytes of longest runs exceed a workgroup's LDS, so "serviceable" and "counts" are refused — the
+    call, the queued call and the shape — with the batch left as it was, no buffer made, and "paths" still served"""
+    from optical_rl_gym_amd._lib import OrlError
+
+    shape = ENVELOPE_SHAPES["star129_rmsa"]
+    env, need, C, S = make_envelope(shape, tmp_path, n=4)
+    env.run(shape.policy, 200)
+    snap, flags = env.get_state(), env.flags().copy()
+    for call in (lambda: env.network_capacity("serviceable"), lambda: env.network_capacity("counts", fetch=False), lambda: env.network_capacity_shape("counts"),
+                 lambda: env.network_capacity("counts"), lambda: env.network_capacity_shape("serviceable")):
+        with pytest.raises(OrlError, match="per-path array of 129 x 129 pairs x 5 paths"):
+            call()
+    for dev in ("serviceable", "capacity_counts"):
+        with pytest.raises(OrlError, match=r"call network_capacity\("):
+            env.device_tensor(dev)
+    assert np.array_equal(env.get_state(), snap) and np.array_equal(env.flags(), flags)
+    assert env.network_capacity_shape("paths") == (83205, 2, 166410, 166412)
+    want = compare(env, "RMSA", C, S, need, "star129 after the refusals", state_untouched=True, layouts=("paths",))
+    assert (want["paths"].reshape(4, -1, 2)[:, :, 1] < S)[want["paths"].reshape(4, -1, 2)[:, :, 0] >= 0].any()
+    for dev in ("serviceable", "capacity_counts"):  # (still none)
+        with pytest.raises(OrlError, match=r"call network_capacity\("):
+            env.device_tensor(dev)
+    env.check()
+    env.close()
+
+
 def pending_rows(env, fam, C, need, paths, rates):
     """(L, F) of the pending pair's rows [n, K C', 2], the need of the pending class on them [n, K C'], and the pending (src, dst, class)"""
     sv = env.services()
@@ -167,8 +284,8 @@ def pending_rows(env, fam, C, need, paths, rates):
     return rows, nd, src, dst, r
 
 
-@pytest.mark.parametrize("name", ["rmsa_nsf_s129", "rmsa_nsf_s512", "rwa_nsf_s129", "rmcsa_c7_s64", "deep_s129_j4"])
-def test_consistent_with_the_existing_views_of_the_pending_service(name):
+@pytest.mark.parametrize("name", ["rmsa_nsf_s129", "rmsa_nsf_s512", "rwa_nsf_s129", "rmcsa_c7_s64", "deep_s129_j4", "ring10c8_k9_rmsa", "k6full_k64_rwa"])
+def test_consistent_with_the_existing_views_of_the_pending_service(name, tmp_path):
     """On one device state, for the pending pair and class: F of the pair's rows is column 1 of block_table(1) and L >= need exactly where
     that table lists a block (rows the service can use); the pair's "serviceable" cell is the path-level action mask's any()."""
     import optical_rl_gym_amd as orl
@@ -179,6 +296,10 @@ def test_consistent_with_the_existing_views_of_the_pending_service(name):
         fam, C, S, pol, steps = "DeepRMSA", 1, 129, "SAP", 700
         rates = cap.class_rates("RMSA", {})
         need = cap.need_table("RMSA", env.topology, rates)
+    elif name in ENVELOPE_SHAPES:  # k = 9 and k = 64: the pending pair's rows past the first eight
+        shape = ENVELOPE_SHAPES[name]
+        env, need, C, S = make_envelope(shape, tmp_path)
+        fam, pol, steps, rates = shape.fam, shape.policy, shape.warm, cap.class_rates(shape.fam, shape.kw)
     else:
         env, fam, tab, C, S = make(name)
         need, pol, steps, rates = need_of(name), hm.HEURISTIC[fam], SHAPES[name][1], cap.class_rates(fam, config(name)[2])
@@ -237,13 +358,38 @@ def test_the_view_follows_every_way_of_stepping(name):
     env.close()
 
 
+def junk_then_alternate(env, views, want, order=("counts", "paths", "serviceable", "paths", "counts")):
+    """The layouts' buffers (views: layout -> device_tensor) filled with junk to their last pad column, then one call of each layout in
+    alternation: every buffer holds its own rows of `want`, pad columns are 0"""
+    import torch
+
+    from optical_rl_gym_amd.envs import _RawDeviceArray
+
+    n, flats = env.num_envs, {}
+    for lay, v in views.items():
+        typestr = "|u1" if lay == "serviceable" else "<i4"
+        cap_items = n * env.network_capacity_shape(lay)[3]
+        flats[lay] = torch.as_tensor(_RawDeviceArray({"shape": (cap_items,), "typestr": typestr, "data": (v.data_ptr(), False), "version": 2, "strides": None}),
+                                     device=v.device)
+    with torch.cuda.stream(env.torch_stream()):
+        for f in flats.values():
+            f.fill_(77)
+        for lay in order:
+            assert env.network_capacity(lay, fetch=False) is None
+    env.sync()
+    for lay, f in flats.items():
+        _, _, dim, pitch = env.network_capacity_shape(lay)
+        body = f.cpu().numpy().reshape(n, pitch)
+        assert np.array_equal(body[:, :dim], want[lay].astype(body.dtype)), lay
+        assert (body[:, dim:] == 0).all(), lay
+
+
 def test_layouts_in_alternation_keep_their_own_buffers_and_pad_columns():
     """Each layout's device_array shows its own rows whatever was called since; pad columns are 0 and nothing is written past B * pitch:
     the buffers are filled with junk first."""
     import torch
 
     from optical_rl_gym_amd._lib import OrlError
-    from optical_rl_gym_amd.envs import _RawDeviceArray
 
     name = "rmsa_nsf_s512"  # three classes: 588 byte columns at a pitch of 592, 199 int32 columns at a pitch of 200
     env, fam, tab, C, S = make(name, n=9)
@@ -261,23 +407,7 @@ def test_layouts_in_alternation_keep_their_own_buffers_and_pad_columns():
         assert v.shape == (9, dim) and v.stride() == (pitch, 1) and (dim, pitch) != (0, 0), lay
         assert v.dtype == (torch.bool if lay == "serviceable" else torch.int32)
     assert env.network_capacity_shape("serviceable")[2:] == (588, 592) and env.network_capacity_shape("counts")[2:] == (199, 200)
-    flats = {}
-    for lay, v in views.items():
-        item, typestr = (1, "|u1") if lay == "serviceable" else (4, "<i4")
-        cap_items = 9 * env.network_capacity_shape(lay)[3]
-        flats[lay] = torch.as_tensor(_RawDeviceArray({"shape": (cap_items,), "typestr": typestr, "data": (v.data_ptr(), False), "version": 2, "strides": None}),
-                                     device=v.device)
-    with torch.cuda.stream(env.torch_stream()):
-        for f in flats.values():
-            f.fill_(77)
-        for lay in ("counts", "paths", "serviceable", "paths", "counts"):
-            assert env.network_capacity(lay, fetch=False) is None
-    env.sync()
-    for lay, f in flats.items():
-        _, _, dim, pitch = env.network_capacity_shape(lay)
-        body = f.cpu().numpy().reshape(9, pitch)
-        assert np.array_equal(body[:, :dim], want[lay].astype(body.dtype)), lay
-        assert (body[:, dim:] == 0).all(), lay
+    junk_then_alternate(env, views, want)
     # a step, then one layout alone: the other two still show the rows of the state before
     env.policy_step("SAP_FF", auto_reset=True, fetch=False)
     env.run("SAP_FF", 40)

@@ -333,6 +333,12 @@ int orl_host_free(void* p);
 #define ORL_BUF_CAPACITY_COUNTS 18 /* i32 [n_envs][pitch]: rows of the last orl_batch_network_capacity(ORL_CAPACITY_COUNTS); each of
                                     * the three is a buffer of its own at its layout's pitch (orl_batch_network_capacity_shape),
                                     * allocated by that layout's first call; n_elements = 0 before it */
+#define ORL_BUF_CAPACITY_AFTER_CLASSES 19 /* i32 [n_envs][pitch]: rows of the last orl_batch_capacity_after(ORL_AFTER_CLASSES) */
+#define ORL_BUF_CAPACITY_AFTER_TOTAL 20   /* i32 [n_envs][pitch]: rows of the last orl_batch_capacity_after(ORL_AFTER_TOTAL); each of the two
+                                           * is a buffer of its own at the last call's pitch (orl_batch_capacity_after_shape), allocated
+                                           * by that layout's first call and replaced by a larger one — of at least twice the size, at
+                                           * most what ORL_AFTER_MAX_Q candidates need — when a later call has more candidates; the
+                                           * one replaced lives on with the batch; n_elements = 0 before any call */
 int orl_batch_device_buffer(orl_batch* b, int which, void** device_ptr, int64_t* n_elements);
 /* The HIP stream (hipStream_t) the batch queues its launches on.  An agent on the same GPU that queues ITS kernels on this
  * stream too (torch: `torch.cuda.ExternalStream(ptr)`) needs no synchronisation between its network and orl_batch_step: the
@@ -750,6 +756,49 @@ int orl_batch_release_horizons(orl_batch* b, int layout, int j, int modulation, 
 int orl_batch_network_capacity_shape(const orl_batch* b, int layout, int32_t* rows, int32_t* width, int64_t* dim, int64_t* pitch);
 int orl_batch_network_capacity(orl_batch* b, int layout, void* out /* host [n_envs][dim] of the layout's type, or NULL */);
 
+/* capacity_after: what each candidate placement of the PENDING service would leave the network — the class counts of
+ * ORL_CAPACITY_COUNTS after the placement, for Q candidates per env in one launch, without a fork, a step or a second batch.  RMSA,
+ * DeepRMSA, RWA and RMCSA; pidx, C', n_cls, need and serviceable are those of the network capacity above.  For env e with slot maps A:
+ *   candidate  (row, s, n): row = p C' + c in the row order of orl_batch_path_features — path p of the pending service's pair, core c —
+ *              and the window of slots [s, s + n).  PRESENT iff 0 <= row < k C', p < n_paths[pair], n >= 1, 0 <= s and s + n <= S
+ *   A - cand   A with the slots s .. s + n - 1 taken on every link of path p in core c, whether they were free or not
+ *   after(q)[r] = the ordered pairs with paths for which class r is NOT serviceable on A - cand_q
+ *               = the first n_cls columns of ORL_CAPACITY_COUNTS evaluated on A - cand_q; -1 throughout for an absent candidate
+ * Row Q, one past the last candidate, is the baseline on A itself: the first n_cls columns of ORL_CAPACITY_COUNTS of the same moment.
+ * This is NOT "the counts of a forked env after its step": a step also runs the releases that fall due before the next arrival. */
+#define ORL_AFTER_CLASSES 0 /* int32 [n_envs][(Q + 1) n_cls]: row q = after(q), row Q the baseline */
+#define ORL_AFTER_TOTAL 1   /* int32 [n_envs][Q + 1]: the sum of row q over the classes; -1 for an absent candidate */
+/* Candidate sources; whatever a table holds (a stale one is the caller's business) is validated on the device by the presence rule: */
+#define ORL_AFTER_ROUTE 0   /* the table last written by orl_batch_route_spectrum (RMSA, RWA: ORL_BUF_ASSIGN_TABLE) or
+                             * orl_batch_route_cores (RMCSA: ORL_BUF_CORE_TABLE): Q = k C', candidate q = (q, column 0, column 2) of
+                             * row q; a row with column 0 >= S has no fit and is absent.  DeepRMSA has no such table: refused */
+#define ORL_AFTER_BLOCKS 1  /* the table last written by orl_batch_block_table for this j (every family): Q = R j, candidate q = r j + b
+                             * — the column order of the block mask, the index orl_batch_select_blocks decodes — with n = column 0
+                             * of row r and s = start_b (placement ORL_BLOCK_FIRST) or start_b + L_b - n (ORL_BLOCK_LAST); a block
+                             * with start_b >= S is absent */
+#define ORL_AFTER_GIVEN 2   /* host candidates int32 [n_envs][Q][3] = (row, s, n), staged through a page-locked buffer of the batch
+                             * like every other `given` (not graph-capturable) */
+#define ORL_AFTER_MAX_Q 1024 /* the most candidates per env of one call; more (RMCSA with many cores and blocks) is refused */
+/* The device pitch is round_up(dim, 4) int32, the pad columns 0.  Each layout has a device buffer of its own
+ * (ORL_BUF_CAPACITY_AFTER_CLASSES, ORL_BUF_CAPACITY_AFTER_TOTAL).  One launch on the batch's stream (the first call also builds the
+ * batch's static need table, if orl_batch_network_capacity has not), one wavefront per env, no global atomics, deterministic: with
+ * out == NULL, after a first call of that (source, layout), the call neither allocates nor synchronises — graph-capturable for
+ * ORL_AFTER_ROUTE and ORL_AFTER_BLOCKS; with `out` ([n_envs][dim] int32) the rows are copied out densely and the call synchronises.
+ * Env state, flags, snapshot bytes and the tables read do not change.  j and placement are read for ORL_AFTER_BLOCKS only,
+ * given / n_given_candidates for ORL_AFTER_GIVEN only (else NULL).  ORL_E_INVALID, before anything is queued or allocated:
+ * QoSConstrainedRA, an unknown source, layout or placement, ORL_AFTER_ROUTE on DeepRMSA, a table that has never been written (the
+ * message names the call to make first), j outside 1 .. 8, Q outside 1 .. ORL_AFTER_MAX_Q, a topology whose N N k per-path
+ * array exceeds the kernel's LDS.
+ * orl_batch_capacity_after_shape: *candidates = Q, *width = n_cls (ORL_AFTER_CLASSES) or 1; *dim = (Q + 1) x width; the device pitch
+ * in int32. */
+int orl_batch_capacity_after_shape(const orl_batch* b, int source, int j, int layout, int n_given_candidates, int32_t* candidates, int32_t* width,
+                                   int64_t* dim, int64_t* pitch);
+/* (*dim, *pitch) of the rows the last orl_batch_capacity_after of `layout` left in its device buffer — what ORL_BUF_CAPACITY_AFTER_*
+ * hands out; (0, 0) before any call of that layout. */
+int orl_batch_capacity_after_last(const orl_batch* b, int layout, int64_t* dim, int64_t* pitch);
+int orl_batch_capacity_after(orl_batch* b, int source, int j, int placement, int layout, const int32_t* given /* host [n_envs][Q][3], or NULL */,
+                             int n_given_candidates, int32_t* out /* host [n_envs][dim], or NULL: stays on the device, no synchronisation */);
+
 /* Snapshot / restore of the complete simulation state of the batch (slot maps, pending releases, RNG, statistics,
  * counters).  The reference has no equivalent (no checkpointing); used for long PPO runs.  The per-env
  * rates (orl_batch_set_rates) are configuration and not part of it. */
@@ -859,6 +908,9 @@ int orl_debug_horizon_plan(int env_type, int W, int64_t B, int N, int E, int K, 
  * per workgroup, grid, dynamic LDS bytes of a workgroup, slot maps staged in LDS, LDS bytes of one wavefront (= one env).  Returns
  * 11, or 0 for arguments outside every batch. */
 int orl_debug_capacity_plan(int env_type, int W, int64_t B, int N, int E, int K, int C, int S, int M, int n_br, int layout, int32_t* out);
+/* The same for capacity_after (csrc/orl_view_plan.h, capacity_after_plan; tests/test_capacity_after.py) with Q candidates: the same
+ * eleven values; out[1] = Q + 1 rows.  Returns 11, or 0 for arguments outside every batch. */
+int orl_debug_capacity_after_plan(int env_type, int W, int64_t B, int N, int E, int K, int C, int S, int M, int n_br, int layout, int Q, int32_t* out);
 /* Test aid: rows of H per round for the release horizons of this batch (0: what the plan says; more than the plan's: the plan's), so
  * that a small shape runs in several rounds. */
 int orl_debug_set_horizon_rows(orl_batch* b, int rows);

@@ -106,6 +106,11 @@ EXPORTS = {
                                                    C.POINTER(C.c_int64)]),
     "orl_batch_network_capacity": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "orl_debug_capacity_plan": (C.c_int, [C.c_int, C.c_int, C.c_int64] + [C.c_int] * 8 + [C.POINTER(C.c_int32)]),
+    "orl_batch_capacity_after_shape": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "orl_batch_capacity_after_last": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "orl_batch_capacity_after": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "orl_debug_capacity_after_plan": (C.c_int, [C.c_int, C.c_int, C.c_int64] + [C.c_int] * 9 + [C.POINTER(C.c_int32)]),
     "orl_batch_path_features_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "orl_batch_path_features": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "orl_batch_link_features_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

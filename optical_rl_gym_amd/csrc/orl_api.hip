@@ -141,6 +141,7 @@ __global__ void k_matrix_obs(DevParams P, unsigned char* out) {
 #include "orl_blocks.h"
 #include "orl_horizon.h"  // (and the decode of a release record, which orl_batch_get_pending shares with the kernel)
 #include "orl_capacity.h"
+#include "orl_capacity_after.h"
 #include "orl_link_obs.h"
 #include "orl_view_plan.h"  // view_shape, view_plan: the shape of each view's rows and the geometry of its launch
 
@@ -711,6 +712,8 @@ extern "C" void orl_batch_destroy(orl_batch* b) try {
     if (g.host) hipHostFree(g.host);
     if (g.up) hipEventDestroy(g.up);
   }
+  if (b->ca_given.host) hipHostFree(b->ca_given.host);
+  if (b->ca_given.up) hipEventDestroy(b->ca_given.up);
   if (b->ev_copy_up) hipEventDestroy(b->ev_copy_up);
   if (b->ev_copy) hipEventDestroy(b->ev_copy);
   if (b->spec_handle) dlclose(b->spec_handle);
@@ -1269,6 +1272,12 @@ extern "C" int orl_batch_device_buffer(orl_batch* b, int which, void** device_pt
       *device_ptr = b->cap_buf[layout];
       *n_elements = b->cap_buf[layout] ? B * capacity_shape(b->P, layout).pitch : 0;
     } break;
+    case ORL_BUF_CAPACITY_AFTER_CLASSES:
+    case ORL_BUF_CAPACITY_AFTER_TOTAL: {
+      const int layout = which - ORL_BUF_CAPACITY_AFTER_CLASSES;
+      *device_ptr = b->ca_pitch[layout] ? b->ca_buf[layout] : nullptr;
+      *n_elements = B * b->ca_pitch[layout];
+    } break;
     default: return fail(ORL_E_INVALID, "unknown buffer %d", which);
   }
   return ORL_OK;
@@ -1650,6 +1659,131 @@ extern "C" int orl_batch_network_capacity(orl_batch* b, int layout, void* out) t
   ORL_LAUNCH(network_capacity, b, b->cap_buf[layout], need, layout);
   HIPCHK(hipGetLastError());
   return view_rows_to_host(b, b->cap_buf[layout], sh, out);
+}
+ORL_ABI_CATCH_INT
+
+// capacity_after (orl_capacity_after.h): the capacity's class counts after each candidate placement of the pending service
+static_assert(ORL_AFTER_MAX_CANDIDATES == ORL_AFTER_MAX_Q, "the kernel header's cap and the public one");
+// the candidates per env of a source into *Q; with_table: the table must have been written (a call, not a shape query)
+static int capacity_after_check(const orl_batch* b, int source, int j, int placement, int layout, int n_given, bool with_table, int* Q) {
+  const DevParams& P = b->P;
+  if (P.env_type == ENV_QOS) return fail(ORL_E_INVALID, "capacity_after is not available for QoSConstrainedRA, which has no slot maps (RMSA, DeepRMSA, RWA and RMCSA only)");
+  if (layout != ORL_AFTER_CLASSES && layout != ORL_AFTER_TOTAL) return fail(ORL_E_INVALID, "unknown capacity_after layout %d (ORL_AFTER_CLASSES = 0, ORL_AFTER_TOTAL = 1)", layout);
+  const int R = (P.env_type == ENV_RMCSA ? P.C : 1) * P.K;
+  int64_t q = 0;
+  switch (source) {
+    case ORL_AFTER_ROUTE:
+      if (P.env_type == ENV_DEEPRMSA) return fail(ORL_E_INVALID, "capacity_after from a route table is for RMSA, RWA (orl_batch_route_spectrum) and RMCSA (orl_batch_route_cores); DeepRMSA has no such table: use ORL_AFTER_BLOCKS or ORL_AFTER_GIVEN");
+      if (with_table && !(P.env_type == ENV_RMCSA ? b->core_table : b->route_table))
+        return fail(ORL_E_INVALID, "capacity_after from the route table: no table yet, call %s first", P.env_type == ENV_RMCSA ? "orl_batch_route_cores (route_cores)" : "orl_batch_route_spectrum (route_spectrum)");
+      q = R;
+      break;
+    case ORL_AFTER_BLOCKS:
+      if (j < 1 || j > 8) return fail(ORL_E_INVALID, "capacity_after from a block table takes j = 1 .. 8 blocks per row, got j = %d", j);
+      if (placement != ORL_BLOCK_FIRST && placement != ORL_BLOCK_LAST) return fail(ORL_E_INVALID, "unknown block placement %d (ORL_BLOCK_FIRST = 0, ORL_BLOCK_LAST = 1)", placement);
+      if (with_table && !b->bt_buf[j]) return fail(ORL_E_INVALID, "capacity_after from the block table of j = %d: no such table yet, call orl_batch_block_table (block_table) with j = %d first", j, j);
+      q = (int64_t)R * j;
+      break;
+    case ORL_AFTER_GIVEN: q = n_given; break;
+    default: return fail(ORL_E_INVALID, "unknown capacity_after source %d (ORL_AFTER_ROUTE = 0, ORL_AFTER_BLOCKS = 1, ORL_AFTER_GIVEN = 2)", source);
+  }
+  if (q < 1 || q > ORL_AFTER_MAX_Q) return fail(ORL_E_INVALID, "capacity_after takes 1 .. %d candidates per env, got %lld", ORL_AFTER_MAX_Q, (long long)q);
+  if (!capacity_after_plan(P, b->wt, layout, (int)q).ok)
+    return fail(ORL_E_INVALID, "capacity_after's per-path array of %d x %d pairs x %d paths (8 bytes per pair and 8 paths) exceeds the kernel's LDS limit of %zu bytes",
+                P.N, P.N, P.K, kViewLdsMax);
+  *Q = (int)q;
+  return ORL_OK;
+}
+
+extern "C" int orl_batch_capacity_after_shape(const orl_batch* b, int source, int j, int layout, int n_given_candidates, int32_t* candidates, int32_t* width,
+                                              int64_t* dim, int64_t* pitch) try {
+  if (!b || !candidates || !width || !dim || !pitch) return fail(ORL_E_INVALID, "null argument");
+  int Q = 0;
+  if (int rc = capacity_after_check(b, source, j, ORL_BLOCK_FIRST, layout, n_given_candidates, false, &Q)) return rc;
+  const ViewShape sh = capacity_after_shape(b->P, layout, Q);
+  *candidates = Q;
+  *width = sh.width;
+  *dim = sh.dim;
+  *pitch = sh.pitch;
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+extern "C" int orl_batch_capacity_after_last(const orl_batch* b, int layout, int64_t* dim, int64_t* pitch) try {
+  if (!b || !dim || !pitch) return fail(ORL_E_INVALID, "null argument");
+  if (layout != ORL_AFTER_CLASSES && layout != ORL_AFTER_TOTAL) return fail(ORL_E_INVALID, "unknown capacity_after layout %d (ORL_AFTER_CLASSES = 0, ORL_AFTER_TOTAL = 1)", layout);
+  *dim = b->ca_dim[layout];
+  *pitch = b->ca_pitch[layout];
+  return ORL_OK;
+}
+ORL_ABI_CATCH_INT
+
+extern "C" int orl_batch_capacity_after(orl_batch* b, int source, int j, int placement, int layout, const int32_t* given, int n_given_candidates, int32_t* out) try {
+  if (!b) return fail(ORL_E_INVALID, "null argument");
+  if (source == ORL_AFTER_GIVEN && !given) return fail(ORL_E_INVALID, "ORL_AFTER_GIVEN needs the candidates (host [n_envs][n][3] int32)");
+  if (source != ORL_AFTER_GIVEN && given) return fail(ORL_E_INVALID, "candidates are for ORL_AFTER_GIVEN only");
+  int Q = 0;
+  if (int rc = capacity_after_check(b, source, j, placement, layout, n_given_candidates, true, &Q)) return rc;
+  HIPCHK(hipSetDevice(b->device));
+  const DevParams& P = b->P;
+  const ViewShape sh = capacity_after_shape(P, layout, Q);
+  if (!b->cap_need) {  // (shared with orl_batch_network_capacity)
+    if (int rc = view_buffer(b, b->cap_need, capacity_need_bytes(P.N, P.K, capacity_classes(P)), "network capacity (slots per pair, class and path)")) return rc;
+    ORL_LAUNCH(capacity_need, b, b->cap_need);
+    HIPCHK(hipGetLastError());
+  }
+  const size_t bytes = (size_t)(P.B * sh.pitch) * sizeof(int32_t);
+  if (bytes > b->ca_cap[layout]) {  // a larger buffer; the one it replaces lives on with the batch (a launch on it may still be queued or captured),
+    // so a buffer grows to at least twice the last one's size — never past what ORL_AFTER_MAX_Q candidates need: a caller whose Q
+    // grows call by call leaves behind less than the buffer it ends with
+    const size_t most = (size_t)(P.B * capacity_after_shape(P, layout, ORL_AFTER_MAX_Q).pitch) * sizeof(int32_t);
+    size_t want = 2 * b->ca_cap[layout] < most ? 2 * b->ca_cap[layout] : most;
+    if (want < bytes) want = bytes;
+    int32_t* grown = nullptr;
+    if (int rc = view_buffer(b, grown, want, "capacity_after")) return rc;
+    b->ca_buf[layout] = grown;
+    b->ca_cap[layout] = want;
+  }
+  const int* tab = nullptr;
+  int tstride = 0;
+  if (source == ORL_AFTER_ROUTE) {
+    const bool rmcsa = P.env_type == ENV_RMCSA;
+    tab = rmcsa ? b->core_table : b->route_table;
+    tstride = (int)view_shape(P, rmcsa ? VIEW_ROUTE_CORES : VIEW_ROUTE, 0).pitch;
+  } else if (source == ORL_AFTER_BLOCKS) {
+    tab = b->bt_buf[j];
+    tstride = (int)view_shape(P, VIEW_BLOCKS, j).pitch;
+  } else {
+    GivenStage& g = b->ca_given;
+    const size_t gbytes = (size_t)P.B * Q * 3 * sizeof(int32_t);
+    if (gbytes > b->ca_given_cap) {  // larger staging buffers: the upload out of the old ones first, then they go (the device one lives on:
+      // at least twice the last size, as above, and never past ORL_AFTER_MAX_Q candidates)
+      if (g.up) HIPCHK(hipEventSynchronize(g.up));
+      const size_t most = (size_t)P.B * ORL_AFTER_MAX_Q * 3 * sizeof(int32_t);
+      size_t want = 2 * b->ca_given_cap < most ? 2 * b->ca_given_cap : most;
+      if (want < gbytes) want = gbytes;
+      int32_t* dev = nullptr;
+      if (int rc = view_buffer(b, dev, want, "capacity_after candidates")) return rc;
+      int32_t* host = nullptr;
+      HIPCHK(hipHostMalloc((void**)&host, want, hipHostMallocPortable));
+      if (g.host) hipHostFree(g.host);
+      g.dev = dev;
+      g.host = host;
+      b->ca_given_cap = want;
+    }
+    if (!g.up) HIPCHK(hipEventCreateWithFlags(&g.up, hipEventDisableTiming));
+    else HIPCHK(hipEventSynchronize(g.up));  // (the last call's upload has left the staging buffer)
+    memcpy(g.host, given, gbytes);
+    HIPCHK(hipMemcpyAsync(g.dev, g.host, gbytes, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipEventRecord(g.up, b->stream));
+    tab = g.dev;
+    tstride = 3 * Q;
+  }
+  ORL_LAUNCH(capacity_after, b, b->ca_buf[layout], b->cap_need, tab, tstride, source, j, placement, Q, layout);
+  HIPCHK(hipGetLastError());
+  b->ca_pitch[layout] = sh.pitch;
+  b->ca_dim[layout] = sh.dim;
+  return view_rows_to_host(b, b->ca_buf[layout], sh, out);
 }
 ORL_ABI_CATCH_INT
 
@@ -2349,6 +2483,19 @@ extern "C" int orl_debug_capacity_plan(int env_type, int W, int64_t B, int N, in
   P.env_type = env_type; P.B = B; P.N = N; P.E = E; P.K = K; P.C = C; P.S = S; P.J = 1; P.M = M; P.n_br = n_br;
   const ViewShape sh = capacity_shape(P, layout);
   const CapacityPlan pl = capacity_plan(P, W, layout);
+  const int32_t v[11] = {(int32_t)sh.dim, sh.rows, sh.width, (int32_t)sh.pitch, pl.ok, pl.waves, pl.block, (int32_t)pl.grid, (int32_t)pl.lds_bytes, pl.staged, pl.wave_bytes};
+  memcpy(out, v, sizeof v);
+  return 11;
+}
+catch (...) { return 0; }
+extern "C" int orl_debug_capacity_after_plan(int env_type, int W, int64_t B, int N, int E, int K, int C, int S, int M, int n_br, int layout, int Q, int32_t* out) try {
+  if (!out || env_type < 0 || env_type > ORL_ENV_QOS || (W != 1 && W != 2 && W != 5 && W != 8) || B < 1 || N < 1 || E < 1 || K < 1 || C < 1 || S < 1 || M < 1 || n_br < 1)
+    return 0;
+  DevParams P;
+  memset(&P, 0, sizeof P);
+  P.env_type = env_type; P.B = B; P.N = N; P.E = E; P.K = K; P.C = C; P.S = S; P.J = 1; P.M = M; P.n_br = n_br;
+  const ViewShape sh = capacity_after_shape(P, layout, Q);
+  const CapacityPlan pl = capacity_after_plan(P, W, layout, Q);
   const int32_t v[11] = {(int32_t)sh.dim, sh.rows, sh.width, (int32_t)sh.pitch, pl.ok, pl.waves, pl.block, (int32_t)pl.grid, (int32_t)pl.lds_bytes, pl.staged, pl.wave_bytes};
   memcpy(out, v, sizeof v);
   return 11;

@@ -119,6 +119,12 @@ struct orl_batch {
   int rh_rows = 0;                 // orl_debug_set_horizon_rows: rows of H per round (0: the plan's)
   void* cap_buf[3] = {};           // network capacity: [B][pitch] rows per layout (ORL_CAPACITY_*), each allocated by that layout's first call
   unsigned char* cap_need = nullptr;  // need(pidx, r), static per batch: [N N][n_cls][round_up(K, 8)] bytes, built by the first call that reads it
+  int32_t* ca_buf[2] = {};         // capacity_after: [B][pitch] int32 rows per layout (ORL_AFTER_*), ca_cap bytes; allocated by the layout's first
+  size_t ca_cap[2] = {};           // call, replaced by a larger one when a call has more candidates; what ORL_BUF_CAPACITY_AFTER_* hand out,
+  int64_t ca_pitch[2] = {};        // at the last call's pitch (0: none yet); ca_dim: that call's row length, (Q + 1) x width
+  int64_t ca_dim[2] = {};
+  GivenStage ca_given;             // its host candidates [B][Q][3]: as `given`, but of ca_given_cap bytes, replaced when a call needs more
+  size_t ca_given_cap = 0;
   // orl_batch_copy_envs (as the destination): the pair indices [2][n] on the device and in page-locked memory, grown on demand
   long long* copy_idx = nullptr;
   long long* h_copy_idx = nullptr;
@@ -181,6 +187,9 @@ template <int W> void release_horizons(orl_batch* b, float* out, int layout, int
 // k_network_capacity -> out [B][pitch] of the layout's type (ORL_CAPACITY_*); need: the batch's need table (null for ORL_CAPACITY_PATHS)
 template <int W> void network_capacity(orl_batch* b, void* out, const unsigned char* need, int layout);
 template <int W> void capacity_need(orl_batch* b, unsigned char* need);  // k_capacity_need -> need [N N][n_cls][round_up(K, 8)]
+// k_capacity_after -> out [B][pitch] int32 in `layout` (ORL_AFTER_*) for the Q candidates per env of `tab` (tstride int32 per env) of `source`
+template <int W> void capacity_after(orl_batch* b, int* out, const unsigned char* need, const int* tab, int tstride, int source, int j, int placement, int Q,
+                                     int layout);
 // k_persist in the form `ch` (the run's choice for the whole batch; use_spec: made for the attached specialisation library) over the
 // env range of view VP up to step `target` of this run, then k_rel_tail, on stream st
 template <int W> void persist(orl_batch* b, const orl::DevParams& VP, const PersistChoice& ch, bool use_spec, hipStream_t st, int pol, int target,

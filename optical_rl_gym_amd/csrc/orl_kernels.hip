@@ -18,6 +18,7 @@
 //   k_block_table, k_select_blocks  block actions: the first j fitting blocks of every row, their mask, an index -> an action (orl_blocks.h)  8 lanes per env
 //   k_release_horizons when each slot of the pending service's rows frees, from the release table (orl_horizon.h)  one wavefront per env, lanes over releases
 //   k_network_capacity (L, F) of every pair's paths, which (pair, class) cells fit, their marginals (orl_capacity.h)  one wavefront per env, lanes over all paths of one slot map
+//   k_capacity_after what each candidate placement of the pending service leaves of the capacity's class counts (orl_capacity_after.h)  one wavefront per env, per candidate only the paths that share a link
 //   k_path_features path-feature observation of the pending service (orl_path_obs.h)    8 lanes per env, rows striped over them
 //   k_link_features per-link feature observation of the pending service (orl_link_obs.h)  8 lanes per env, slot rows striped over them
 //               [what these three views share — and k_qos_matrix_obs of orl_api.hip with them — lives in orl_view.h]
@@ -2065,6 +2066,7 @@ __global__ void __launch_bounds__(256) k_obs8(DevParams P, int with_terminal) {
 #include "orl_blocks.h"  // k_block_table, k_select_blocks: DeepRMSA's (row, free block) action space for every slot-map family
 #include "orl_horizon.h"  // k_release_horizons: when each slot of the pending service's rows frees, per slot or per listed block
 #include "orl_capacity.h"  // k_network_capacity: every pair's paths on the env's whole slot map, and what still fits
+#include "orl_capacity_after.h"  // k_capacity_after: the capacity's class counts after each candidate placement of the pending service
 #include "orl_path_obs.h"  // k_path_features: the path-feature observation of the pending service (every slot-map family)
 #include "orl_link_obs.h"  // k_link_features: the per-link feature observation of the pending service (every slot-map family)
 #include "orl_qos_obs.h"  // (its kernel is the API unit's: here the LDS size of its wavefront alone)
@@ -2403,6 +2405,26 @@ template <int W> void network_capacity(orl_batch* b, void* out, const unsigned c
   }
   ORL_TK(b, "k_network_capacity");
 }
+// k_capacity_after (orl_capacity_after.h) into `out` ([B][pitch] int32 on the device) for the Q candidates per env of `tab` (tstride
+// int32 per env; source: ORL_AFTER_*): what capacity_after_plan says
+template <int W> void capacity_after(orl_batch* b, int* out, const unsigned char* need, const int* tab, int tstride, int source, int j, int placement, int Q,
+                                     int layout) {
+  const DevParams& VP = b->P;
+  const CapacityPlan pl = capacity_after_plan(VP, W, layout, Q);
+  const ViewShape sh = capacity_after_shape(VP, layout, Q);
+  if (pl.staged) {
+    if (pl.lds_bytes > kViewLdsDefault)
+      hipFuncSetAttribute((const void*)k_capacity_after<W, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+    hipLaunchKernelGGL((k_capacity_after<W, true>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, out, need, tab, tstride, source, j, placement, Q,
+                       layout, capacity_classes(VP), (int)sh.pitch, pl.wave_bytes);
+  } else {
+    if (pl.lds_bytes > kViewLdsDefault)
+      hipFuncSetAttribute((const void*)k_capacity_after<W, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+    hipLaunchKernelGGL((k_capacity_after<W, false>), dim3(pl.grid), dim3(pl.block), pl.lds_bytes, b->stream, VP, out, need, tab, tstride, source, j, placement, Q,
+                       layout, capacity_classes(VP), (int)sh.pitch, pl.wave_bytes);
+  }
+  ORL_TK(b, "k_capacity_after");
+}
 template <int W> void capacity_need(orl_batch* b, unsigned char* need) {
   const DevParams& VP = b->P;
   const i64 n = (i64)capacity_need_bytes(VP.N, VP.K, capacity_classes(VP));
@@ -2573,6 +2595,7 @@ template void link_features<ORL_W>(orl_batch*, float*);
 template void release_horizons<ORL_W>(orl_batch*, float*, int, int, int, int);
 template void network_capacity<ORL_W>(orl_batch*, void*, const unsigned char*, int);
 template void capacity_need<ORL_W>(orl_batch*, unsigned char*);
+template void capacity_after<ORL_W>(orl_batch*, int*, const unsigned char*, const int*, int, int, int, int, int, int);
 template void persist<ORL_W>(orl_batch*, const DevParams&, const PersistChoice&, bool, hipStream_t, int, int, int*, unsigned int*, unsigned int*, int);
 template void step2<ORL_W>(orl_batch*, int);
 template void agent_step<ORL_W>(orl_batch*, int, int);

@@ -275,3 +275,44 @@ inline CapacityPlan capacity_plan(const orl::DevParams& P, int W, int layout) {
   r.lds_bytes = (size_t)r.waves * r.wave_bytes;
   return r;
 }
+
+// capacity_after (orl_capacity_after.h): what each of Q candidate placements of the pending service leaves of the COUNTS class row.
+// Q: the candidates of the call — the rows of the route / core table, the rows of the block table times j, or the given count —
+// 1 .. ORL_AFTER_MAX_Q; the rows are Q + 1, the last one the baseline.  dim == 0: no such rows (QoSConstrainedRA, an unknown layout,
+// Q out of range).
+inline ViewShape capacity_after_shape(const orl::DevParams& P, int layout, int Q) {
+  ViewShape s = {0, 0, 0, 0, 4};
+  if (P.env_type == orl::ENV_QOS || Q < 1 || Q > ORL_AFTER_MAX_Q) return s;
+  const int64_t n_cls = capacity_classes(P);
+  switch (layout) {
+    case ORL_AFTER_CLASSES: s.rows = Q + 1; s.width = (int)n_cls; break;
+    case ORL_AFTER_TOTAL: s.rows = Q + 1; s.width = 1; break;
+    default: return s;
+  }
+  s.dim = (int64_t)s.rows * s.width;
+  s.pitch = (s.dim + 3) / 4 * 4;
+  return s;
+}
+// The launch of k_capacity_after: capacity_plan's rules — the most wavefronts per workgroup of 4, 2, 1 whose shares hold the fixed
+// terms and the maps within kViewLdsDefault; else one wavefront with all of it within kViewLdsMax; else the maps stay in global
+// memory and the same two rules go for the rest — with this kernel's fixed terms: the longest runs, 64 lanes' scratch of k8 bytes, the
+// class row twice, and for TOTAL the Q + 1 sums (capacity_after_fixed_bytes).  ok == 0: refused.
+inline CapacityPlan capacity_after_plan(const orl::DevParams& P, int W, int layout, int Q) {
+  CapacityPlan r = {};
+  const ViewShape sh = capacity_after_shape(P, layout, Q);
+  if (!sh.dim) return r;
+  const size_t fixed = capacity_after_fixed_bytes(P.N, P.K, capacity_classes(P), Q, layout == ORL_AFTER_TOTAL);
+  if (fixed > kViewLdsMax) return r;
+  const size_t maps = capacity_map_bytes(W, P.env_type == orl::ENV_RMCSA ? P.C : 1, P.E);
+  r.waves = view_waves(fixed + maps);
+  r.staged = r.waves != 0;
+  if (!r.waves && fixed + maps <= kViewLdsMax) { r.waves = 1; r.staged = true; }
+  if (!r.waves) r.waves = view_waves(fixed);
+  if (!r.waves) r.waves = 1;
+  r.ok = true;
+  r.block = 64 * r.waves;
+  r.grid = (unsigned)((P.B + r.waves - 1) / r.waves);
+  r.wave_bytes = (int)(fixed + (r.staged ? maps : 0));
+  r.lds_bytes = (size_t)r.waves * r.wave_bytes;
+  return r;
+}

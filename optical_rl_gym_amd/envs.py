@@ -1138,6 +1138,70 @@ class BatchedOpticalEnv:
                               lambda: self.network_capacity_shape(lay)[2], np.uint8 if lay == 1 else np.int32, fetch, out)
         return out.view(np.bool_) if out is not None and lay == 1 else out
 
+    # ---- capacity_after (include/orl.h, orl_batch_capacity_after): RMSA, DeepRMSA, RWA and RMCSA -------------------------------
+    AFTER_LAYOUTS = {"classes": 0, "total": 1}
+    AFTER_SOURCES = {"route": 0, "blocks": 1, "given": 2}
+    AFTER_MAX_CANDIDATES = 1024
+
+    def capacity_after_shape(self, source="route", layout="total", j=1, n_candidates=0):
+        """(Q, width, dim, pitch) of the capacity_after rows: Q candidates per env — k C' for "route", rows * j for "blocks",
+        n_candidates for "given" — and Q + 1 rows (the last is the baseline) of width n_cls ("classes") or 1 ("total"); dim =
+        (Q + 1) * width columns per env, rows of the device buffer pitch int32 apart."""
+        src = self._named_id("source", self.AFTER_SOURCES, source)
+        lay = self._named_id("layout", self.AFTER_LAYOUTS, layout)
+        q, w, d, p = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        self._ck(self.lib.orl_batch_capacity_after_shape(self._h, src, int(j), lay, int(n_candidates), C.byref(q), C.byref(w), C.byref(d), C.byref(p)))
+        return q.value, w.value, d.value, p.value
+
+    def capacity_after(self, source="route", layout="total", j=1, placement="first", candidates=None, fetch=True, out=None):
+        """What the network of every env would still carry if the PENDING service went to each of Q candidate placements, in one
+        launch on the device: int32 [num_envs, dim].  A candidate is (row, s, n): row = p * C' + c in the row order of the path
+        features (path p of the pending service's pair, core c), and the window of slots [s, s + n).  It is present iff 0 <= row <
+        k * C', p < n_paths[pair], n >= 1, s >= 0 and s + n <= S.  With A the env's slot maps and A - cand the same maps with the
+        window taken on every link of p in core c (free or not),
+            after(q)[r] = network_capacity("counts")[:n_cls] evaluated on A - cand_q
+        the ordered pairs with paths for which class r is not serviceable; -1 throughout for an absent candidate.  Row Q, one past the
+        last candidate, is the baseline on A itself.
+        "classes"  reshape(num_envs, Q + 1, n_cls): row q = after(q)
+        "total"    [num_envs, Q + 1]: the sum of a row over the classes, -1 for an absent candidate
+        Sources of the candidates:
+        "route"   the table route_spectrum (RMSA, RWA) or route_cores (RMCSA) last wrote: Q = k * C', candidate q = (q, column 0,
+                  column 2) of row q; a row on which nothing fits is absent
+        "blocks"  the table block_table(j) last wrote (every family): Q = rows * j, candidate q = r * j + b — the column of the block
+                  mask, the index select_blocks decodes — placed at the block's lower ("first") or upper end ("last")
+        "given"   `candidates`: an int array [num_envs, Q, 3] of (row, s, n) from the host (not graph-capturable)
+        A table that was never written is refused; a stale one is the caller's business.  At most AFTER_MAX_CANDIDATES per env.
+        This is NOT the counts of a forked child after its step: a step also runs the releases that fall due before the next
+        arrival.  Env state and flags are not touched.  `out` (C-contiguous int32 [num_envs, dim]) receives the rows instead of a
+        fresh array.  fetch=False only queues the launch on the batch's stream (graph-capturable after a first call of that source
+        and layout) — read the rows in place with device_tensor("capacity_after_classes" / "capacity_after_total") and, say,
+        torch.argmin over "total" written into column 0 of device_tensor("actions") before select_blocks(blocks=None)."""
+        src = self._named_id("source", self.AFTER_SOURCES, source)
+        lay = self._named_id("layout", self.AFTER_LAYOUTS, layout)
+        g, nq = None, 0
+        if candidates is not None:
+            if src != 2:
+                raise ValueError("candidates belong to the \"given\" source, not %r" % (source,))
+            g = np.asarray(candidates)
+            if g.ndim != 3 or g.shape[0] != self.num_envs or g.shape[2] != 3 or g.dtype.kind not in "iu":
+                raise ValueError("candidates must be an int array of shape (%d, Q, 3), got %s %r" % (self.num_envs, g.dtype, g.shape))
+            g = np.ascontiguousarray(g, np.int32)
+            nq = g.shape[1]
+        elif src == 2:
+            raise ValueError("the \"given\" source needs candidates: an int array [num_envs, Q, 3] of (row, s, n)")
+        jj, pl = int(j), self._named_id("placement", self.BLOCK_PLACEMENTS, placement)
+        sh = self.capacity_after_shape(src, lay, jj, nq)
+        self._keep_given = g  # (alive until the call returns: the library copies it before it does)
+        res = self._view_rows(lambda p: self._ck(self.lib.orl_batch_capacity_after(self._h, src, jj, pl, lay, None if g is None else g.ctypes.data, nq, p)),
+                              lambda: sh[2], np.int32, fetch, out)
+        return res
+
+    def _capacity_after_last(self, layout):
+        """(dim, pitch) of the rows the last capacity_after call of `layout` left on the device, as the library holds them"""
+        d, p = C.c_int64(), C.c_int64()
+        self._ck(self.lib.orl_batch_capacity_after_last(self._h, layout, C.byref(d), C.byref(p)))
+        return d.value, p.value
+
     # ---- zero-copy device views (an agent on the same GPU: no PCIe in the loop) -------------------------
     _BUFFERS = {"actions": (0, "<i4", 4), "reward": (1, "<f8", 0), "done": (2, "|u1", 0), "info": (3, "<f8", -1),
                 "obs": (4, "<f8", -2), "terminal_obs": (5, "<f8", -2), "paths": (6, "<i4", 0), "action_mask": (7, "|b1", None),
@@ -1146,6 +1210,8 @@ class BatchedOpticalEnv:
                 "block_table": (13, "<i4", None), "block_mask": (14, "|b1", None), "release_horizons": (15, "<f4", None)}
     # the network capacity's rows, one buffer per layout (a table of their own beside the I/O arrays and the pending service's views)
     _CAPACITY_BUFFERS = {"path_capacity": (16, "<i4", None), "serviceable": (17, "|b1", None), "capacity_counts": (18, "<i4", None)}
+    # capacity_after's rows, one buffer per layout, at the last call's pitch
+    _AFTER_BUFFERS = {"capacity_after_classes": (19, "<i4", None), "capacity_after_total": (20, "<i4", None)}
     # The views of the pending service: [num_envs, dim] rows of the last call at the device pitch.  name -> (the message while no
     # call has been made, (dim, pitch in items) of those rows, item size).  Every mask layout and every j of the path features has
     # a buffer of its own: a view taken after a "joint" call keeps showing the joint rows (as the last "joint" call left them)
@@ -1173,13 +1239,18 @@ class BatchedOpticalEnv:
               "serviceable": ("no serviceable matrix yet: call network_capacity(\"serviceable\") (fetch=False only queues it) first",
                               lambda self: self.network_capacity_shape(1)[2:], 1),
               "capacity_counts": ("no capacity counts yet: call network_capacity(\"counts\") (fetch=False only queues it) first",
-                                  lambda self: self.network_capacity_shape(2)[2:], 4)}
+                                  lambda self: self.network_capacity_shape(2)[2:], 4),
+              "capacity_after_classes": ("no capacity_after rows yet: call capacity_after(layout=\"classes\") (fetch=False only queues it) first",
+                                         lambda self: self._capacity_after_last(0), 4),
+              "capacity_after_total": ("no capacity_after totals yet: call capacity_after(layout=\"total\") (fetch=False only queues it) first",
+                                       lambda self: self._capacity_after_last(1), 4)}
 
     def device_array(self, name):
         """The batch's device-resident I/O array `name` as an object with `__cuda_array_interface__` (what
         `torch.as_tensor(x, device="cuda")` and CuPy consume without a copy).  Write actions into "actions", call
         `step(None, fetch=False)`, `sync()`, read "reward" / "done" / "info" / "obs" in place."""
-        which, typestr, cols = self._BUFFERS[name] if name in self._BUFFERS else self._CAPACITY_BUFFERS[name]
+        which, typestr, cols = (self._BUFFERS[name] if name in self._BUFFERS else
+                                self._CAPACITY_BUFFERS[name] if name in self._CAPACITY_BUFFERS else self._AFTER_BUFFERS[name])
         ptr, n = C.c_void_p(), C.c_int64()
         self._ck(self.lib.orl_batch_device_buffer(self._h, which, C.byref(ptr), C.byref(n)))
         strides = None

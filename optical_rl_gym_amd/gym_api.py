@@ -413,11 +413,27 @@ class _NetworkCapacity:
         return row[:width - n * n].copy(), row[width - n * n:].reshape(n, n)
 
 
-class RMSAEnv(_NetworkCapacity, _ReleaseHorizons, _BlockActions, _SpectrumRules, _SingleEnv):
+class _CapacityAfter:
+    """RMSAEnv, DeepRMSAEnv, RWAEnv and RMCSAEnv: what each candidate placement of the pending service leaves the network."""
+
+    def capacity_after(self, source="route", layout="total", j=1, placement="first", candidates=None):
+        """The env's row of the batch's capacity_after (BatchedOpticalEnv.capacity_after), computed on the device: "classes" int32
+        [Q + 1, n_cls], "total" int32 [Q + 1]; row q is what candidate q leaves (-1: the candidate is absent), the last row the
+        baseline.  `candidates` ("given"): an int array [Q, 3] of (row, s, n).  Not the counts after a step, which also runs the
+        releases due before the next arrival."""
+        b = self.batch
+        cand = None if candidates is None else np.asarray(candidates)[None]
+        row = b.capacity_after(source, layout, j, placement, cand)[0]
+        if b._named_id("layout", b.AFTER_LAYOUTS, layout) == 1:
+            return row
+        return row.reshape(-1, b.capacity_after_shape(source, layout, j, 0 if cand is None else cand.shape[1])[1])
+
+
+class RMSAEnv(_CapacityAfter, _NetworkCapacity, _ReleaseHorizons, _BlockActions, _SpectrumRules, _SingleEnv):
     BATCH_CLS = BatchedRMSAEnv
 
 
-class DeepRMSAEnv(_NetworkCapacity, _ReleaseHorizons, _SingleEnv):
+class DeepRMSAEnv(_CapacityAfter, _NetworkCapacity, _ReleaseHorizons, _SingleEnv):
     BATCH_CLS = BatchedDeepRMSAEnv
     POLICY_SAP = "SAP"
 
@@ -445,7 +461,7 @@ class DeepRMSAEnv(_NetworkCapacity, _ReleaseHorizons, _SingleEnv):
         return action // self.j, action % self.j
 
 
-class RWAEnv(_NetworkCapacity, _ReleaseHorizons, _BlockActions, _SpectrumRules, _SingleEnv):
+class RWAEnv(_CapacityAfter, _NetworkCapacity, _ReleaseHorizons, _BlockActions, _SpectrumRules, _SingleEnv):
     BATCH_CLS = BatchedRWAEnv
     DEFAULT_SLOTS = 80
     DEFAULT_REJECTION = True
@@ -488,7 +504,7 @@ class RWAEnv(_NetworkCapacity, _ReleaseHorizons, _BlockActions, _SpectrumRules, 
         return d
 
 
-class RMCSAEnv(_NetworkCapacity, _ReleaseHorizons, _BlockActions, _SingleEnv):
+class RMCSAEnv(_CapacityAfter, _NetworkCapacity, _ReleaseHorizons, _BlockActions, _SingleEnv):
     BATCH_CLS = BatchedRMCSAEnv
     POLICY_SAP = "SAP_BM_FC_FF"
 

@@ -430,6 +430,18 @@ class MultiDeviceBatch:
         C-contiguous) every shard writes its own rows."""
         return self._view_rows(lambda r, **kw: self.shards[r].network_capacity(layout, **kw), fetch, out)
 
+    def capacity_after_shape(self, source="route", layout="total", j=1, n_candidates=0):
+        return self.shards[0].capacity_after_shape(source, layout, j, n_candidates)
+
+    def capacity_after(self, source="route", layout="total", j=1, placement="first", candidates=None, fetch=True, out=None):
+        """BatchedOpticalEnv.capacity_after of every shard, rows in env order; `candidates` ([num_envs, Q, 3]) is split by env; with
+        `out` (int32 [num_envs, dim], C-contiguous) every shard writes its own rows."""
+        cand = None if candidates is None else np.asarray(candidates)
+        if cand is not None and (cand.ndim != 3 or cand.shape[0] != self.num_envs):
+            raise ValueError("candidates must be an int array of shape (%d, Q, 3), got %r" % (self.num_envs, cand.shape))
+        return self._view_rows(lambda r, **kw: self.shards[r].capacity_after(
+            source, layout, j, placement, None if cand is None else self._cut(cand, r), **kw), fetch, out)
+
     def link_features_shape(self):
         return self.shards[0].link_features_shape()
 
